@@ -3,6 +3,7 @@
 NMS-10 (+ OSD-p on the syndrome-failed frames) at Eb/N0 = 2.5 dB on synthetic AWGN frames.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload nms10_osd2|nms10_osd0|nms10|nms10_fs2|nms10_pb3|surface_nms]
+                    [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one device-resident batch of frames:
 NMS-10 -> error counters + failed-frame compaction -> OSD-p on the failures -> OSD counters, all on the GPU
@@ -16,10 +17,13 @@ BEFORE touching any GPU, relays rank 0's JSON line and fails if any rank fails o
 Frames shard across ranks (weak scaling: fixed per-GPU batch); the only collective is ONE all-reduce of the
 error counters per measurement, inside the timed region.
 
-Prints ONE JSON line (rank 0) with the contract fields plus "roofline" (dominant kernel, HIP-event timed),
-"cpu_baseline" (the C oracle = scalar port of the same math on this host's cores, bounded sample, N = 1 only;
-with its FER and, as `reference_equivalent`, the dense NumPy mirror of the reference's formulation on one core)
-and "fer_vs_cpu" (north_star acceptance: FER within +-5 % of the float CPU path in the same run).
+Prints ONE JSON line (rank 0) with the contract fields, the config and the FER of the timed steps.  A plain run does
+nothing else: set-up, warm-up, the K timed steps, the outputs (--dump-outputs DIR: what the last timed step returned,
+a fixed sample of its frames, as DIR/<name>.npy) and the line.  With --full the line also holds "overlap" (the same
+steps on three streams), "roofline" (dominant kernel, timed in a HIP-event pass of its own), "cpu_baseline" (the C
+oracle = scalar port of the same math on this host's cores, bounded sample, N = 1 only; with its FER and, as
+`reference_equivalent`, the dense NumPy mirror of the reference's formulation on one core) and "fer_vs_cpu"
+(north_star acceptance: FER within +-5 % of the float CPU path in the same run; the run fails outside it).
 """
 from __future__ import annotations
 
@@ -54,6 +58,10 @@ WORKLOADS = {
     "surface_nms": (None, 131072, "stage-5 call surface: ms_test.Decoding_model(inputs, labels), NumPy in, lists of rows out"),
 }
 OSD_ALGO = {"nms10_fs2": 1, "nms10_pb3": 2}
+# --dump-outputs: frames (surface_nms: buffer rows) of the last step written at most, and the seed of the sample drawn when there
+# are more (16 384 frames of the pipeline's outputs are ~19 MB, well inside the 64 MB the dump may take)
+DUMP_FRAMES = 16384
+DUMP_SEED = 20241020
 
 
 def parse_args(argv=None):
@@ -91,6 +99,13 @@ def parse_args(argv=None):
                          "only how searches are cut into chunks and handed on); recorded in the line's config")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams of the timed region; >1 keeps several batches in flight (batch i runs on stream i mod N)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the event-timed roofline pass, the three-stream "
+                         "overlap pass and the CPU baseline with its FER comparison (surface_nms: the reference's 1000-frame batch, "
+                         "the device-part timings and the CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy (float32 / "
+                         "float64; a fixed, seeded sample of the frames when the batch is larger than %d)" % DUMP_FRAMES)
     return ap.parse_args(argv)
 
 
@@ -182,6 +197,56 @@ def make_frames(dec, B, seed, snr_db=SNR_DB):
         y[s:e] = (1 - 2 * cw) * (1 + sigma * noise)
         labels[s:e] = dec.pack_bits(cw.to(torch.uint8))
     return y, labels
+
+
+def dump_sample(n):
+    """Indices (sorted) of the rows --dump-outputs writes out of n: all of them, or a fixed, seeded sample of DUMP_FRAMES."""
+    import numpy as np
+    if n <= DUMP_FRAMES:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_FRAMES, replace=False))
+
+
+def write_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every array; only float32 / float64 arrays, at most 64 MB in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def dump_pipeline(out_dir, pipe, runs):
+    """--dump-outputs of the pipeline workloads: what BatchPipeline.run() of the last timed step left in the buffers its caller
+    reads, for the sampled frames of that step's batch.  `frame` = the frames' indices in the batch; soft / hard / fail = the NMS
+    outputs (hard words unpacked to one 0/1 per bit); counters = that step's int64[8] (the buffer accumulates over the `runs`
+    runs of this batch, all alike); with OSD, osd_* = the failure list's entries of the sampled frames (osd_frame = their
+    indices, osd_cw unpacked like hard, osd_metric, osd_best, osd_ntep)."""
+    import numpy as np
+    import torch
+    frame = dump_sample(pipe.B)
+    sel = torch.from_numpy(frame).to(pipe.dec.device)
+
+    def bits(words):
+        return np.unpackbits(np.ascontiguousarray(words.cpu().numpy()).view(np.uint8), axis=1, bitorder="little").astype(np.float32)
+
+    out = {"frame": frame.astype(np.float64),
+           "soft": pipe.soft[sel].cpu().numpy().astype(np.float32),
+           "hard": bits(pipe.hard[sel]),
+           "fail": pipe.fail[sel].cpu().numpy().astype(np.float32),
+           "counters": (pipe.counters() // runs).cpu().numpy().astype(np.float64)}
+    if pipe.osd_order is not None:
+        nf = int(pipe.count.cpu()[0])
+        index = pipe.index[:nf].cpu().numpy()
+        pos = np.flatnonzero(np.isin(index, frame))
+        p = torch.from_numpy(pos).to(pipe.dec.device)
+        out.update(osd_frame=index[pos].astype(np.float64), osd_cw=bits(pipe.cw[p]),
+                   osd_metric=pipe.metric[p].cpu().numpy().astype(np.float32),
+                   osd_best=pipe.best[p].cpu().numpy().astype(np.float64),
+                   osd_ntep=pipe.ntep[p].cpu().numpy().astype(np.float64))
+    write_outputs(out_dir, out)
 
 
 def pmc_profile(kernel, workload, B):
@@ -339,9 +404,9 @@ def run_surface(args):
     dec = default_decoder(code)
     alpha = float(softplus32(STORED_NMS1_WEIGHT))
     big = args.batch or WORKLOADS["surface_nms"][1]
-    steps = max(2, min(args.steps, 20))
+    steps = args.steps
     lines = {}
-    for B in (1000, big):
+    for B in (1000, big) if args.full else (big,):
         y_d, lab_d = make_frames(dec, B, seed=20241020 + B, snr_db=args.snr)
         inputs = y_d.cpu().numpy()
         labels = dec.unpack_bits(lab_d).cpu().numpy()                    # [B,128] int64, one integer per bit as the reference holds them
@@ -354,7 +419,21 @@ def run_surface(args):
         torch.cuda.synchronize()
         call_ms = 1e3 * (time.perf_counter() - t0) / steps
         nfail = len(model.last_failed_index)
-        # the device part alone (inputs resident): NMS, counters, failure list, rows of the failures
+        row_bytes = nfail * (T_ITERS + 1) * 512
+        lines[B] = dict(frames=B, frames_per_s=B / (call_ms * 1e-3), call_ms=call_ms, failed_frames=nfail, fer=fer, ber=float(ber),
+                        undetected=und, buffer_rows=len(bi), trajectory_bytes_per_input_frame=row_bytes / B)
+        if B == big and args.dump_outputs:
+            # the last call's return values; of the row buffers (RowBuffer: one array, rows repeated `repeat` times) the
+            # sampled rows, buffer_row = their indices
+            rows = dump_sample(len(bi))
+            write_outputs(args.dump_outputs, {
+                "fer": np.array([fer], dtype=np.float64), "ber": np.array([ber], dtype=np.float64),
+                "undetected": np.array([und], dtype=np.float64), "buffer_row": rows.astype(np.float64),
+                "buffer_inputs": np.asarray(bi.array[rows // bi.repeat], dtype=np.float32),
+                "buffer_labels": np.asarray(bl.array[rows // bl.repeat], dtype=np.float32)})
+        if not args.full:
+            continue
+        # (--full) the device part alone (inputs resident): NMS, counters, failure list, rows of the failures
         e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         lab_bits = dec.pack_bits(torch.from_numpy(labels).to(dec.device))
         dev_ms, rows_ms = [], []
@@ -373,14 +452,9 @@ def run_surface(args):
             dec.nms(y_d, T_ITERS, alpha, want_traj=True, want_soft=False, want_hard=False, want_fail=False)      # round 3's surface: [T][B][n] for every frame
         e[3].record(); torch.cuda.synchronize()
         full_traj_ms = e[0].elapsed_time(e[3]) / steps
-        row_bytes = nfail * (T_ITERS + 1) * 512
-        lines[B] = dict(frames=B, frames_per_s=B / (call_ms * 1e-3), call_ms=call_ms, device_ms=float(np.median(dev_ms)),
-                        traj_rows_kernel_ms=float(np.median(rows_ms)), failed_frames=nfail, fer=fer, ber=float(ber), undetected=und,
-                        buffer_rows=len(bi), trajectory_bytes_per_input_frame=row_bytes / B,
+        lines[B].update(device_ms=float(np.median(dev_ms)), traj_rows_kernel_ms=float(np.median(rows_ms)),
                         full_trajectory_bytes_per_input_frame=T_ITERS * 512, full_trajectory_kernel_ms=full_traj_ms)
     b = lines[big]
-    rows_ms = b["traj_rows_kernel_ms"]
-    nbytes = b["failed_frames"] * (512 + (T_ITERS + 1) * 512)          # channel row in, T + 1 rows out per failed frame
     res = {
         "metric": "decoded frames/sec through the reference call surface Decoding_model(inputs, labels), NMS-10 @ 2.5 dB",
         "timed_region": "wall clock around model(inputs, labels): host conversion + H2D + kernels + D2H of the failed frames' rows + list building",
@@ -389,13 +463,17 @@ def run_surface(args):
         "config": {"workload": f"surface_nms -- {WORKLOADS['surface_nms'][2]}", "code": "CCSDS (128,64)", "snr_db": args.snr,
                    "nms_iterations": T_ITERS, "alpha": alpha, "frames_per_call": big,
                    "note": "NOT the headline metric: host buffers cross PCIe in both directions inside the timed region"},
-        "surface": {"reference_batch_1000": lines[1000], f"batch_{big}": b},
-        "roofline": {"bound": "hbm", "kernel": "nms_qc16_kernel<ROWS> (ldpc_nms_traj_rows)", "achieved": nbytes / (rows_ms * 1e-3) / 1e9,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": nbytes / (rows_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
-                     "avg_launch_ms": rows_ms, "algorithmic_bytes_per_launch": float(nbytes),
-                     "note": "the listed frames decoded again with their T + 1 rows written in the reference's buffer order; issue-bound like the decoder"},
+        "surface": {f"batch_{big}": b},
     }
-    if not args.no_cpu_baseline:
+    if args.full:
+        rows_ms = b["traj_rows_kernel_ms"]
+        nbytes = b["failed_frames"] * (512 + (T_ITERS + 1) * 512)          # channel row in, T + 1 rows out per failed frame
+        res["surface"] = {"reference_batch_1000": lines[1000], f"batch_{big}": b}
+        res["roofline"] = {"bound": "hbm", "kernel": "nms_qc16_kernel<ROWS> (ldpc_nms_traj_rows)", "achieved": nbytes / (rows_ms * 1e-3) / 1e9,
+                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": nbytes / (rows_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
+                           "avg_launch_ms": rows_ms, "algorithmic_bytes_per_launch": float(nbytes),
+                           "note": "the listed frames decoded again with their T + 1 rows written in the reference's buffer order; issue-bound like the decoder"}
+    if args.full and not args.no_cpu_baseline:
         from oracle import np_oracle
         y_np = y_d[:1000].cpu().numpy() if big >= 1000 else inputs
         cw_np = dec.unpack_bits(lab_d[:1000].contiguous()).cpu().numpy()
@@ -543,19 +621,23 @@ def run_rank(args):
         if runs:
             distinct += p.counters() // runs
     d = allreduce_counters(distinct).cpu().numpy().astype(np.int64)
+    if args.dump_outputs and rank == 0:
+        last = (args.steps - 1) % nb
+        dump_pipeline(args.dump_outputs, pipes[last], len(range(last, args.steps, nb)))
 
-    # kernel durations for the roofline: a SEPARATE pass with the library's HIP events around the hot kernels (none inside
-    # the timed region; recording five events costs ~17 us of a 0.3 ms step)
-    nev = max(1, min(args.event_steps, TIMING_SLOTS))
-    for k in range(nev):
-        pipes[k % nb].run(timing_slot=k)
-    torch.cuda.synchronize()
-    timed_slots = list(range(nev))
+    # (--full) kernel durations for the roofline: a SEPARATE pass with the library's HIP events around the hot kernels (none
+    # inside the timed region; recording five events costs ~17 us of a 0.3 ms step)
+    if args.full:
+        nev = max(1, min(args.event_steps, TIMING_SLOTS))
+        for k in range(nev):
+            pipes[k % nb].run(timing_slot=k)
+        torch.cuda.synchronize()
+        timed_slots = list(range(nev))
 
-    # informative second pass (not the headline): the same steps with three batches in flight on three streams,
+    # (--full) informative second pass (not the headline): the same steps with three batches in flight on three streams,
     # where the NMS of one batch overlaps the OSD kernels (and the kernel tails) of another
     overlap = None
-    if args.streams == 1 and args.overlap_pass and order is not None and nb >= 3:
+    if args.full and args.streams == 1 and args.overlap_pass and order is not None and nb >= 3:
         ost = [torch.cuda.current_stream(), torch.cuda.Stream(), torch.cuda.Stream()]
         for k in range(6):
             with torch.cuda.stream(ost[k % 3]):
@@ -615,7 +697,7 @@ def run_rank(args):
     if overlap is not None:
         res["overlap"] = overlap
     fer_ok = True
-    if rank == 0:
+    if rank == 0 and args.full:
         # roofline of the dominant kernel from the HIP events recorded on the launch stream
         tm = np.array([pipes[0].timing(k) for k in timed_slots])   # (slots are per context: any pipeline reads them)
         nms_name = {1: "nms_generic_kernel", 2: "nms_qc16_kernel"}[dec.nms_kernel]
@@ -662,6 +744,7 @@ def run_rank(args):
             res["fer_vs_cpu"] = {"gpu_fer_end_to_end": fg, "cpu_fer_end_to_end": fc, "fer_rel_diff_vs_cpu": rel,
                                  "two_sigma_of_rel_diff": two_sigma, "gpu_frame_errors": eg, "cpu_frame_errors": ec,
                                  "judged": enough, "within_5_percent": bool(fer_ok) if enough else None}
+    if rank == 0:
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -6,7 +6,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_osd_pb.py tests/test_gpu_graph
 rc=$?; echo "[tests] rc=$rc"; tail -n 5 $O/${TAG}_tests.log
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "tests hit their limit: stopping"; exit 1; fi
 for SNR in "$@"; do
-  timeout -k 10 300 python bench.py --workload nms10_pb3 --snr $SNR --steps 12 --warmup 4 --no-cpu-baseline --no-overlap-pass > $O/${TAG}_bench_snr$SNR.json 2> $O/${TAG}_bench_snr$SNR.err
+  timeout -k 10 300 python bench.py --workload nms10_pb3 --snr $SNR --steps 12 --warmup 4 --full --no-cpu-baseline --no-overlap-pass > $O/${TAG}_bench_snr$SNR.json 2> $O/${TAG}_bench_snr$SNR.err
   rc=$?; echo "[bench $SNR] rc=$rc"
   if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "bench hit its limit: stopping"; exit 1; fi
   python - <<PY

@@ -69,7 +69,7 @@ def test_bench_launcher_path_and_refusal():
     # under a launcher environment (what torchrun sets): the distributed branch with one rank
     env = _env(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), LDPC_BENCH_FORCE_DIST="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--batch", "16384",
-                        "--no-cpu-baseline", "--no-overlap-pass"], capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--no-cpu-baseline", "--no-overlap-pass"], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["rccl_ranks"] == 1 and line["config"]["global_frames_per_step"] == 16384

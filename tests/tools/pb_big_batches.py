@@ -2,7 +2,7 @@
 for the chunk kernel's tail rule, under several of its settings), every run twice: where a search is handed on depends on timing, the
 results must not.  (~80 s, most of it the oracle.)"""
 import os, sys, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
 import numpy as np, torch
 from oracle import c_oracle, np_oracle
 from short_ldpc_decoding_osd_amd import Code, _lib

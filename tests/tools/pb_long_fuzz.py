@@ -2,7 +2,7 @@
 SNR 1.0-3.5 dB, orders 1-3, default schedule and random ones (budgets, chunk targets, tail rule), the default route and the
 front-end-inside option; every count, stop reason, winner and metric exact.  (The long form of tests/test_gpu_fuzz.py.)"""
 import os, sys, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
 import numpy as np, torch
 from oracle import c_oracle, np_oracle
 from short_ldpc_decoding_osd_amd import Code, _lib

@@ -1,7 +1,7 @@
 """GPU box: python tests/tools/pb_tie_stress.py -- PB-OSD on finely to coarsely quantised channel values (equal sums everywhere) under three
 hand-over schedules, every result against the C oracle (8640 frame decodes; the long form of test_pb_ties_under_schedules)."""
 import os, sys
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
 import numpy as np, torch
 from oracle import c_oracle, np_oracle
 from short_ldpc_decoding_osd_amd import Code

@@ -3,7 +3,7 @@ pipeline against the C oracle on fresh random batches until the time is up: rand
 exact zeros and ties sprinkled in, front-end results in caller buffers or not (order 2 then runs the fused front-end + scan kernel),
 plus the failed-frame rows of ldpc_nms_traj_rows.  Everything bit for bit.  (The long form of tests/test_gpu_fuzz.py.)"""
 import os, sys, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
 import numpy as np, torch
 from oracle import c_oracle, np_oracle
 from short_ldpc_decoding_osd_amd import Code, _lib
