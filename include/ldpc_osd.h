@@ -298,8 +298,8 @@ int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label
 
 /* ---------------------------------------------------------------------------------------
  * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H):
- * DL_OSD_Testing_serial/ordered_statistics_decoding.py.  The trained networks of that stage stay
- * on the host; these entry points do the per-frame sort / elimination / candidate scan.
+ * DL_OSD_Testing_serial/ordered_statistics_decoding.py and nn_net.py: the per-frame sort / elimination /
+ * candidate scan, the scan with the sliding-window early stop, and the bit-wise CNN.
  * ------------------------------------------------------------------------------------- */
 
 /* Host: the TEPs of one order pattern, osd.error_pattern_gen (:81-98): pattern[s] flips inside
@@ -337,6 +337,51 @@ int ldpc_hosd_search(ldpc_ctx *ctx, const float *d_order_llr, const float *d_met
                      const int32_t *d_block_off, int32_t nblk, const uint64_t *d_label_bits, float *d_block_min,
                      int32_t *d_block_arg, float *d_truth, uint64_t *d_cw, float *d_metric, int32_t *d_best,
                      void *stream);
+
+/* The block scan of ldpc_hosd_search with the sliding-window early stop of the reference's lazy loop
+ * (sliding_osd :187-218, sliding_window_ops :140-151; the classifier is Predict_outlier_light,
+ * nn_net.py:136-149).  Same frame inputs and TEP blocks as ldpc_hosd_search (block minima and first-minimum
+ * keys bit-identical to it), plus:
+ *   win          the window width (1..15, nblk >= win)
+ *   soft_margin  stop when p1 > soft_margin (compared in double)
+ *   fcn_weights  HOST f32: dense1 kernel [win+1][win+1] then dense2 kernel [win+1][2], no biases;
+ *                n_weights must be (win+1)^2 + 2(win+1).  Copied by value into the kernel arguments.
+ *   group        blocks scanned together before the decisions they allow are replayed; 0 = the default
+ *                (blocks until 256 TEPs and the first window); results do not depend on it.
+ * The decisions: the first `win` blocks, then block by block; decision k (window = blocks k..k+win-1)
+ * is skipped for k > 0 when block k+win-1's minimum is > global_min; otherwise the classifier runs on
+ * the ascending window with float(k) appended -- h = x.W1 and z = h.W2, each output a sequential f32
+ * sum over its input index starting from the first product; p1 = e1/(e0+e1), e_c = expf(z_c - max(z))
+ * -- global_min = min(global_min, min(window)), and the frame stops when p1 > soft_margin.
+ * Per-frame outputs (all nullable):
+ *   d_deep_limit [F] i32  blocks the reference evaluates (windows = deep_limit - win + 1;
+ *                          its complexity is acc_block_size[deep_limit])
+ *   d_global_min [F] f32
+ *   d_truth [F] f32, d_success [F] u8 (global_min == truth): need d_label_bits [F][2] u64   (:181-183, :213)
+ *   d_cw [F][2] u64, d_metric [F] f32, d_best [F] i32: first minimum over blocks 0..deep_limit-1
+ *   d_teps_evaluated [F] i32  TEPs the kernel scanned (>= the reference's complexity by the
+ *                          speculative part of the last group)                                      */
+int ldpc_hosd_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F, const uint8_t *d_lri,
+                      const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps, const int32_t *d_block_off,
+                      int32_t nblk, int32_t win, double soft_margin, const float *fcn_weights, int32_t n_weights,
+                      int32_t group, const uint64_t *d_label_bits, int32_t *d_deep_limit, float *d_global_min,
+                      float *d_truth, uint8_t *d_success, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                      int32_t *d_teps_evaluated, void *stream);
+
+/* The bit-wise CNN of the DL-OSD stage, conv_bitwise.call (nn_net.py:174-197): for every frame f and
+ * bit v, the sequence rows[f][0..L-1][v] (the retest layout of ldpc_nms_traj_rows, row 0 = channel
+ * values, L = T+1 >= 7; preprocessing_inputs :198-211 without the transpose) through
+ *   Conv1D 1->8, Conv1D 8->4, Conv1D 4->2 (kernel 3, valid, no bias), Flatten, Dense(2(L-6) -> 1) + bias.
+ * (The model's PReLU is never applied in call.)
+ * weights: HOST f32, packed in Keras layouts: conv1 [3][1][8], conv2 [3][8][4], conv3 [3][4][2],
+ *   dense kernel [2(L-6)][1] (Flatten order: position-major, channel-minor), dense bias [1] --
+ *   n_weights = 24 + 96 + 24 + 2(L-6) + 1.  Copied by value into the kernel arguments.
+ * Float order: every conv output is a sequential f32 sum over the flattened (tap, in-channel) index,
+ * tap-major, starting from the first product; the dense output the sequential sum over the flattened
+ * index starting from the first product, then + bias.  No fused multiply-adds.
+ *   d_rows [F][L][n] f32, d_out [F][n] f32.                                                          */
+int ldpc_dia_cnn(ldpc_ctx *ctx, const float *d_rows, int64_t F, int32_t L, const float *weights, int32_t n_weights,
+                 float *d_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * One batch through the whole path with a single host call: the body of the reference drivers'

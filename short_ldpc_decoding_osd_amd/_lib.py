@@ -21,7 +21,7 @@ SYMBOLS = (
     "ldpc_ctx_create", "ldpc_ctx_destroy", "ldpc_ctx_nms_kernel", "ldpc_ctx_get_pb_tuning", "ldpc_ctx_set_pb_tuning",
     "ldpc_nms_decode", "ldpc_nms_traj_rows", "ldpc_eval_counts", "ldpc_compact", "ldpc_pack_bits", "ldpc_unpack_bits",
     "ldpc_osd_reserve", "ldpc_osd_reserve_stream", "ldpc_osd_release_stream", "ldpc_osd_index_errors", "ldpc_osd_ge", "ldpc_osd_front", "ldpc_osd_search", "ldpc_osd_decode", "ldpc_osd_tep_eval", "ldpc_osd_counts",
-    "ldpc_hosd_pattern_teps", "ldpc_hosd_front", "ldpc_hosd_search",
+    "ldpc_hosd_pattern_teps", "ldpc_hosd_front", "ldpc_hosd_search", "ldpc_hosd_sliding", "ldpc_dia_cnn",
     "ldpc_pipeline_run", "ldpc_pipeline_timing",
 )
 
@@ -113,6 +113,9 @@ def load():
         "ldpc_hosd_pattern_teps": (i64, [i32, pi32, pi32, C.POINTER(C.c_uint8)]),
         "ldpc_hosd_front": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, vp]),
         "ldpc_hosd_search": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ldpc_hosd_sliding": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, C.c_double, C.POINTER(f32), i32, i32,
+                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ldpc_dia_cnn": (C.c_int, [vp, vp, i64, i32, C.POINTER(f32), i32, vp, vp]),
         "ldpc_pipeline_run": (C.c_int, [vp, C.POINTER(Pipeline), vp]),
         "ldpc_pipeline_timing": (C.c_int, [vp, i32, C.POINTER(f32)]),
     }

@@ -87,6 +87,7 @@ struct __attribute__((aligned(16))) HSearchLds {
     u64 keys[RUNS ? kHosdRunBlocks : kHosdMaxBlocks];   // per block: (metric bits << 32) | TEP index, minimum = first minimum
     u64 hgL, hgM, mrb0, DL0, best, cw[2];
     int ticket, heavy;
+    float truth;          // the label's metric (hosd_frame_setup with labels)
     unsigned char o[128]; // original bit index of updated position p
     int boff[RUNS ? kHosdRunBlocks + 1 : 1];            // block_off, once per workgroup
     unsigned short tl[RUNS ? kHosdLdsTeps : 2];         // the TEP table, once per workgroup: x | y << 6 | weight << 12
@@ -111,6 +112,79 @@ __device__ __forceinline__ void hosd_apply(const LDS &L, uchar4 s, u64 &DL, u64 
     if (s.w > 0) { DL ^= L.Mcol[s.x]; DM ^= 1ull << s.x; }
     if (s.w > 1) { DL ^= L.Mcol[s.y]; DM ^= 1ull << s.y; }
     if (s.w > 2) { DL ^= L.Mcol[s.z]; DM ^= 1ull << s.z; }
+}
+
+// Per-frame set-up shared by the block scans (hosd_search_kernel, hosd_sliding_kernel): values in updated order, hard
+// decisions, M columns, block keys reset, byte LUTs, the order-0 discrepancies DL0 / DM0 and (with labels) the label's metric
+// (L.truth, and truth[f] where truth is given).
+// On return every thread sees the LUTs, the M columns and the keys of blocks 0..nblk-1 reset to ~0.
+template <class LDS>
+__device__ __forceinline__ void hosd_frame_setup(LDS &L, const float *__restrict__ xo, const float *__restrict__ xm, long long f,
+                                                 const unsigned char *__restrict__ lri, const unsigned char *__restrict__ uidx,
+                                                 const u64 *__restrict__ Mrows, int nblk, const u64 *__restrict__ label,
+                                                 float *__restrict__ truth, u64 &DL0, u64 &DM0)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // ---- phase 0: values in updated order (:172-176), hard decisions, M columns, key reset --------
+    if (tid < 128) {
+        const int o = lri[f * 128 + uidx[f * 128 + tid]];
+        const float m = xm[f * 128 + o];
+        L.o[tid] = (unsigned char)o;
+        L.w[tid] = __builtin_fabsf(m);
+        const u64 hg = __ballot(!(m > 0.0f));                       // order_hard_original (:180)
+        if (wave == 0) { if (lane == 0) L.hgL = hg; }
+        else {
+            const u64 h0 = __ballot(!(xo[f * 128 + o] > 0.0f));      // initial_mrb (:186-187)
+            if (lane == 0) { L.hgM = hg; L.mrb0 = h0; }
+        }
+    } else if (wave == 2) {
+        L.Mcol[lane] = transpose64(Mrows[f * 64 + lane], lane);
+    } else {
+        if (lane == 0) { L.ticket = 0; L.best = ~0ull; L.cw[0] = 0; L.cw[1] = 0; }
+    }
+    for (int b = tid; b < nblk; b += 256) L.keys[b] = ~0ull;
+    __syncthreads();
+    // ---- phase 1: byte LUTs (four per wavefront), order-0 discrepancy of the LRB part (:155,:159) --
+    build_byte_luts<4>(&L.lut[4 * wave], &L.w[32 * wave], lane);
+    if (wave == 0) {
+        const u64 d = wave_xor64(((L.mrb0 >> lane) & 1) ? L.Mcol[lane] : 0ull) ^ L.hgL;
+        if (lane == 0) L.DL0 = d;
+    }
+    __syncthreads();
+    DL0 = L.DL0; DM0 = L.mrb0 ^ L.hgM;
+    if (label && wave == 1) {
+        const u64 l0 = label[f * 2], l1 = label[f * 2 + 1];
+        const int o1 = L.o[lane], o2 = L.o[64 + lane];
+        const u64 labL = __ballot(((o1 < 64 ? l0 : l1) >> (o1 & 63)) & 1);
+        const u64 labM = __ballot(((o2 < 64 ? l0 : l1) >> (o2 & 63)) & 1);
+        const float t = hosd_cost(L, labL ^ L.hgL, labM ^ L.hgM);     // (:181-183)
+        if (lane == 0) { if (truth) truth[f] = t; L.truth = t; }
+    }
+}
+
+// Wave 0 of a frame's workgroup, after the keys of the candidate blocks have been folded into L.best: the first minimum's
+// metric and TEP index and its codeword in the original bit order (ldpc_hosd_search's d_metric / d_best / d_cw).
+template <class LDS>
+__device__ __forceinline__ void hosd_frame_best(LDS &L, const uchar4 *__restrict__ teps, long long f, u64 DL0, u64 DM0,
+                                                u64 *__restrict__ cw_out, float *__restrict__ metric_out, int *__restrict__ best_out)
+{
+    const int lane = threadIdx.x & 63;
+    const u64 k = L.best;
+    const bool none = k == ~0ull;
+    if (lane == 0) {
+        if (metric_out) metric_out[f] = none ? INFINITY : __int_as_float((int)(k >> 32));
+        if (best_out) best_out[f] = none ? -1 : (int)(unsigned)k;
+    }
+    if (cw_out) {
+        u64 DL = DL0, DM = DM0;
+        if (!none) hosd_apply(L, teps[(unsigned)k], DL, DM);
+        const u64 bitsL = DL ^ L.hgL, bitsM = DM ^ L.hgM;
+        const int o1 = L.o[lane], o2 = L.o[64 + lane];
+        if ((bitsL >> lane) & 1) atomicOr(&L.cw[o1 >> 6], 1ull << (o1 & 63));
+        if ((bitsM >> lane) & 1) atomicOr(&L.cw[o2 >> 6], 1ull << (o2 & 63));
+        wave_fence();
+        if (lane < 2) cw_out[f * 2 + lane] = L.cw[lane];
+    }
 }
 
 // One frame per 256-thread workgroup: the four wavefronts share the frame's LUTs.  Every thread scans ITS OWN run of
@@ -160,41 +234,8 @@ __global__ __launch_bounds__(256) void hosd_search_kernel(const float *__restric
     }
 
     for (long long f = blockIdx.x; f < F; f += gridDim.x) {
-        // ---- phase 0: values in updated order (:172-176), hard decisions, M columns, key reset --------
-        if (tid < 128) {
-            const int o = lri[f * 128 + uidx[f * 128 + tid]];
-            const float m = xm[f * 128 + o];
-            L.o[tid] = (unsigned char)o;
-            L.w[tid] = __builtin_fabsf(m);
-            const u64 hg = __ballot(!(m > 0.0f));                       // order_hard_original (:180)
-            if (wave == 0) { if (lane == 0) L.hgL = hg; }
-            else {
-                const u64 h0 = __ballot(!(xo[f * 128 + o] > 0.0f));      // initial_mrb (:186-187)
-                if (lane == 0) { L.hgM = hg; L.mrb0 = h0; }
-            }
-        } else if (wave == 2) {
-            L.Mcol[lane] = transpose64(Mrows[f * 64 + lane], lane);
-        } else {
-            if (lane == 0) { L.ticket = 0; L.best = ~0ull; L.cw[0] = 0; L.cw[1] = 0; }
-        }
-        for (int b = tid; b < nblk; b += 256) L.keys[b] = ~0ull;
-        __syncthreads();
-        // ---- phase 1: byte LUTs (four per wavefront), order-0 discrepancy of the LRB part (:155,:159) --
-        build_byte_luts<4>(&L.lut[4 * wave], &L.w[32 * wave], lane);
-        if (wave == 0) {
-            const u64 d = wave_xor64(((L.mrb0 >> lane) & 1) ? L.Mcol[lane] : 0ull) ^ L.hgL;
-            if (lane == 0) L.DL0 = d;
-        }
-        __syncthreads();
-        const u64 DL0 = L.DL0, DM0 = L.mrb0 ^ L.hgM;
-        if (truth && wave == 1) {
-            const u64 l0 = label[f * 2], l1 = label[f * 2 + 1];
-            const int o1 = L.o[lane], o2 = L.o[64 + lane];
-            const u64 labL = __ballot(((o1 < 64 ? l0 : l1) >> (o1 & 63)) & 1);
-            const u64 labM = __ballot(((o2 < 64 ? l0 : l1) >> (o2 & 63)) & 1);
-            const float t = hosd_cost(L, labL ^ L.hgL, labM ^ L.hgM);     // (:181-183)
-            if (lane == 0) truth[f] = t;
-        }
+        u64 DL0, DM0;
+        hosd_frame_setup(L, xo, xm, f, lri, uidx, Mrows, nblk, label, truth, DL0, DM0);
         if constexpr (RUNS) {
             // ---- phase 2: the scan: this thread's run, a flush per block boundary -----------------------------
             int b = b0;
@@ -256,24 +297,144 @@ __global__ __launch_bounds__(256) void hosd_search_kernel(const float *__restric
         }
         if (mine != ~0ull) atomicMin(&L.best, mine);
         __syncthreads();
-        if (wave == 0) {
-            const u64 k = L.best;
-            const bool none = k == ~0ull;
-            if (lane == 0) {
-                if (metric_out) metric_out[f] = none ? INFINITY : __int_as_float((int)(k >> 32));
-                if (best_out) best_out[f] = none ? -1 : (int)(unsigned)k;
+        if (wave == 0) hosd_frame_best(L, teps, f, DL0, DM0, cw_out, metric_out, best_out);
+        __syncthreads();
+    }
+}
+
+// ---- the block scan with the reference's sliding-window early stop (sliding_osd :187-218, sliding_window_ops :140-151) ----
+// One frame per 256-thread workgroup.  The blocks are scanned in GROUPS of consecutive blocks, all threads on one group
+// (per-thread runs of consecutive TEPs as above, TEPs read from the table in global memory); then lane 0 replays every
+// window decision the group's block minima make possible and the workgroup stops scanning the frame as soon as the
+// classifier fires.  Blocks of a group past the stopping block are speculative work: they count in d_teps_evaluated but
+// in no result, so the results do not depend on the group size.
+constexpr int kSlideMaxWin = 15;         // window + the block index: at most 16 classifier inputs
+constexpr int kSlideGroupTeps = 256;     // default group: consecutive blocks until the group holds one TEP per thread
+
+struct SlideFcnArg {                     // Predict_outlier_light, by value: dense1 [win+1][win+1], dense2 [win+1][2]
+    float w1[(kSlideMaxWin + 1) * (kSlideMaxWin + 1)];
+    float w2[(kSlideMaxWin + 1) * 2];
+};
+
+struct SlideLds {
+    int boff[kHosdMaxBlocks + 1];        // block_off, once per workgroup
+    float x[kSlideMaxWin + 1];           // classifier input: the sorted window, then the window index
+    float h[kSlideMaxWin + 1];           // dense1 output
+    int done, deep;
+};
+
+__device__ __forceinline__ float key_metric(u64 k) { return k == ~0ull ? INFINITY : __int_as_float((int)(k >> 32)); }
+
+// p1 of the classifier on S.x[0..win]: h = x . W1, z = h . W2, each output a sequential f32 sum over the input index
+// (starting from the first product), then softmax with the maximum subtracted: p1 = e1 / (e0 + e1), e_c = expf(z_c - max).
+__device__ __forceinline__ float slide_p1(SlideLds &S, int win, const SlideFcnArg &w)
+{
+    const int d = win + 1;
+    for (int j = 0; j < d; ++j) {
+        float acc = S.x[0] * w.w1[j];
+        for (int i = 1; i < d; ++i) acc = acc + S.x[i] * w.w1[i * d + j];
+        S.h[j] = acc;
+    }
+    float z0 = S.h[0] * w.w2[0], z1 = S.h[0] * w.w2[1];
+    for (int j = 1; j < d; ++j) {
+        z0 = z0 + S.h[j] * w.w2[2 * j];
+        z1 = z1 + S.h[j] * w.w2[2 * j + 1];
+    }
+    const float m = z1 > z0 ? z1 : z0;
+    const float e0 = expf(z0 - m), e1 = expf(z1 - m);
+    return e1 / (e0 + e1);
+}
+
+__global__ __launch_bounds__(256) void hosd_sliding_kernel(const float *__restrict__ xo, const float *__restrict__ xm, long long F,
+                                                           const unsigned char *__restrict__ lri,
+                                                           const unsigned char *__restrict__ uidx, const u64 *__restrict__ Mrows,
+                                                           const uchar4 *__restrict__ teps, const int *__restrict__ block_off,
+                                                           int nblk, int win, double margin, SlideFcnArg fcn, int group,
+                                                           const u64 *__restrict__ label, int *__restrict__ deep_out,
+                                                           float *__restrict__ gmin_out, float *__restrict__ truth,
+                                                           unsigned char *__restrict__ success, u64 *__restrict__ cw_out,
+                                                           float *__restrict__ metric_out, int *__restrict__ best_out,
+                                                           int *__restrict__ nteps_out)
+{
+    __shared__ HSearchLds<false> L;
+    __shared__ SlideLds S;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    for (int b = tid; b <= nblk; b += 256) S.boff[b] = block_off[b];
+    __syncthreads();
+
+    for (long long f = blockIdx.x; f < F; f += gridDim.x) {
+        u64 DL0, DM0;
+        hosd_frame_setup(L, xo, xm, f, lri, uidx, Mrows, nblk, label, truth, DL0, DM0);
+        int k = 0, deep = win;           // (lane 0) the next window decision, blocks evaluated so far in the reference's sense
+        float gmin = INFINITY;           // (lane 0) global_min
+        int g0 = 0, g1 = 0;
+        for (;;) {
+            // ---- the group [g0, g1): `group` blocks, or blocks until kSlideGroupTeps TEPs and the first window
+            if (group > 0) {
+                g1 = g0 + group < nblk ? g0 + group : nblk;
+            } else {
+                g1 = g0 + 1;
+                while (g1 < nblk && (g1 < win || S.boff[g1] - S.boff[g0] < kSlideGroupTeps)) ++g1;
             }
-            if (cw_out) {
-                u64 DL = DL0, DM = DM0;
-                if (!none) hosd_apply(L, teps[(unsigned)k], DL, DM);
-                const u64 bitsL = DL ^ L.hgL, bitsM = DM ^ L.hgM;
-                const int o1 = L.o[lane], o2 = L.o[64 + lane];
-                if ((bitsL >> lane) & 1) atomicOr(&L.cw[o1 >> 6], 1ull << (o1 & 63));
-                if ((bitsM >> lane) & 1) atomicOr(&L.cw[o2 >> 6], 1ull << (o2 & 63));
-                wave_fence();
-                if (lane < 2) cw_out[f * 2 + lane] = L.cw[lane];
+            const int t0 = S.boff[g0], nt = S.boff[g1] - t0, per = (nt + 255) / 256;
+            const int run0 = t0 + (tid * per < nt ? tid * per : nt), run1 = t0 + (tid * per + per < nt ? tid * per + per : nt);
+            if (run0 < run1) {
+                int lo = g0, hi = g1;    // the block that holds TEP run0: the last b with boff[b] <= run0 (blocks may be empty)
+                while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (S.boff[mid] <= run0) lo = mid; else hi = mid; }
+                int b = lo;
+                float best = INFINITY;
+                int bestt = 0;
+                for (int t = run0; t < run1; ++t) {
+                    while (t >= S.boff[b + 1]) {
+                        if (best < INFINITY) atomicMin(&L.keys[b], ((u64)(unsigned)__float_as_int(best) << 32) | (unsigned)bestt);
+                        best = INFINITY;
+                        ++b;
+                    }
+                    u64 DL = DL0, DM = DM0;
+                    hosd_apply(L, teps[t], DL, DM);
+                    const float c = hosd_cost(L, DL, DM);
+                    if (c < best) { best = c; bestt = t; }                     // ascending t: first minimum
+                }
+                if (best < INFINITY) atomicMin(&L.keys[b], ((u64)(unsigned)__float_as_int(best) << 32) | (unsigned)bestt);
             }
+            __syncthreads();
+            // ---- lane 0: every decision whose window lies in the blocks scanned so far (:193-209)
+            if (tid == 0) {
+                bool stop = false;
+                for (; !stop && k <= nblk - win && k + win <= g1; ++k) {
+                    deep = k + win;
+                    if (k != 0 && key_metric(L.keys[k + win - 1]) > gmin) continue;       // :203-204
+                    for (int i = 0; i < win; ++i) {                                     // the window, ascending
+                        const float v = key_metric(L.keys[k + i]);
+                        int j = i;
+                        while (j > 0 && S.x[j - 1] > v) { S.x[j] = S.x[j - 1]; --j; }
+                        S.x[j] = v;
+                    }
+                    S.x[win] = (float)k;
+                    const float p1 = slide_p1(S, win, fcn);
+                    gmin = S.x[0] < gmin ? S.x[0] : gmin;                               // min(global_min, window.min())
+                    stop = (double)p1 > margin;
+                }
+                S.done = stop || g1 >= nblk;
+                S.deep = deep;
+            }
+            __syncthreads();
+            if (S.done) break;
+            g0 = g1;
         }
+        // ---- per-frame results; the best candidate among the blocks the reference evaluates (0 .. deep_limit-1)
+        const int dl = S.deep;
+        if (tid == 0) {
+            if (deep_out) deep_out[f] = dl;
+            if (gmin_out) gmin_out[f] = gmin;
+            if (success) success[f] = gmin == L.truth;                                 // :213
+            if (nteps_out) nteps_out[f] = S.boff[g1] - S.boff[0];
+        }
+        u64 mine = ~0ull;
+        for (int b = tid; b < dl; b += 256) mine = L.keys[b] < mine ? L.keys[b] : mine;
+        if (mine != ~0ull) atomicMin(&L.best, mine);
+        __syncthreads();
+        if (wave == 0) hosd_frame_best(L, teps, f, DL0, DM0, cw_out, metric_out, best_out);
         __syncthreads();
     }
 }
@@ -352,6 +513,38 @@ int ldpc_hosd_search(ldpc_ctx *ctx, const float *d_order_llr, const float *d_met
                        reinterpret_cast<const uchar4 *>(d_teps), d_block_off, (int)nblk,
                        reinterpret_cast<const u64 *>(d_label_bits), d_block_min, d_block_arg, d_truth,
                        reinterpret_cast<u64 *>(d_cw), d_metric, d_best);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+int ldpc_hosd_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F, const uint8_t *d_lri,
+                      const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps, const int32_t *d_block_off,
+                      int32_t nblk, int32_t win, double soft_margin, const float *fcn_weights, int32_t n_weights,
+                      int32_t group, const uint64_t *d_label_bits, int32_t *d_deep_limit, float *d_global_min,
+                      float *d_truth, uint8_t *d_success, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                      int32_t *d_teps_evaluated, void *stream)
+{
+    if (!ctx || F < 0 || win < 1 || win > kSlideMaxWin || nblk < win || group < 0 || !fcn_weights ||
+        (F > 0 && (!d_order_llr || !d_metric_llr || !d_lri || !d_uidx || !d_M || !d_teps || !d_block_off)))
+        return fail(LDPC_E_ARG, "ldpc_hosd_sliding: bad arguments (win %d, nblk %d, group %d)", (int)win, (int)nblk, (int)group);
+    const int d = win + 1;
+    if (n_weights != d * d + 2 * d)
+        return fail(LDPC_E_ARG, "ldpc_hosd_sliding: %d classifier weights, a window of %d takes %d", (int)n_weights, (int)win,
+                    d * d + 2 * d);
+    if ((d_truth || d_success) && !d_label_bits) return fail(LDPC_E_ARG, "ldpc_hosd_sliding: d_truth / d_success need d_label_bits");
+    if (!ctx->hosd_ok)
+        return fail(LDPC_E_UNSUPPORTED, "H-form OSD kernels need n=128, m=k=64; this code is n=%d m=%d k=%d", ctx->code.n,
+                    ctx->code.m, ctx->code.k);
+    if (nblk > kHosdMaxBlocks) return fail(LDPC_E_UNSUPPORTED, "ldpc_hosd_sliding: %d TEP blocks, at most %d", nblk, kHosdMaxBlocks);
+    if (F == 0) return LDPC_OK;
+    SlideFcnArg w = {};
+    for (int i = 0; i < d * d; ++i) w.w1[i] = fcn_weights[i];
+    for (int i = 0; i < 2 * d; ++i) w.w2[i] = fcn_weights[d * d + i];
+    hipLaunchKernelGGL(hosd_sliding_kernel, dim3(grid_for(F, 1)), dim3(256), 0, (hipStream_t)stream, d_order_llr, d_metric_llr,
+                       (long long)F, d_lri, d_uidx, reinterpret_cast<const u64 *>(d_M), reinterpret_cast<const uchar4 *>(d_teps),
+                       d_block_off, (int)nblk, (int)win, soft_margin, w, (int)group, reinterpret_cast<const u64 *>(d_label_bits),
+                       d_deep_limit, d_global_min, d_truth, d_success, reinterpret_cast<u64 *>(d_cw), d_metric, d_best,
+                       d_teps_evaluated);
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
 }

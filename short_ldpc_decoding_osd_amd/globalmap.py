@@ -3,9 +3,14 @@
 FS_OSD/globalmap.py:28-50).  The decoders read the same keys the reference reads:
 'code_parameters', 'num_iterations', 'selected_decoder_type', 'order_limit',
 'termination_num_threshlod' (sic), 'd_min', 'tau_psc', 'pb_osd', 'fs_osd', 'convention_osd',
-'miracle_view'.  Unlike the reference a missing key raises KeyError instead of printing.
+'miracle_view'; the DL-OSD stage's keys (DL_OSD_Testing_serial/globalmap.py:28-54, ``stage="DL"``):
+'convention_path', 'termination_threshold', 'threshold_sum', 'training_snr', 'segment_num',
+'soft_margin', 'decoding_length', 'sliding_win_width'.  Unlike the reference a missing key raises
+KeyError instead of printing.
 """
 from __future__ import annotations
+
+import os
 
 map = {}  # noqa: A001  (name kept from the reference)
 
@@ -46,9 +51,59 @@ def global_setting(argv, stage="PB"):
     set_map('termination_num_threshlod', 100)
     set_map('miracle_view', False)
     set_map('convention_osd', False)
-    if stage.upper() == "FS":
+    if stage.upper() == "DL":
+        set_map('print_interval', 100)
+        set_map('record_interval', 100)
+        set_map('convention_path', False)
+        set_map('termination_threshold', 500)
+        set_map('threshold_sum', 3)
+        set_map('training_snr', 2.7)
+        set_map('segment_num', 6)
+        set_map('soft_margin', 0.9)
+        set_map('decoding_length', 30)
+        set_map('sliding_win_width', 5)
+    elif stage.upper() == "FS":
         set_map('fs_osd', True)
         set_map('d_min', 14)
         set_map('tau_psc', 30)
     else:
         set_map('pb_osd', True)
+
+
+# ---- DL-OSD stage: where the training stage left its checkpoints and statistics (DL_OSD_Testing_serial/globalmap.py:78-117).
+# 'dl_training_dir' (default: the reference's '../DL_Training_serial/') roots them.
+def _training_root():
+    return get_map('dl_training_dir', '../DL_Training_serial/')
+
+
+def _snr_info():
+    t = get_map('training_snr')
+    return '/' + str(t) + '-' + str(t) + 'dB/'
+
+
+def secure_segment_threshold():
+    """:57-76 (segment sizes, MRB boundaries)."""
+    from .ordered_statistics_decoding import secure_segment_threshold as sst
+    return sst()
+
+
+def logistic_setting_model(indicator_list, prefix_list):
+    """:78-95 -> [ckpts_dir, 'ldpc-ckpt', 'latest'] of the selected network (the directory is created)."""
+    prefix = next(prefix_list[i] for i, e in enumerate(indicator_list) if e)
+    ckpts_dir = _training_root() + 'ckpts/' + prefix + _snr_info() + str(get_map('num_iterations')) + 'th' + '/'
+    os.makedirs(ckpts_dir, exist_ok=True)
+    return [ckpts_dir, 'ldpc-ckpt', 'latest']
+
+
+def set_predict_model(DIA):   # noqa: N803
+    """:96-117 -> [ckpts_dir, 'ldpc-ckpt', 'latest'] of the sliding-window classifier (the directory is created)."""
+    nn_type = 'fcn' if DIA else 'benchmark'
+    ckpts_dir = (_training_root() + 'ckpts/' + nn_type + _snr_info() + str(get_map('num_iterations')) + 'th/len-'
+                 + str(get_map('decoding_length')) + '-order-' + str(get_map('threshold_sum')) + '/')
+    os.makedirs(ckpts_dir, exist_ok=True)
+    return [ckpts_dir, 'ldpc-ckpt', 'latest']
+
+
+def pattern_log_dir():
+    """Directory of ``dist-error-pattern-<nn>.pkl`` (nn_testing.py:96-99: the 2.7-2.7 dB statistics)."""
+    return _training_root() + 'log/' + get_map('selected_decoder_type') + '/2.7-2.7dB/'

@@ -2,13 +2,14 @@
 LDPC_128/DL_OSD_Testing_serial/ordered_statistics_decoding.py (class ``osd``) plus the pattern helpers
 of nn_testing.py:65-82,120-148 and globalmap.py:57-76 that feed it.
 
-The stage's trained networks (the bit-wise CNN that refines the LLRs and the sliding-window
-classifier ``fcn``) stay ordinary Python callables on the host, as in the reference; everything
-per frame and per TEP -- ascending reliability sort, elimination of the permuted H, MRB bookkeeping,
-re-encoding and weighted-distance scan of every TEP block -- runs in the HIP kernels behind
+Everything per frame and per TEP -- ascending reliability sort, elimination of the permuted H, MRB
+bookkeeping, re-encoding and weighted-distance scan of every TEP block -- runs in the HIP kernels behind
 ``ldpc_hosd_front`` / ``ldpc_hosd_search``.  ``sliding_osd`` evaluates ALL blocks of the decoding
 path on the device (the reference evaluates them lazily) and then replays the reference's window
-loop on the block minima, so decisions, window counts and complexity figures are the reference's.
+loop on the block minima with a host callable ``fcn``, so decisions, window counts and complexity
+figures are the reference's.  ``sliding_osd_device`` runs the window loop inside the scan
+(``ldpc_hosd_sliding``, the classifier's weights from ``nn_net.Predict_outlier_light``): a frame stops
+being scanned when the classifier fires.
 
 Only the live path of the reference is mirrored (``Testing_OSD`` -> ``sliding_osd``, nn_testing.py:214);
 ``execute_osd`` / ``best_estimating`` / ``collect_tep`` are never called there.
@@ -238,6 +239,34 @@ class osd:   # noqa: N801  (name kept from the reference)
         res["success"] = decided
         self.last = res
         return success_dec, failure_dec, windows_sum, complexity_sum
+
+    def sliding_osd_device(self, fcn, input_list, inputs, labels, tep_info, group=0):
+        """``sliding_osd`` with the window loop on the device (``ldpc_hosd_sliding``): the same return value; ``fcn`` must
+        be an ``nn_net.Predict_outlier_light`` (its weights travel to the kernel).  ``inputs`` (the ordering values) may
+        be a device tensor.  ``self.last`` keeps the per-frame arrays: deep_limit, global_min, truth, success, cw,
+        metric, best, teps (TEPs scanned)."""
+        win = GL.get_map('sliding_win_width')
+        if getattr(fcn, "sliding_win_width", None) != win:
+            raise ValueError("sliding_osd_device: fcn must be a Predict_outlier_light of the 'sliding_win_width' window")
+        teps_list, acc_block_size = tep_info
+        dec = _dec()
+        list_length = GL.get_map('num_iterations') + 1
+        if isinstance(inputs, torch.Tensor):
+            order = inputs.to(device=dec.device, dtype=torch.float32).contiguous()
+        else:
+            order = torch.from_numpy(np.ascontiguousarray(inputs, dtype=np.float32)).to(dec.device)
+        metric = torch.from_numpy(np.ascontiguousarray(np.asarray(input_list, dtype=np.float32)[0::list_length])).to(dec.device)
+        lab = dec.pack_bits(torch.from_numpy(np.ascontiguousarray(labels).astype(np.uint8)).to(dec.device))
+        teps, off = self._device_blocks(dec, teps_list)
+        front = dec.hosd_front(order)
+        out = dec.hosd_sliding(order, metric, front, teps, off, win, GL.get_map('soft_margin'), fcn.packed(), label_bits=lab,
+                               group=group)
+        res = {k: v.cpu().numpy() for k, v in out.items() if v is not None}
+        deep = res["deep_limit"].astype(np.int64)
+        self.last = res
+        success = int(res["success"].sum())
+        return (success, len(deep) - success, int((deep - win + 1).sum()),
+                int(np.asarray(acc_block_size, dtype=np.int64)[deep].sum()))
 
     def unpack_codewords(self, cw):
         """[F,2] packed words -> [F,128] 0/1 (original bit order)."""

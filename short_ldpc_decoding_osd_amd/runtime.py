@@ -316,6 +316,58 @@ class Decoder:
                                            _ptr(out["best"]), self._stream()), "ldpc_hosd_search")
         return out
 
+    def hosd_sliding(self, order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights, label_bits=None,
+                     group=0, want_best=True):
+        """``hosd_search`` with the reference's sliding-window early stop: the blocks are scanned in groups of ``group``
+        consecutive blocks (0 = the library's default; results do not depend on it) and a frame stops when the classifier
+        (``fcn_weights``: dense1 [win+1,win+1] then dense2 [win+1,2], packed f32) fires with p1 > soft_margin.  Returns
+        dict(deep_limit[F] int32, global_min[F], truth[F], success[F] bool, cw[F,2], metric[F], best[F] (first minimum over
+        the blocks the reference evaluates), teps[F] int32 (TEPs scanned, speculative ones included))."""
+        self._chk(order_llr, torch.float32, (self.n,), "order_llr")
+        self._chk(metric_llr, torch.float32, (self.n,), "metric_llr")
+        lri, uidx, M = front[:3]
+        F = order_llr.shape[0]
+        if metric_llr.shape[0] != F or lri.shape[0] != F:
+            raise ValueError("order_llr, metric_llr and the front-end results must hold the same frames")
+        self._chk(teps, torch.uint8, (4,), "teps")
+        if block_off.dtype != torch.int32 or block_off.device != self.device or block_off.dim() != 1 or block_off.numel() < 1:
+            raise ValueError("block_off: expected a 1-D int32 tensor [nblk+1] on the device")
+        w = np.ascontiguousarray(np.asarray(fcn_weights, dtype=np.float32).reshape(-1))
+        nblk = block_off.numel() - 1
+        lab = label_bits is not None
+        out = dict(deep_limit=self.empty((F,), torch.int32), global_min=self.empty((F,), torch.float32),
+                   truth=self.empty((F,), torch.float32) if lab else None,
+                   success=self.empty((F,), torch.bool) if lab else None,
+                   cw=self.empty((F, 2), torch.int64) if want_best else None,
+                   metric=self.empty((F,), torch.float32) if want_best else None,
+                   best=self.empty((F,), torch.int32) if want_best else None,
+                   teps=self.empty((F,), torch.int32))
+        _lib.check(self.L.ldpc_hosd_sliding(self._ctx, _ptr(order_llr), _ptr(metric_llr), F, _ptr(lri), _ptr(uidx), _ptr(M),
+                                            _ptr(teps), _ptr(block_off), nblk, int(win), float(soft_margin),
+                                            w.ctypes.data_as(C.POINTER(C.c_float)), w.size, int(group), _ptr(label_bits),
+                                            _ptr(out["deep_limit"]), _ptr(out["global_min"]), _ptr(out["truth"]),
+                                            _ptr(out["success"]), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
+                                            _ptr(out["teps"]), self._stream()), "ldpc_hosd_sliding")
+        return out
+
+    def dia_cnn(self, rows, weights, out=None):
+        """The bit-wise CNN (conv_bitwise) on retest rows ``[F, L, n]`` (or ``[F*L, n]`` with ``L`` taken from the
+        weight count) -> refined values [F, n].  ``weights``: the packed f32 vector of ``nn_net.conv_bitwise.packed()``."""
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+        L = (w.size - 24 - 96 - 24 - 1) // 2 + 6
+        if rows.dim() == 2:
+            if rows.shape[0] % L:
+                raise ValueError(f"rows: {rows.shape[0]} rows are not whole trajectories of {L}")
+            rows = rows.reshape(rows.shape[0] // L, L, rows.shape[1])
+        if rows.dtype != torch.float32 or rows.device != self.device or rows.dim() != 3 or rows.shape[2] != self.n \
+                or not rows.is_contiguous():
+            raise ValueError(f"rows: expected a contiguous float32 [F, L, {self.n}] tensor on {self.device}")
+        F = rows.shape[0]
+        out = self.empty((F, self.n), torch.float32) if out is None else out
+        _lib.check(self.L.ldpc_dia_cnn(self._ctx, _ptr(rows), F, rows.shape[1], w.ctypes.data_as(C.POINTER(C.c_float)), w.size,
+                                       _ptr(out), self._stream()), "ldpc_dia_cnn")
+        return out
+
     def osd_counts(self, cw, label_bits, index=None, count=None, ntep=None, counts=None, F=None):
         """counts[3] += {frames, frames_wrong, teps_total}; labels are looked up through index."""
         F = cw.shape[0] if F is None else F
