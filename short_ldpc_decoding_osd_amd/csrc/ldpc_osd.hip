@@ -274,8 +274,8 @@ __global__ __launch_bounds__(64) void osd_search2_kernel(const float *__restrict
 
 // ---------------------------------------------------------------------------------------
 // Order-2 scan, second form (the one the launcher uses when the wave_rol probe succeeded):
-//  * pairing by ROTATION: in round r = 1..32 lane l meets lane (l -+ r) mod 64, whose row of P' and weight
-//    arrive by three `wave_rol:1` DPP moves of a rotating copy -- no v_readlane (8 issue cycles each, six per
+//  * pairing by ROTATION: in round r = 1..32 lane l meets lane (l -+ r) mod 64, whose low word of P' and weight
+//    arrive by two `wave_rol:1` DPP moves of a rotating copy -- no v_readlane (8 issue cycles each, six per
 //    round in the triangular pairing above) and no selects; rounds 1..31 cover every unordered pair once per
 //    lane, round 32 pairs l with l +- 32 and only lanes < 32 count;
 //  * persistent workgroups (one wavefront each) stride over the frames, and the global inputs of frame
@@ -283,16 +283,17 @@ __global__ __launch_bounds__(64) void osd_search2_kernel(const float *__restrict
 //    frame f is scanned, so the ~2 us of dependent global latency of the prologue is hidden;
 //  * everything else (two-stage scan with the exact prefix bound, survivor ring, rank-ordered ties) as above.
 // ---------------------------------------------------------------------------------------
-// LDS of the rotation scan: the byte LUT and the survivor ring, exactly 10 KiB -> 16 workgroups = 4 wavefronts per SIMD
-// (the scan is occupancy-sensitive: 1.75x the time at half the residency).  The parity weights are only needed while the
-// LUT is built and the codeword words only after the last survivor batch, so both borrow the ring's memory.
+// LDS of the rotation scan: the byte LUT, the survivor ring and the rows of P', 9.5 KiB -> 16 workgroups = 4 wavefronts per
+// SIMD (the scan is occupancy-sensitive: 1.75x the time at half the residency).  The parity weights are only needed while
+// the LUT is built and the codeword words only after the last survivor batch, so both borrow the ring's memory.
 struct __attribute__((aligned(16))) Search2rLds {
     float lut[8][256];   // lut[b][v] = sum of |y'[64+8b+t]| over the set bits t of v, ascending t
-    uint4 q[128];        // survivors: D.lo, D.hi, prefix metric bits, r * 64 + lane
+    uint2 q[128];        // survivors: prefix metric bits, r * 64 + lane (the candidate is rebuilt from P)
+    u64 P[64];           // rows of P' (survivor batches rebuild D = d0 ^ P[l] ^ P[partner])
     __device__ __forceinline__ float *wpar() { return reinterpret_cast<float *>(q); }           // [64], before the scan
     __device__ __forceinline__ u64 *cw() { return reinterpret_cast<u64 *>(q) + 32; }            // [2], after the scan
 };
-static_assert(sizeof(Search2rLds) == 10240, "LDS budget of the rotation scan");
+static_assert(sizeof(Search2rLds) <= 10240, "LDS budget of the rotation scan");
 
 __device__ __forceinline__ float cost2r(const Search2rLds &L, float mrb, u64 D)
 {
@@ -304,26 +305,65 @@ __device__ __forceinline__ float cost2r(const Search2rLds &L, float mrb, u64 D)
 
 __device__ __forceinline__ int wave_rot1(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x134, 0xF, 0xF, true); }
 
-__device__ __forceinline__ void search2r_finish_batch(const Search2rLds &L, uint4 e, bool valid, int dir, const int *__restrict__ base2,
+__device__ __forceinline__ void search2r_finish_batch(const Search2rLds &L, uint2 e, bool valid, int dir, u64 d0, const int *__restrict__ base2,
                                                       float &best, int &bi, int &bj, u64 &bestD)
 {
     if (!valid) return;
-    const u64 D = ((u64)e.y << 32) | e.x;
-    float acc = __uint_as_float(e.z);
+    const int r = (int)(e.y >> 6), l = (int)(e.y & 63), m = (l - dir * r) & 63;
+    const u64 D = d0 ^ L.P[l] ^ L.P[m];
+    float acc = __uint_as_float(e.x);
     acc = acc + lut_byte<2>(L.lut, D); acc = acc + lut_byte<3>(L.lut, D); acc = acc + lut_byte<4>(L.lut, D);
     acc = acc + lut_byte<5>(L.lut, D); acc = acc + lut_byte<6>(L.lut, D); acc = acc + lut_byte<7>(L.lut, D);
     if (!(acc <= best)) return;
-    const int r = (int)(e.w >> 6), l = (int)(e.w & 63), m = (l - dir * r) & 63;
     const int ci = l < m ? l : m, cj = l < m ? m : l;
     // equal metrics are ordered by table rank (practically never taken)
     if (acc < best || tep2_rank(ci, cj, base2) < tep2_rank(bi, bj, base2)) { best = acc; bi = ci; bj = cj; bestD = D; }
 }
 
+// Stage-1 state of the rotation scan between rounds (wave-uniform: bound, qn)
+struct Scan2r {
+    float m, t0, t1;     // round r: |y'_l| + |y'_partner| and the LUT terms of parity bytes 0 and 1 (read one round ahead)
+    float bound;         // smallest complete metric seen by any lane
+    int plo, wr;         // rotating copies of P'.lo and |y'| (bits)
+    int qn;              // survivors waiting in q[0 .. qn)
+};
+
+// Round R of stage 1.  Software pipeline: the two LUT reads of round R + 1 are issued before round R is finished, so their
+// LDS latency (bank conflicts included) overlaps the survivor bookkeeping -- at 4 wavefronts per SIMD nothing else hides
+// it.  Returns true when the ring holds a full batch.  (R is a constant: the caller's round loop is unrolled.)
+__device__ __forceinline__ bool search2r_round(Search2rLds &LL, Scan2r &s, int R, unsigned dlo, float wl, int lane)
+{
+    float mn = 0.0f, u0 = 0.0f, u1 = 0.0f;
+    if (R < 32) {
+        s.plo = wave_rot1(s.plo); s.wr = wave_rot1(s.wr);
+        const unsigned Dn = dlo ^ (unsigned)s.plo;
+        mn = wl + __int_as_float(s.wr); u0 = lut_byte<0>(LL.lut, Dn); u1 = lut_byte<1>(LL.lut, Dn);
+    }
+    float acc = s.m + s.t0;                                                   // |y'_i| + |y'_j| (commutative), then byte 0
+    acc = acc + s.t1;
+    s.m = mn; s.t0 = u0; s.t1 = u1;
+    const bool keep = (R < 32 || lane < 32) && !(acc > s.bound);             // round 32: l and l +- 32 meet twice
+    const u64 km = __ballot(keep);
+    if (!km) return false;
+    if (keep) {
+        const int slot = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, (unsigned)s.qn));
+        LL.q[slot] = make_uint2(__float_as_uint(acc), (unsigned)(R * 64 + lane));
+    }
+    s.qn += __popcll(km);
+    return s.qn >= 64;
+}
+
+// Stage 1 carries only what it reads: the low word of the candidate (parity bytes 0 and 1) and the partner's weight travel
+// round the wavefront (two DPP moves per round); a survivor is stored as (prefix metric, r * 64 + lane) and its batch rebuilds
+// the whole candidate from the P' rows in LDS.  The 32 rounds are unrolled (round number, id and the half-lane rule of round
+// 32 are constants, no loop counter, no pipeline copies).  The ring is not circular: a batch takes slots 0..63 and moves the < 64 entries behind them
+// down to slot 0, so an append is "slot = qn + mbcnt" with no wrap-around.
 __device__ __forceinline__ void search2r_device(Search2rLds &LL, const SearchFrame &S, u64 Pl, float wl, int dir,
                                                 const int *__restrict__ base2, int lane, float &best_out, int &rank_out,
                                                 u64 &D_out, u64 &E_out)
 {
     Search2rLds &L = LL;
+    LL.P[lane] = Pl;     // read only by the survivor batches, after a wave_fence
     // order 0 (rank 0, identical in every lane), then order 1: lane l owns TEP {l}
     float best = cost2r(L, 0.0f, S.d0);
     int bi = -1, bj = -1;
@@ -333,41 +373,27 @@ __device__ __forceinline__ void search2r_device(Search2rLds &LL, const SearchFra
         const float c = cost2r(L, wl, dP);
         if (c < best) { best = c; bj = lane; bestD = dP; }      // a tie keeps the lower rank (order 0)
     }
-    float bound = wave_min_f32(best);
-    int qhead = 0, qn = 0;   // ring state (wave-uniform)
-    int plo = (int)(unsigned)Pl, phi = (int)(unsigned)(Pl >> 32), wr = __float_as_int(wl);
-    // software pipeline: the two LUT reads of round r + 1 are issued before round r is finished, so their LDS latency
-    // (bank conflicts included) overlaps the survivor bookkeeping -- at 3.5 wavefronts per SIMD nothing else hides it
-    plo = wave_rot1(plo); phi = wave_rot1(phi); wr = wave_rot1(wr);
-    u64 D = dP ^ (((u64)(unsigned)phi << 32) | (unsigned)plo);
-    float m = wl + __int_as_float(wr), t0 = lut_byte<0>(L.lut, D), t1 = lut_byte<1>(L.lut, D);
+    const unsigned dlo = (unsigned)dP;
+    Scan2r s;
+    s.bound = wave_min_f32(best);
+    s.qn = 0;
+    s.plo = wave_rot1((int)(unsigned)Pl); s.wr = wave_rot1(__float_as_int(wl));
+    s.m = wl + __int_as_float(s.wr);
+    s.t0 = lut_byte<0>(L.lut, dlo ^ (unsigned)s.plo); s.t1 = lut_byte<1>(L.lut, dlo ^ (unsigned)s.plo);
+#pragma unroll
     for (int r = 1; r <= 32; ++r) {
-        plo = wave_rot1(plo); phi = wave_rot1(phi); wr = wave_rot1(wr);          // (round 33 is computed and never used)
-        const u64 Dn = dP ^ (((u64)(unsigned)phi << 32) | (unsigned)plo);
-        const float mn = wl + __int_as_float(wr), u0 = lut_byte<0>(L.lut, Dn), u1 = lut_byte<1>(L.lut, Dn);
-        float acc = m + t0;                                                       // |y'_i| + |y'_j| (commutative), then byte 0
-        acc = acc + t1;
-        const bool keep = (r < 32 || lane < 32) && !(acc > bound);
-        const u64 km = __ballot(keep);
-        if (km) {
-            if (keep) {
-                const int slot = (qhead + qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, 0))) & 127;
-                LL.q[slot] = make_uint4((unsigned)D, (unsigned)(D >> 32), __float_as_uint(acc), (unsigned)(r * 64 + lane));
-            }
-            qn += __popcll(km);
-            if (qn >= 64) {
-                wave_fence();
-                search2r_finish_batch(L, LL.q[(qhead + lane) & 127], true, dir, base2, best, bi, bj, bestD);
-                qhead = (qhead + 64) & 127;
-                qn -= 64;
-                bound = wave_min_f32(best);
-                wave_fence();
-            }
+        if (search2r_round(LL, s, r, dlo, wl, lane)) {
+            wave_fence();
+            const uint2 e = LL.q[lane], rest = LL.q[64 + lane];
+            s.qn -= 64;
+            if (lane < s.qn) LL.q[lane] = rest;
+            search2r_finish_batch(L, e, true, dir, S.d0, base2, best, bi, bj, bestD);
+            s.bound = wave_min_f32(best);
+            wave_fence();
         }
-        D = Dn; m = mn; t0 = u0; t1 = u1;
     }
     wave_fence();
-    search2r_finish_batch(L, LL.q[(qhead + lane) & 127], lane < qn, dir, base2, best, bi, bj, bestD);
+    search2r_finish_batch(L, LL.q[lane], lane < s.qn, dir, S.d0, base2, best, bi, bj, bestD);
     wave_fence();
     int bestt = tep2_rank(bi, bj, base2);
     u64 bestE = (bi >= 0 ? 1ull << bi : 0ull) | (bj >= 0 ? 1ull << bj : 0ull);
@@ -382,7 +408,7 @@ __device__ __forceinline__ void search2r_device(Search2rLds &LL, const SearchFra
 // they are looked at: 129 us; static: 102 us (the wavefronts are then alive for ~63 % of the launch: the scan time
 // varies with the number of survivors) -- so the balance comes from the hardware dispatcher instead: the grid is 6x
 // the resident wavefronts (see the launcher).
-__global__ __launch_bounds__(64) void osd_search2r_kernel(const float *__restrict__ y, const int *__restrict__ index,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void osd_search2r_kernel(const float *__restrict__ y, const int *__restrict__ index,
                                                           const int *__restrict__ count, long long F,
                                                           const unsigned char *__restrict__ perm_in,
                                                           const u64 *__restrict__ parity_in, int dir,
@@ -471,9 +497,9 @@ __global__ __launch_bounds__(64) void osd_search2r_kernel(const float *__restric
 // channel values pass from one to the other in registers and LDS and never touch memory.  Two launches moved 640 B of
 // workspace per frame out and in again and read y twice (PMC, round 3: 41 + 49 MB per 33.5 k frames against 18 MB
 // algorithmic: 5.1x); this form reads 512 B and writes 24 B per frame.  The front end's 3.6 KiB of LDS lie inside the
-// scan's LUT area (built afterwards), the frame's y row in its survivor ring (filled afterwards): 10 KiB, 16 wavefronts per CU.
+// scan's LUT area (built afterwards), the frame's y row in its P' rows (filled afterwards): 9.5 KiB, 16 wavefronts per CU.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void osd_fused2r_kernel(const float *__restrict__ y, const int *__restrict__ index,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void osd_fused2r_kernel(const float *__restrict__ y, const int *__restrict__ index,
                                                          const int *__restrict__ count, long long F,
                                                          const u64 *__restrict__ Gcols, int dir, const int *__restrict__ base2,
                                                          u64 *__restrict__ cw_out, float *__restrict__ metric_out,
@@ -483,7 +509,7 @@ __global__ __launch_bounds__(64) void osd_fused2r_kernel(const float *__restrict
     __shared__ Search2rLds LL;
     static_assert(sizeof(FrontLds) <= sizeof(LL.lut), "the front end works inside the LUT area");
     FrontLds &LF = *reinterpret_cast<FrontLds *>(LL.lut);
-    float *const yrow = reinterpret_cast<float *>(LL.q) + 256;      // bytes 1024 .. 1535 of the ring (wpar: 0 .. 255, cw: 512 .. 527)
+    float *const yrow = reinterpret_cast<float *>(LL.P);            // the frame's y row in the P' table (filled by the scan)
     const int lane = threadIdx.x;
     long long nframes = F;
     if (count) { const long long c = *count; nframes = c < F ? c : F; }
