@@ -178,7 +178,9 @@ int ldpc_unpack_bits(ldpc_ctx *ctx, const uint64_t *d_words, int64_t B, void *d_
 
 /* Per-frame GF(2) elimination on the device: full_gf2elim, PB_OSD/pb_testing.py:231-266.
  * d_rows_in/out: [F][64][2] u64 (row r of frame f, columns 0..127); d_swaps: [F][64][2] u8
- * recorded (j, col) pairs; d_nswaps: [F] i32.                                              */
+ * recorded (j, col) pairs; d_nswaps: [F] i32, the number of exchanges, or -1 for a rank-deficient
+ * matrix (its reduced rows and exchange records are then unspecified: the kernel does not drop
+ * all-zero rows as the host GE does).                                                         */
 int ldpc_osd_ge(ldpc_ctx *ctx, const uint64_t *d_rows_in, int64_t F, uint64_t *d_rows_out, uint8_t *d_swaps,
                 int32_t *d_nswaps, void *stream);
 

@@ -1,0 +1,254 @@
+"""-m gpu: the OSD front end (ge_columns, front_device_vals) and every search route behind it on hard inputs, bit for bit
+against the C oracle (np_oracle.hosd_* for the H form): frames crafted by tests/osd_adversary.py so that the elimination
+makes dozens of column exchanges (the natural frames of the other tests make a handful), arbitrary 64 x 128 matrices for
+ldpc_osd_ge (rank-deficient ones included), and magnitude extremes through the conventional, FS and PB searches.
+Metrics are compared as uint32 bit patterns."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import c_oracle, np_oracle
+from tests import dlosd_model as DM
+from tests import osd_adversary as adv
+from tests.gpu_util import pack_np, to_dev, words_np
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def dec():
+    from short_ldpc_decoding_osd_amd import Code
+    from short_ldpc_decoding_osd_amd.runtime import Decoder
+    return Decoder(Code())
+
+
+@pytest.fixture(scope="module")
+def crafted(dec):
+    s = adv.crafted_sets(dec.code.G, dec.code.H)
+    ns = [len(c_oracle.osd_front(dec.code.G, row)[2]) for row in s["g"][0]]
+    assert max(ns) >= 40
+    y = np.concatenate([s["g"][0], s["g_ties"][0]])
+    cw = np.concatenate([s["g"][1], s["g_ties"][1]])
+    return y, cw, s["h"]
+
+
+def _extremes(G, frames=12, seed=404):
+    """Natural frames at 2.0 dB under six magnitude extremes (finite, every 128-term |y| sum finite)."""
+    y, cw = np_oracle.make_frames(G, 2.0, frames, np.random.default_rng(seed))
+    rng = np.random.default_rng(seed + 1)
+    out = []
+    out.append(y * F32(1e-41))                                            # all denormal
+    out.append(np.where(np.signbit(y), F32(-0.75), F32(0.75)))            # all-equal magnitudes
+    z = y.copy()
+    m = rng.random(y.shape) < 0.15
+    z[m] = np.where(rng.random(m.sum()) < 0.5, F32(0.0), F32(-0.0))       # +0.0 / -0.0 entries
+    out.append(z)
+    c = np.clip(y, -1.0, 1.0)
+    c[:, rng.choice(128, 6, replace=False)] = 0.0                         # clipped, with zeros
+    out.append(c)
+    o = y.copy()
+    o[np.arange(frames), rng.integers(0, 128, frames)] = F32(1e30)        # one outlier per frame
+    out.append(o)
+    out.append(y * F32(2.0 ** 60))
+    y_all = np.concatenate(out).astype(F32)
+    assert np.isfinite(np.abs(y_all.astype(np.float64)).sum(axis=1)).all()
+    assert np.isfinite(np.abs(y_all).sum(axis=1, dtype=F32)).all()
+    return y_all, np.concatenate([cw] * len(out))
+
+
+@pytest.fixture(scope="module")
+def extremes(dec):
+    return _extremes(dec.code.G)
+
+
+def _rows_packed(M):
+    F = M.shape[0]
+    return np.packbits(M.astype(np.uint8), axis=2, bitorder="little").view(np.uint64).reshape(F, 64, 2)
+
+
+def test_device_ge_on_arbitrary_matrices(dec):
+    mats = adv.ge_matrices()
+    names = [n for n in mats for _ in mats[n]]
+    M = np.stack([m for n in mats for m in mats[n]])
+    red, swaps, ns = dec.osd_ge(to_dev(_rows_packed(M).view(np.int64), dec))
+    torch.cuda.synchronize()
+    red, sw, ns = words_np(red).reshape(-1, 64, 2), swaps.cpu().numpy(), ns.cpu().numpy()
+    seen127 = False
+    for i, name in enumerate(names):
+        R, rsw = c_oracle.gf2elim(M[i])
+        if R.shape[0] < 64:
+            assert name.startswith("deficient") and ns[i] == -1, (i, name)
+            continue
+        assert ns[i] == len(rsw), (i, name)
+        assert [tuple(int(v) for v in p) for p in sw[i, :ns[i]]] == rsw, (i, name)
+        assert np.array_equal(red[i], _rows_packed(R[None])[0]), (i, name)
+        seen127 |= any(c == 127 for _, c in rsw)
+    assert seen127 and (ns == -1).sum() == sum(n.startswith("deficient") for n in names)
+
+
+def _front_oracle(G, y):
+    perm_o, par_o, ns_o = [], [], []
+    for row in y:
+        perm, Gp, sw = c_oracle.osd_front(G, row)
+        perm_o.append(perm)
+        par_o.append(np.packbits(Gp[:, 64:].astype(np.uint8), axis=1, bitorder="little").view(np.uint64)[:, 0])
+        ns_o.append(len(sw))
+    return np.stack(perm_o), np.stack(par_o), np.array(ns_o)
+
+
+def test_front_end_on_crafted_frames(dec, crafted):
+    y = crafted[0]
+    perm, parity, ns = dec.osd_front(to_dev(y, dec))
+    torch.cuda.synchronize()
+    perm_o, par_o, ns_o = _front_oracle(dec.code.G, y)
+    assert ns_o.max() >= 40
+    assert np.array_equal(ns.cpu().numpy(), ns_o)
+    assert np.array_equal(perm.cpu().numpy(), perm_o)
+    assert np.array_equal(words_np(parity), par_o)
+
+
+def _conv_routes(dec, y, cw, order):
+    yd = to_dev(y, dec)
+    ref = c_oracle.conv_osd(dec.code.G, y, cw, order)
+    perm_o, par_o, _ = _front_oracle(dec.code.G, y)
+    perm, parity, _ = dec.osd_front(yd)
+    routes = {"default": dec.osd_decode(yd, order),
+              "search_device_front": dec.osd_search(yd, perm, parity, dec.osd_params(order)),
+              "search_oracle_front": dec.osd_search(yd, to_dev(perm_o.astype(np.uint8), dec),
+                                                    to_dev(par_o.view(np.int64), dec), dec.osd_params(order))}
+    if order == 2:
+        routes["table"] = dec.osd_decode(yd, 2, params=dec.osd_params(2, table_scan=True))
+        routes["readlane"] = dec.osd_decode(yd, 2, params=dec.osd_params(2, readlane_scan=True))
+    torch.cuda.synchronize()
+    for name, o in routes.items():
+        assert np.array_equal(words_np(o["cw"]), pack_np(ref["codeword"])), (name, order)
+        assert np.array_equal(o["best"].cpu().numpy(), ref["best"]), (name, order)
+        assert np.array_equal(o["metric"].cpu().numpy().view(np.uint32), ref["metric"].view(np.uint32)), (name, order)
+        assert (o["ntep"].cpu().numpy() == ref["teps_size"]).all(), (name, order)
+    # one given TEP per frame on the device front end (ldpc_osd_tep_eval) against the oracle's G'
+    rng = np.random.default_rng(order)
+    masks = np.zeros(len(y), dtype=np.uint64)
+    for f in range(len(y)):
+        for p in rng.choice(64, size=int(rng.integers(0, 6)), replace=False):
+            masks[f] |= np.uint64(1) << np.uint64(p)
+    te = dec.osd_tep_eval(yd, perm, parity, to_dev(masks.view(np.int64), dec))
+    torch.cuda.synchronize()
+    got_cw, got_m, got_hd = words_np(te["cw"]), te["metric"].cpu().numpy(), te["hd"].cpu().numpy()
+    for f in range(len(y)):
+        yp, _, Gp, pm, _ = np_oracle.swapped_info(y[f], cw[f], dec.code.G)
+        hard = np.where(yp > 0, 0, 1).astype(np.int64)
+        e = np.array([(int(masks[f]) >> p) & 1 for p in range(64)], dtype=np.int64)
+        cand = ((hard[:64] + e) % 2).dot(Gp) % 2
+        disc = (cand + hard) % 2
+        assert got_hd[f] == disc.sum(), f
+        assert got_m[f].view(np.uint32) == np_oracle.weighted_distance(disc, np.abs(yp)).view(np.uint32), f
+        orig = np.empty(128, dtype=np.int64)
+        orig[pm] = cand
+        assert np.array_equal(got_cw[f], pack_np(orig[None])[0]), f
+
+
+@pytest.mark.parametrize("order", [0, 1, 2, 3])
+def test_conventional_on_crafted_frames(dec, crafted, order):
+    y, cw, _ = crafted
+    _conv_routes(dec, y, cw, order)
+
+
+@pytest.mark.parametrize("order", [0, 1, 2, 3])
+def test_conventional_on_magnitude_extremes(dec, extremes, order):
+    y, cw = extremes
+    if order == 3:
+        y, cw = y[::2], cw[::2]
+    _conv_routes(dec, y, cw, order)
+
+
+def _fs_check(dec, y, cw, order, beta=0.1, tau_e=6.5, tau_psc=30.0):
+    from short_ldpc_decoding_osd_amd import _lib
+    ref = c_oracle.fs_osd(dec.code.G, y, cw, order, beta, tau_e, tau_psc)
+    yd = to_dev(y, dec)
+    for quirk in (1, 0):
+        p = dec.osd_params(order, _lib.OSD_FS, fs_beta=beta, fs_tau_e=tau_e, fs_tau_psc=tau_psc, fs_reference_quirk=quirk)
+        out = dec.osd_decode(yd, order, params=p)
+        torch.cuda.synchronize()
+        assert np.array_equal(out["ntep"].cpu().numpy(), ref["num_teps"]), (order, quirk)
+        want_cw = ref["codeword_ref"] if quirk else ref["codeword_hit"]
+        want_m = ref["metric_ref"] if quirk else ref["metric_hit"]
+        assert np.array_equal(words_np(out["cw"]), pack_np(want_cw)), (order, quirk)
+        assert np.array_equal(out["metric"].cpu().numpy().view(np.uint32), want_m.view(np.uint32)), (order, quirk)
+        if quirk:
+            assert np.array_equal(out["best"].cpu().numpy(), ref["best_index"]), order
+    return ref
+
+
+@pytest.mark.parametrize("which", ["crafted", "extremes"])
+def test_fs_on_hard_inputs(dec, crafted, extremes, which):
+    y, cw = (crafted[0], crafted[1]) if which == "crafted" else extremes
+    for order in (1, 2, 3):
+        _fs_check(dec, y, cw, order)
+    _fs_check(dec, y, cw, 2, 0.1, 14.5, 30.0)                  # loose tau_e: the tau_e stop and the quirk
+
+
+PB_ROUTES = [dict(), dict(pb_path="block"), dict(pb_path="replay"), dict(pb_front_inside=True)]
+
+
+def _pb_check(dec, y, cw, order, snr):
+    from short_ldpc_decoding_osd_amd import _lib
+    ref = c_oracle.pb_osd(dec.code.G, y, cw, order, snr)
+    yd = to_dev(y, dec)
+    for kw in PB_ROUTES:
+        aux = torch.zeros((y.shape[0], 4), dtype=torch.int32, device=dec.device)
+        out = dec.osd_decode(yd, order, params=dec.osd_params(order, _lib.OSD_PB, snr_db=snr, aux=aux, **kw))
+        torch.cuda.synchronize()
+        a = aux.cpu().numpy()
+        tag = (order, snr, kw)
+        assert np.array_equal(out["ntep"].cpu().numpy(), ref["num_teps"]), tag
+        assert np.array_equal(a[:, 3], ref["stop"]) and np.array_equal(a[:, 0], ref["comparisons"]), tag
+        assert np.array_equal(a[:, 1], ref["suc1"]) and np.array_equal(a[:, 2], ref["suc2"]), tag
+        assert np.array_equal(out["best"].cpu().numpy(), ref["best_index"]), tag
+        assert np.array_equal(words_np(out["cw"]), pack_np(ref["codeword"])), tag
+        assert np.array_equal(out["metric"].cpu().numpy().view(np.uint32), ref["metric"].view(np.uint32)), tag
+
+
+@pytest.mark.parametrize("snr", [1.0, 2.5])
+def test_pb_on_crafted_frames(dec, crafted, snr):
+    y, cw, _ = crafted
+    for order in (1, 2, 3):
+        _pb_check(dec, y, cw, order, snr)
+
+
+@pytest.mark.parametrize("snr", [1.0, 2.5])
+def test_pb_on_magnitude_extremes(dec, extremes, snr):
+    y, cw = extremes
+    for order in (1, 2, 3):
+        _pb_check(dec, y[::2] if order == 3 else y, cw[::2] if order == 3 else cw, order, snr)
+
+
+def test_hform_on_crafted_frames(dec, crafted):
+    """hosd_front / hosd_search on ascending-order frames whose H elimination makes 20+ exchanges, against
+    np_oracle.hosd_frame; hosd_sliding against the oracle's window loop."""
+    from tests.test_gpu_dlosd import _blocks, _check_sliding, _convention_path
+    y, cw = crafted[2]
+    ns_o = [len(c_oracle.gf2elim(dec.code.H[:, np_oracle.hosd_reorder(r)])[1]) for r in y]
+    assert max(ns_o) >= 20
+    blocks = _blocks(_convention_path())
+    from short_ldpc_decoding_osd_amd.ordered_statistics_decoding import _teps_from_matrix
+    teps = np.concatenate([_teps_from_matrix(E) for E in blocks])
+    off = np.insert(np.cumsum([len(E) for E in blocks]), 0, 0).astype(np.int32)
+    yd = to_dev(y, dec)
+    front = dec.hosd_front(yd)
+    out = dec.hosd_search(yd, yd, front, to_dev(teps, dec), to_dev(off, dec), label_bits=to_dev(pack_np(cw).view(np.int64), dec))
+    torch.cuda.synchronize()
+    lri, uidx, M, ns = (t.cpu().numpy() for t in front)
+    Mb = np.unpackbits(M.view(np.uint8).reshape(-1, 64, 8), axis=2, bitorder="little")
+    bmin, barg = out["block_min"].cpu().numpy(), out["block_arg"].cpu().numpy()
+    cwg = np.unpackbits(words_np(out["cw"]).view(np.uint8).reshape(-1, 16), axis=1, bitorder="little")
+    for f in range(len(y)):
+        r = np_oracle.hosd_frame(y[f], y[f], cw[f], dec.code.H, blocks)
+        assert np.array_equal(lri[f], r["lri"]) and np.array_equal(uidx[f], r["uidx"]), f
+        assert np.array_equal(Mb[f], r["M"]) and ns[f] == len(r["swaps"]) == ns_o[f], f
+        assert np.array_equal(bmin[f].view(np.uint32), r["block_min"].view(np.uint32)), f
+        assert np.array_equal(barg[f], r["block_arg"]), f
+        assert out["truth"][f].item() == r["truth"] and out["metric"][f].item() == r["metric"], f
+        assert out["best"][f].item() == r["best_index"] and np.array_equal(cwg[f], r["codeword"]), f
+    w1, w2 = DM.stopping_fcn_weights(3)
+    _check_sliding(dec, y, y, cw, blocks, 3, 0.9, w1, w2, groups=(1, 0))
