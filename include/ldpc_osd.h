@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LDPC_OSD_ABI_VERSION 4
+#define LDPC_OSD_ABI_VERSION 5
 
 enum {
     LDPC_OK = 0,
@@ -192,6 +192,23 @@ int ldpc_osd_ge(ldpc_ctx *ctx, const uint64_t *d_rows_in, int64_t F, uint64_t *d
 int ldpc_osd_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
                    uint8_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, void *stream);
 
+/* ldpc_osd_params.flags: routes that compute the same results as the default one (cross-checks and options).
+ * Every call validates them before it launches anything (LDPC_E_ARG names the offending flag).
+ *   flag                        algorithm     entry points        route
+ *   LDPC_OSD_F_TABLE_SCAN       CONVENTIONAL  all                 the table-driven scan at order 2 (orders 0, 1, 3 take it anyway)
+ *   LDPC_OSD_F_READLANE_SCAN    CONVENTIONAL  all                 order 2 only: the v_readlane-paired scan; not with TABLE_SCAN
+ *   LDPC_OSD_F_PB_BLOCK         PB            all                 every frame through the sorted-chunk kernel from its first TEP
+ *   LDPC_OSD_F_PB_REPLAY        PB            all                 every frame through the list replay; not with PB_BLOCK
+ *   LDPC_OSD_F_PB_FRONT_INSIDE  PB            ldpc_osd_decode,    the front end inside the first PB kernel (no workspace
+ *                                             ldpc_pipeline_run   traffic, 4-5 % slower); not with PB_REPLAY, not where the
+ *                                             (d_perm/d_parity    caller supplies or wants the front-end results
+ *                                             NULL)                                                                          */
+#define LDPC_OSD_F_TABLE_SCAN       (1u << 0)
+#define LDPC_OSD_F_PB_BLOCK         (1u << 1)
+#define LDPC_OSD_F_PB_REPLAY        (1u << 2)
+#define LDPC_OSD_F_READLANE_SCAN    (1u << 3)
+#define LDPC_OSD_F_PB_FRONT_INSIDE  (1u << 4)
+
 typedef struct ldpc_osd_params {
     int32_t order;       /* 0..3                                                          */
     int32_t algo;        /* LDPC_OSD_*                                                    */
@@ -200,12 +217,7 @@ typedef struct ldpc_osd_params {
     float fs_tau_e;      /* FS-OSD floor(d_min-1)/2 as the reference evaluates it (6.5)    */
     float fs_tau_psc;    /* FS-OSD tau_psc, FS_OSD/globalmap.py:50 (30)                    */
     int32_t fs_reference_quirk; /* 1: keep optimal_codeword un-updated on a tau_e hit (fs_testing.py:145) */
-    int32_t reserved;    /* 0; cross-check switches: bit 0 = conventional order 2 through the table-driven scan instead of
-                            the register-resident kernels, bit 3 = the register-resident kernel with v_readlane
-                            pairing instead of the rotation-paired persistent one; PB-OSD: bit 0 = ldpc_osd_decode runs the front
-                            end inside the first PB kernel (no workspace traffic; 4-5 % slower), bit 1 = every frame
-                            through the sorted-chunk kernel from its first TEP, bit 2 = every frame through the
-                            literal list replay                                                               */
+    int32_t flags;       /* LDPC_OSD_F_* (table above); 0 = the default route                                       */
     void *d_aux;         /* optional DEVICE [F][4] i32, PB-OSD statistics per frame: {frontier comparisons
                             (memory_sum, pb_testing.py:122), suc counter 1 (:138), suc counter 2 (:144),
                             stop reason 0 = none / 1 = promising rule (:129) / 2 = success rule (:145)} */
@@ -294,7 +306,9 @@ int ldpc_osd_tep_eval(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, c
                       float *d_metric, int32_t *d_hd, void *stream);
 
 /* OSD statistics against labels: d_counts[3] += {frames, frames_wrong, teps_total}.
- * (the success test of convention_osd.py:65-66 / pb_testing.py:158 / fs_testing.py:162)   */
+ * (the success test of convention_osd.py:65-66 / pb_testing.py:158 / fs_testing.py:162)
+ * teps_total sums d_ntep and stays unchanged when d_ntep is NULL -- on every route, also where the search kernel counts
+ * (ldpc_pipeline_run's d_osd_counts).                                                      */
 int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label_bits, const int32_t *d_index,
                     const int32_t *d_count, const int32_t *d_ntep, int64_t F, int64_t *d_counts, void *stream);
 
@@ -415,7 +429,7 @@ typedef struct ldpc_pipeline {
     uint64_t *d_cw;                /* [B][2]                                               */
     float *d_metric;               /* [B] nullable                                         */
     int32_t *d_best, *d_ntep;      /* [B] nullable / [B]                                   */
-    int64_t *d_osd_counts;         /* [3] accumulated, nullable                            */
+    int64_t *d_osd_counts;         /* [3] accumulated, nullable (as ldpc_osd_counts)       */
 } ldpc_pipeline;
 
 #define LDPC_TIMING_SLOTS 64

@@ -1,6 +1,6 @@
 """PB-OSD order 3 on the NMS failures of four 131 072-frame batches, three routes, HIP-event timed (GPU box):
    ldpc_osd_decode (front end as its own kernel, through the workspace) / the same with the front end inside the first PB kernel
-   (reserved bit 0) /
+   (LDPC_OSD_F_PB_FRONT_INSIDE) /
    ldpc_osd_front + ldpc_osd_search through caller buffers.      python scripts/bench_pb_routes.py [snr ...]"""
 import os, sys
 ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, ROOT)

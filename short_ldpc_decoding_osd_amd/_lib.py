@@ -27,12 +27,14 @@ SYMBOLS = (
 
 NMS_AUTO, NMS_GENERIC, NMS_QC16 = 0, 1, 2
 OSD_CONVENTIONAL, OSD_FS, OSD_PB = 0, 1, 2
+# ldpc_osd_params.flags (LDPC_OSD_F_*)
+OSD_F_TABLE_SCAN, OSD_F_PB_BLOCK, OSD_F_PB_REPLAY, OSD_F_READLANE_SCAN, OSD_F_PB_FRONT_INSIDE = 1, 2, 4, 8, 16
 
 
 class OsdParams(C.Structure):
     _fields_ = [("order", C.c_int32), ("algo", C.c_int32), ("snr_db", C.c_float), ("fs_beta", C.c_float),
                 ("fs_tau_e", C.c_float), ("fs_tau_psc", C.c_float), ("fs_reference_quirk", C.c_int32),
-                ("reserved", C.c_int32), ("d_aux", C.c_void_p), ("y_frames", C.c_int64)]
+                ("flags", C.c_int32), ("d_aux", C.c_void_p), ("y_frames", C.c_int64)]
 
 
 class PbTuning(C.Structure):

@@ -118,6 +118,13 @@ int ldpc_pipeline_run(ldpc_ctx *ctx, const ldpc_pipeline *p, void *stream)
 {
     if (!ctx || !p) return fail(LDPC_E_ARG, "ldpc_pipeline_run: null argument");
     if (!p->d_hard || !p->d_fail) return fail(LDPC_E_ARG, "ldpc_pipeline_run: d_hard and d_fail are required");
+    const bool front = p->d_perm && p->d_parity;   // the caller wants the front-end results: front end and search apart
+    int rc;
+    if (p->osd_enable) {
+        if (!p->d_index || !p->d_count || !p->d_cw)
+            return fail(LDPC_E_ARG, "ldpc_pipeline_run: OSD stage needs d_index, d_count, d_cw");
+        if ((rc = check_params(ctx, &p->osd, front, "ldpc_pipeline_run"))) return rc;
+    }
     hipStream_t s = (hipStream_t)stream;
     hipEvent_t *ev = nullptr;
     unsigned *rec = nullptr;            // which of the slot's events THIS run records (ldpc_pipeline_timing reads only those)
@@ -128,54 +135,33 @@ int ldpc_pipeline_run(ldpc_ctx *ctx, const ldpc_pipeline *p, void *stream)
         *rec = 0;
     }
 #define LDPC_EV(i) do { if (ev) { LDPC_HIP(hipEventRecord(ev[i], s)); *rec |= 1u << (i); } } while (0)
-    int rc;
     LDPC_EV(0);
     if ((rc = ldpc_nms_decode(ctx, p->d_llr, p->B, p->T, p->alpha, p->w_in, p->w_out, p->d_soft, nullptr, p->d_hard,
                               p->d_fail, p->nms_kernel, stream))) return rc;
     LDPC_EV(1);
     const bool want_eval = p->d_label_bits && p->d_nms_counts;
-    if (p->osd_enable) {
-        if (!p->d_index || !p->d_count || !p->d_cw)
-            return fail(LDPC_E_ARG, "ldpc_pipeline_run: OSD stage needs d_index, d_count, d_cw");
-        if (want_eval && p->B > 0) {   // counters and the compaction's counting pass share one kernel
-            if ((rc = eval_and_compact(ctx, p->d_hard, p->d_label_bits, p->d_fail, p->B, p->d_nms_counts, p->d_index,
-                                       p->d_count, s))) return rc;
-        } else if ((rc = ldpc_compact(ctx, p->d_fail, p->B, p->d_index, p->d_count, stream))) return rc;
-        LDPC_EV(2);
-        if (p->d_perm && p->d_parity) {   // caller wants the front-end results: two kernels
-            if ((rc = ldpc_osd_front(ctx, p->d_llr, p->d_index, p->d_count, p->B, p->d_perm, p->d_parity, nullptr, stream))) return rc;
-            LDPC_EV(3);
-            // the search kernel counts its own successes where it can (order-2 scan); otherwise the counting launch follows
-            // the search's closing event, so that ms[2] is the search alone for every algorithm
-            const bool counted = p->d_label_bits && p->d_osd_counts;
-            bool fused = false;
-            if ((rc = osd_search_counted(ctx, p->d_llr, p->d_index, p->d_count, p->B, p->d_perm, p->d_parity, &p->osd, p->d_cw,
-                                         p->d_metric, p->d_best, p->d_ntep, counted ? p->d_label_bits : nullptr,
-                                         counted ? p->d_osd_counts : nullptr, s, &fused))) return rc;
-            LDPC_EV(4);
-            if (counted && !fused &&
-                (rc = ldpc_osd_counts(ctx, p->d_cw, p->d_label_bits, p->d_index, p->d_count, p->d_ntep, p->B, p->d_osd_counts, stream))) return rc;
-            return LDPC_OK;
-        } else {                          // ldpc_osd_decode: one fused kernel (conventional order 2) or the stream's workspace
-            LDPC_EV(3);
-            if (!ctx->osd_ok) return fail(LDPC_E_UNSUPPORTED, "OSD kernels need an (n=128, k=64) code; this one is (%d,%d)", ctx->code.n, ctx->code.k);
-            if (p->osd.order < 0 || p->osd.order > 3 || p->osd.algo < 0 || p->osd.algo > 2 || (p->osd.algo == LDPC_OSD_PB && p->osd.order < 1))
-                return fail(LDPC_E_ARG, "ldpc_pipeline_run: OSD order %d / algorithm %d", p->osd.order, p->osd.algo);
-            const bool counted = p->d_label_bits && p->d_osd_counts;
-            bool fused = false;
-            if (p->B > 0 && (rc = osd_decode_counted(ctx, p->d_llr, p->d_index, p->d_count, p->B, &p->osd, p->d_cw, p->d_metric, p->d_best,
-                                                     p->d_ntep, counted ? p->d_label_bits : nullptr, counted ? p->d_osd_counts : nullptr, s, &fused))) return rc;
-            LDPC_EV(4);
-            if (counted && !fused &&
-                (rc = ldpc_osd_counts(ctx, p->d_cw, p->d_label_bits, p->d_index, p->d_count, p->d_ntep, p->B, p->d_osd_counts, stream))) return rc;
-            return LDPC_OK;
-        }
-        LDPC_EV(4);
-        if (p->d_label_bits && p->d_osd_counts &&
-            (rc = ldpc_osd_counts(ctx, p->d_cw, p->d_label_bits, p->d_index, p->d_count, p->d_ntep, p->B, p->d_osd_counts,
-                                  stream))) return rc;
-    } else if (want_eval && (rc = ldpc_eval_counts(ctx, p->d_hard, p->d_label_bits, p->d_fail, p->B, p->d_nms_counts, stream)))
-        return rc;
+    if (!p->osd_enable) {
+        if (want_eval && (rc = ldpc_eval_counts(ctx, p->d_hard, p->d_label_bits, p->d_fail, p->B, p->d_nms_counts, stream))) return rc;
+        return LDPC_OK;
+    }
+    if (want_eval && p->B > 0) {   // counters and the compaction's counting pass share one kernel
+        if ((rc = eval_and_compact(ctx, p->d_hard, p->d_label_bits, p->d_fail, p->B, p->d_nms_counts, p->d_index,
+                                   p->d_count, s))) return rc;
+    } else if ((rc = ldpc_compact(ctx, p->d_fail, p->B, p->d_index, p->d_count, stream))) return rc;
+    LDPC_EV(2);
+    if (front && (rc = ldpc_osd_front(ctx, p->d_llr, p->d_index, p->d_count, p->B, p->d_perm, p->d_parity, nullptr, stream))) return rc;
+    LDPC_EV(3);
+    // the search kernel counts its own successes where it can (rotation-paired order-2 scan); otherwise the counting launch
+    // follows the search's closing event, so that ms[2] is the search alone for every route
+    const bool counts = p->d_label_bits && p->d_osd_counts;
+    bool counted = false;
+    if (p->B > 0 && (rc = osd_launch(ctx, p->d_llr, p->d_index, p->d_count, p->B, front ? p->d_perm : nullptr, front ? p->d_parity : nullptr,
+                                     &p->osd, p->d_cw, p->d_metric, p->d_best, p->d_ntep, counts ? p->d_label_bits : nullptr,
+                                     counts ? p->d_osd_counts : nullptr, s, &counted))) return rc;
+    LDPC_EV(4);
+    if (counts && !counted &&
+        (rc = ldpc_osd_counts(ctx, p->d_cw, p->d_label_bits, p->d_index, p->d_count, p->d_ntep, p->B, p->d_osd_counts, stream))) return rc;
+#undef LDPC_EV
     return LDPC_OK;
 }
 

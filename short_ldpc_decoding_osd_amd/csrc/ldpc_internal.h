@@ -80,13 +80,31 @@ int launch_nms(ldpc_ctx *ctx, const float *d_llr, int64_t B, int T, const float 
                float *d_soft, float *d_traj, uint64_t *d_hard, uint8_t *d_fail, int kernel, hipStream_t st,
                const int32_t *d_index = nullptr, const int32_t *d_count = nullptr, float *d_rows = nullptr);
 int probe_dpp(bool *ror_up, int *wave_rol_dir);
-int osd_search_counted(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
-                       const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *p, uint64_t *d_cw, float *d_metric,
-                       int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label, int64_t *d_counts, hipStream_t s,
-                       bool *counted_by_search = nullptr);
-int osd_decode_counted(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
-                       const ldpc_osd_params *p, uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_ntep,
-                       const uint64_t *d_label, int64_t *d_counts, hipStream_t s, bool *counted_by_search);
+// OSD (ldpc_osd.hip).  check_params runs first on every OSD entry point: the order, the algorithm and the flags
+// (LDPC_OSD_F_*) against each other and against front_outside -- the caller supplies or wants the front-end results
+// (ldpc_osd_search; ldpc_pipeline_run with d_perm and d_parity) -- before anything is launched.
+int check_params(ldpc_ctx *ctx, const ldpc_osd_params *p, bool front_outside, const char *who);
+// The kernel sequence of an OSD call; select_route reads the flags of params that check_params accepted.
+enum class OsdRoute {
+    Fused2r,        // conventional order 2, front end and scan in one kernel (osd_fused2r_kernel)
+    Search2r,       // front end + osd_search2r_kernel (conventional order 2 on the caller's front-end results)
+    Search2,        // front end + osd_search2_kernel (READLANE_SCAN, or no usable wave rotation)
+    Table,          // front end + osd_search_kernel (orders 0, 1, 3; TABLE_SCAN at order 2)
+    Fs,             // front end + osd_fs_kernel
+    PbStaged,       // front end + the PB kernels (pb_mode 0 = staged, 1 = PB_BLOCK, 2 = PB_REPLAY)
+    PbFrontInside,  // the PB kernels with the front end inside pb_singles_kernel (pb_mode 0 or 1)
+};
+struct OsdPlan {
+    OsdRoute route;
+    int pb_mode;
+};
+OsdPlan select_route(const ldpc_ctx *ctx, const ldpc_osd_params *p, bool front_outside);
+// The OSD of ldpc_osd_search (d_perm, d_parity: the caller's front-end results) or of ldpc_osd_decode (both NULL) on
+// validated params.  With d_label and d_counts, *counted tells whether the search kernel accumulated the counters of
+// ldpc_osd_counts itself (the caller launches ldpc_osd_counts otherwise).
+int osd_launch(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F, const uint8_t *d_perm,
+               const uint64_t *d_parity, const ldpc_osd_params *p, uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_ntep,
+               const uint64_t *d_label, int64_t *d_counts, hipStream_t s, bool *counted);
 int eval_and_compact(ldpc_ctx *ctx, const uint64_t *d_hard, const uint64_t *d_label, const uint8_t *d_fail, int64_t B,
                      int64_t *d_counts, int32_t *d_index, int32_t *d_count, hipStream_t st);
 

@@ -401,6 +401,45 @@ __device__ __forceinline__ void search2r_device(Search2rLds &LL, const SearchFra
     best_out = best; rank_out = bestt; D_out = bestD; E_out = bestE;
 }
 
+// The frame body of both rotation-paired order-2 kernels (osd_search2r_kernel, osd_fused2r_kernel): the scan of frame f on
+// (o1, o2, P'[lane], y1 = y'[lane], y2 = y'[64 + lane]), its outputs, and -- with counts -- the wrong-codeword counter
+// against lab (the label word of lane 0 / 1).
+__device__ __forceinline__ void search2r_frame(Search2rLds &LL, int o1, int o2, u64 Pl, float y1, float y2, int dir, const int *base2,
+                                               long long f, u64 lab, int lane, u64 *cw_out, float *metric_out, int *best_out,
+                                               int *ntep_out, u64 *counts)
+{
+    SearchFrame S;
+    S.o1 = o1; S.o2 = o2;
+    const float w1 = __builtin_fabsf(y1), w2 = __builtin_fabsf(y2);
+    LL.wpar()[lane] = w2;
+    S.hm = __ballot(!(y1 > 0.0f));
+    S.hp = __ballot(!(y2 > 0.0f));
+    wave_fence();
+    build_byte_luts<8>(LL.lut, LL.wpar(), lane);
+    S.d0 = wave_xor64(((S.hm >> lane) & 1) ? Pl : 0ull) ^ S.hp;
+    wave_fence();
+    float best; int bestt; u64 bestD, bestE;
+    search2r_device(LL, S, Pl, w1, dir, base2, lane, best, bestt, bestD, bestE);
+    {   // search_finish, with the codeword words still in hand for the success test (convention_osd.py:65-66)
+        const u64 mrb_bits = S.hm ^ bestE, par_bits = bestD ^ S.hp;
+        u64 *const cw = LL.cw();
+        if (lane < 2) cw[lane] = 0;
+        wave_fence();
+        if ((mrb_bits >> lane) & 1) atomicOr(&cw[S.o1 >> 6], 1ull << (S.o1 & 63));
+        if ((par_bits >> lane) & 1) atomicOr(&cw[S.o2 >> 6], 1ull << (S.o2 & 63));
+        wave_fence();
+        const u64 word = lane < 2 ? cw[lane] : 0ull;
+        if (lane < 2) cw_out[f * 2 + lane] = word;
+        if (counts && __ballot(lane < 2 && word != lab) && lane == 0) atomicAdd(&counts[1], 1ull);
+        wave_fence();
+    }
+    if (lane == 0) {
+        if (metric_out) metric_out[f] = best;
+        if (best_out) best_out[f] = bestt;
+        if (ntep_out) ntep_out[f] = 2081;
+    }
+}
+
 // Frame assignment is static (frame = block + k grid).  Dynamic hand-out was measured and dropped: a device-scope
 // ticket word saturates at ~88 fetch-adds per us (MI355X_MICROARCH.md, "dequeue") and a returning atomic takes
 // microseconds under load -- every frame through ONE ticket word: 551 us; through 16 words on their own 128-byte
@@ -423,7 +462,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void os
     if (count) { const long long c = *count; nframes = c < F ? c : F; }
     // the OSD success counters ride along when the caller wants them (ldpc_pipeline_run): {frames, wrong, TEPs};
     // frames and TEPs are known up front, a wrong codeword costs one fire-and-forget atomic (~6 % of the frames)
-    if (counts && blockIdx.x == 0 && lane == 0) { atomicAdd(&counts[0], (u64)nframes); atomicAdd(&counts[2], (u64)nframes * 2081ull); }
+    if (counts && blockIdx.x == 0 && lane == 0) {
+        atomicAdd(&counts[0], (u64)nframes);
+        if (ntep_out) atomicAdd(&counts[2], (u64)nframes * 2081ull);       // TEPs only with d_ntep, as osd_counts_kernel
+    }
     // software pipeline over the frames of this workgroup: (o, P) two frames ahead, y one frame ahead
     const long long G = gridDim.x;
     long long f0 = blockIdx.x, f1 = f0 + G, f2 = f1 + G;
@@ -454,36 +496,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void os
             srcc = index ? index[f2] : f2;
         }
         // ---- frame f0
-        SearchFrame S;
-        S.o1 = o1a; S.o2 = o2a;
-        const float w1 = __builtin_fabsf(y1a), w2 = __builtin_fabsf(y2a);
-        LL.wpar()[lane] = w2;
-        S.hm = __ballot(!(y1a > 0.0f));
-        S.hp = __ballot(!(y2a > 0.0f));
-        wave_fence();
-        build_byte_luts<8>(LL.lut, LL.wpar(), lane);
-        S.d0 = wave_xor64(((S.hm >> lane) & 1) ? Pa : 0ull) ^ S.hp;
-        wave_fence();
-        float best; int bestt; u64 bestD, bestE;
-        search2r_device(LL, S, Pa, w1, dir, base2, lane, best, bestt, bestD, bestE);
-        {   // search_finish, with the codeword words still in hand for the success test (convention_osd.py:65-66)
-            const u64 mrb_bits = S.hm ^ bestE, par_bits = bestD ^ S.hp;
-            u64 *const cw = LL.cw();
-            if (lane < 2) cw[lane] = 0;
-            wave_fence();
-            if ((mrb_bits >> lane) & 1) atomicOr(&cw[S.o1 >> 6], 1ull << (S.o1 & 63));
-            if ((par_bits >> lane) & 1) atomicOr(&cw[S.o2 >> 6], 1ull << (S.o2 & 63));
-            wave_fence();
-            const u64 word = lane < 2 ? cw[lane] : 0ull;
-            if (lane < 2) cw_out[f0 * 2 + lane] = word;
-            if (counts && __ballot(lane < 2 && word != laba) && lane == 0) atomicAdd(&counts[1], 1ull);
-            wave_fence();
-        }
-        if (lane == 0) {
-            if (metric_out) metric_out[f0] = best;
-            if (best_out) best_out[f0] = bestt;
-            if (ntep_out) ntep_out[f0] = 2081;
-        }
+        search2r_frame(LL, o1a, o2a, Pa, y1a, y2a, dir, base2, f0, laba, lane, cw_out, metric_out, best_out, ntep_out, counts);
         // ---- rotate the pipeline
         f0 = f1; f1 = f2; f2 += G;
         o1a = o1b; o2a = o2b; Pa = Pb; srca = srcb; y1a = y1b; y2a = y2b; laba = labb;
@@ -513,7 +526,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void os
     const int lane = threadIdx.x;
     long long nframes = F;
     if (count) { const long long c = *count; nframes = c < F ? c : F; }
-    if (counts && blockIdx.x == 0 && lane == 0) { atomicAdd(&counts[0], (u64)nframes); atomicAdd(&counts[2], (u64)nframes * 2081ull); }
+    if (counts && blockIdx.x == 0 && lane == 0) {
+        atomicAdd(&counts[0], (u64)nframes);
+        if (ntep_out) atomicAdd(&counts[2], (u64)nframes * 2081ull);       // TEPs only with d_ntep, as osd_counts_kernel
+    }
     // software pipeline over the frames of this workgroup: the frame number two frames ahead, the y row one frame ahead
     const long long G = gridDim.x;
     long long f0 = blockIdx.x, f1 = f0 + G, f2 = f1 + G;
@@ -534,38 +550,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void os
         const FrontResult fr = front_device_vals(LF, __float_as_uint(ya1) & 0x7FFFFFFFu, __float_as_uint(ya2) & 0x7FFFFFFFu, Gcols, lane);
         const float y1 = yrow[fr.o1], y2 = yrow[fr.o2];            // y'[p] = y[perm[p]]
         wave_fence();
-        // ---- scan (the frame body of osd_search2r_kernel)
-        SearchFrame S;
-        S.o1 = fr.o1; S.o2 = fr.o2;
-        const u64 Pa = fr.Prow;
-        const float w1 = __builtin_fabsf(y1), w2 = __builtin_fabsf(y2);
-        LL.wpar()[lane] = w2;
-        S.hm = __ballot(!(y1 > 0.0f));
-        S.hp = __ballot(!(y2 > 0.0f));
-        wave_fence();
-        build_byte_luts<8>(LL.lut, LL.wpar(), lane);
-        S.d0 = wave_xor64(((S.hm >> lane) & 1) ? Pa : 0ull) ^ S.hp;
-        wave_fence();
-        float best; int bestt; u64 bestD, bestE;
-        search2r_device(LL, S, Pa, w1, dir, base2, lane, best, bestt, bestD, bestE);
-        {
-            const u64 mrb_bits = S.hm ^ bestE, par_bits = bestD ^ S.hp;
-            u64 *const cw = LL.cw();
-            if (lane < 2) cw[lane] = 0;
-            wave_fence();
-            if ((mrb_bits >> lane) & 1) atomicOr(&cw[S.o1 >> 6], 1ull << (S.o1 & 63));
-            if ((par_bits >> lane) & 1) atomicOr(&cw[S.o2 >> 6], 1ull << (S.o2 & 63));
-            wave_fence();
-            const u64 word = lane < 2 ? cw[lane] : 0ull;
-            if (lane < 2) cw_out[f0 * 2 + lane] = word;
-            if (counts && __ballot(lane < 2 && word != laba) && lane == 0) atomicAdd(&counts[1], 1ull);
-            wave_fence();
-        }
-        if (lane == 0) {
-            if (metric_out) metric_out[f0] = best;
-            if (best_out) best_out[f0] = bestt;
-            if (ntep_out) ntep_out[f0] = 2081;
-        }
+        // ---- scan
+        search2r_frame(LL, fr.o1, fr.o2, fr.Prow, y1, y2, dir, base2, f0, laba, lane, cw_out, metric_out, best_out, ntep_out, counts);
         f0 = f1; f1 = f2; f2 += G;
         srca = srcb; srcb = srcc; ya1 = yb1; ya2 = yb2; laba = labb;
     }
@@ -813,6 +799,7 @@ void osd_ctx_release(ldpc_ctx *ctx)
         (void)hipFree(st->d_base2);
         (void)hipFree(st->d_cdf_half);
         (void)hipFree(st->d_index_errors);
+        for (unsigned long long *d : st->d_pb_prof) (void)hipFree(d);
         delete st;
     }
     ctx->osd_state = nullptr;
@@ -907,22 +894,131 @@ static unsigned osd_grid(int64_t F)
     return (unsigned)(want < 1 ? 1 : (want < 4096 ? want : 4096));
 }
 
+static const char *flag_name(unsigned f)   // the lowest LDPC_OSD_F_* flag in f
+{
+    if (f & LDPC_OSD_F_TABLE_SCAN) return "LDPC_OSD_F_TABLE_SCAN";
+    if (f & LDPC_OSD_F_PB_BLOCK) return "LDPC_OSD_F_PB_BLOCK";
+    if (f & LDPC_OSD_F_PB_REPLAY) return "LDPC_OSD_F_PB_REPLAY";
+    if (f & LDPC_OSD_F_READLANE_SCAN) return "LDPC_OSD_F_READLANE_SCAN";
+    return "LDPC_OSD_F_PB_FRONT_INSIDE";
+}
 
-}  // namespace ldpc
-
-using namespace ldpc;
-
-extern "C" {
-
-static int check_params(ldpc_ctx *ctx, const ldpc_osd_params *p, const char *who)
+int check_params(ldpc_ctx *ctx, const ldpc_osd_params *p, bool front_outside, const char *who)
 {
     if (!ctx->osd_ok) return fail(LDPC_E_UNSUPPORTED, "OSD kernels need an (n=128, k=64) code; this one is (%d,%d)", ctx->code.n, ctx->code.k);
     if (p->order < 0 || p->order > 3) return fail(LDPC_E_ARG, "%s: order %d outside 0..3", who, p->order);
     if (p->algo != LDPC_OSD_CONVENTIONAL && p->algo != LDPC_OSD_FS && p->algo != LDPC_OSD_PB)
         return fail(LDPC_E_ARG, "%s: unknown search algorithm %d", who, p->algo);
     if (p->algo == LDPC_OSD_PB && p->order < 1) return fail(LDPC_E_ARG, "%s: PB-OSD needs order >= 1", who);
+    const unsigned f = (unsigned)p->flags;
+    const unsigned conv = LDPC_OSD_F_TABLE_SCAN | LDPC_OSD_F_READLANE_SCAN;
+    const unsigned pb = LDPC_OSD_F_PB_BLOCK | LDPC_OSD_F_PB_REPLAY | LDPC_OSD_F_PB_FRONT_INSIDE;
+    if (f & ~(conv | pb)) return fail(LDPC_E_ARG, "%s: flags 0x%x are no LDPC_OSD_F_* flag", who, f & ~(conv | pb));
+    if ((f & conv) && p->algo != LDPC_OSD_CONVENTIONAL)
+        return fail(LDPC_E_ARG, "%s: %s needs the conventional algorithm, not %d", who, flag_name(f & conv), p->algo);
+    if ((f & LDPC_OSD_F_READLANE_SCAN) && (p->order != 2 || (f & LDPC_OSD_F_TABLE_SCAN)))
+        return fail(LDPC_E_ARG, "%s: LDPC_OSD_F_READLANE_SCAN needs order 2 (not %d) and no LDPC_OSD_F_TABLE_SCAN", who, p->order);
+    if ((f & pb) && p->algo != LDPC_OSD_PB)
+        return fail(LDPC_E_ARG, "%s: %s needs the PB algorithm, not %d", who, flag_name(f & pb), p->algo);
+    if ((f & LDPC_OSD_F_PB_REPLAY) && (f & (LDPC_OSD_F_PB_BLOCK | LDPC_OSD_F_PB_FRONT_INSIDE)))
+        return fail(LDPC_E_ARG, "%s: LDPC_OSD_F_PB_REPLAY excludes %s", who, flag_name(f & (LDPC_OSD_F_PB_BLOCK | LDPC_OSD_F_PB_FRONT_INSIDE)));
+    if ((f & LDPC_OSD_F_PB_FRONT_INSIDE) && front_outside)
+        return fail(LDPC_E_ARG, "%s: LDPC_OSD_F_PB_FRONT_INSIDE keeps the front-end results inside the PB kernels, and this call "
+                    "supplies or wants them", who);
     return LDPC_OK;
 }
+
+OsdPlan select_route(const ldpc_ctx *ctx, const ldpc_osd_params *p, bool front_outside)
+{
+    const unsigned f = (unsigned)p->flags;
+    if (p->algo == LDPC_OSD_FS) return {OsdRoute::Fs, 0};
+    if (p->algo == LDPC_OSD_PB)
+        return {(f & LDPC_OSD_F_PB_FRONT_INSIDE) ? OsdRoute::PbFrontInside : OsdRoute::PbStaged,
+                (f & LDPC_OSD_F_PB_REPLAY) ? 2 : ((f & LDPC_OSD_F_PB_BLOCK) ? 1 : 0)};
+    if (p->order != 2 || (f & LDPC_OSD_F_TABLE_SCAN)) return {OsdRoute::Table, 0};
+    // the rotation-paired kernels need the probed wave_rol:1 direction
+    if ((f & LDPC_OSD_F_READLANE_SCAN) || ctx->dpp_wave_rol_dir == 0) return {OsdRoute::Search2, 0};
+    return {front_outside ? OsdRoute::Search2r : OsdRoute::Fused2r, 0};
+}
+
+int osd_launch(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F, const uint8_t *d_perm,
+               const uint64_t *d_parity, const ldpc_osd_params *p, uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_ntep,
+               const uint64_t *d_label, int64_t *d_counts, hipStream_t s, bool *counted)
+{
+    *counted = false;
+    const OsdPlan r = select_route(ctx, p, d_perm != nullptr);
+    OsdState *st = state(ctx);
+    int rc;
+    if ((rc = guarded_index(ctx, p, d_index, d_count, F, s, &d_index))) return rc;
+    if (!d_perm && r.route != OsdRoute::Fused2r && r.route != OsdRoute::PbFrontInside) {   // the front end into the stream's workspace
+        StreamWs *w;
+        if ((rc = stream_ws(ctx, s, F, &w))) return rc;
+        hipLaunchKernelGGL(osd_front_kernel, dim3((unsigned)(F < 65536 ? F : 65536)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
+                           reinterpret_cast<const u64 *>(ctx->d_Gcols), w->d_perm, w->d_parity, (int *)nullptr);
+        d_perm = w->d_perm; d_parity = reinterpret_cast<const uint64_t *>(w->d_parity);
+    }
+    const u64 *const parity = reinterpret_cast<const u64 *>(d_parity);
+    u64 *const cw = reinterpret_cast<u64 *>(d_cw);
+    const u64 *const label = d_label && d_counts ? reinterpret_cast<const u64 *>(d_label) : nullptr;
+    u64 *const counts = label ? reinterpret_cast<u64 *>(d_counts) : nullptr;
+    // the rotation-paired kernels: 4 wavefronts per SIMD are resident (10 KiB of LDS each); the grid is 6x that, ~1.5 frames per
+    // workgroup at the headline size: the dispatcher then evens out the different scan times, and the prefetch still covers the
+    // second frame (measured, 33 487 frames: 1x 119 us, 2x 117, 3x 108, 4x 107, 6x 100, 9x 102 per call incl. events)
+    const long long grid2r = (long long)ctx->cu_count * 16 * 6;
+    const unsigned g2r = (unsigned)(F < grid2r ? F : grid2r), g64 = (unsigned)(F < 65536 ? F : 65536);
+    switch (r.route) {
+    case OsdRoute::Fused2r:
+        hipLaunchKernelGGL(osd_fused2r_kernel, dim3(g2r), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
+                           reinterpret_cast<const u64 *>(ctx->d_Gcols), ctx->dpp_wave_rol_dir, st->d_base2, cw, d_metric, d_best, d_ntep,
+                           label, counts);
+        *counted = label != nullptr;
+        break;
+    case OsdRoute::Search2r:
+        hipLaunchKernelGGL(osd_search2r_kernel, dim3(g2r), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity,
+                           ctx->dpp_wave_rol_dir, st->d_base2, cw, d_metric, d_best, d_ntep, label, counts);
+        *counted = label != nullptr;
+        break;
+    case OsdRoute::Search2:
+        hipLaunchKernelGGL(osd_search2_kernel, dim3(g64), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity, st->d_base2,
+                           cw, d_metric, d_best, d_ntep);
+        break;
+    case OsdRoute::Table:
+        if (p->order >= 2)
+            hipLaunchKernelGGL(osd_search_kernel<1>, dim3(g64), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity,
+                               reinterpret_cast<const uchar4 *>(ctx->d_tep), (int)st->ntep[p->order], cw, d_metric, d_best, d_ntep);
+        else
+            hipLaunchKernelGGL(osd_search_kernel<4>, dim3(osd_grid(F)), dim3(256), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity,
+                               reinterpret_cast<const uchar4 *>(ctx->d_tep), (int)st->ntep[p->order], cw, d_metric, d_best, d_ntep);
+        break;
+    case OsdRoute::Fs: {
+        FsParams fp;
+        fp.order = p->order; fp.quirk = p->fs_reference_quirk != 0;
+        fp.beta_term = (float)((double)p->fs_beta * (double)(kOsdN - kOsdK));   // fs_testing.py:138
+        fp.tau_e = p->fs_tau_e; fp.tau_psc = p->fs_tau_psc;
+        for (int w = 0; w < 4; ++w) { fp.cls_off[w] = st->fs_off[w]; fp.cls_cnt[w] = st->fs_cnt[w]; }
+        hipLaunchKernelGGL(osd_fs_kernel, dim3(g64), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity, st->d_tep_fs, fp,
+                           cw, d_metric, d_best, d_ntep);
+        break;
+    }
+    case OsdRoute::PbStaged:
+        return launch_pb(ctx, d_y, d_index, d_count, F, d_perm, parity, p, r.pb_mode, false, d_cw, d_metric, d_best, d_ntep, s);
+    // The front end INSIDE the first PB kernel, nothing through a workspace (not the list replay, which needs records to set a
+    // frame up from).  Measured against the two kernels (osd_front + pb_singles, per 131 072-frame step): 170 against 164 us at
+    // 2.5 dB, 507 against 481 us at 1.0 dB, 58 against 102 MB and 236 against 400 MB of HBM traffic -- the path is
+    // instruction-bound, the traffic was never its limiter: an option, not the default.
+    case OsdRoute::PbFrontInside:
+        return launch_pb(ctx, d_y, d_index, d_count, F, nullptr, nullptr, p, r.pb_mode, true, d_cw, d_metric, d_best, d_ntep, s);
+    }
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+
+}  // namespace ldpc
+
+using namespace ldpc;
+
+extern "C" {
 
 int ldpc_osd_reserve(ldpc_ctx *ctx, int64_t max_frames)
 {
@@ -941,10 +1037,10 @@ int ldpc_osd_reserve_stream(ldpc_ctx *ctx, int64_t max_frames, const ldpc_osd_pa
 {
     if (!ctx || max_frames < 0) return fail(LDPC_E_ARG, "ldpc_osd_reserve_stream: bad arguments");
     if (!ctx->osd_ok) return fail(LDPC_E_UNSUPPORTED, "OSD kernels need an (n=128, k=64) code; this one is (%d,%d)", ctx->code.n, ctx->code.k);
+    int rc;
+    if (params && (rc = check_params(ctx, params, false, "ldpc_osd_reserve_stream"))) return rc;
     StreamWs *w;
-    int rc = stream_ws(ctx, (hipStream_t)stream, max_frames, &w);
-    if (rc || !params) return rc;
-    if ((rc = check_params(ctx, params, "ldpc_osd_reserve_stream"))) return rc;
+    if ((rc = stream_ws(ctx, (hipStream_t)stream, max_frames, &w)) || !params) return rc;
     if (params->algo == LDPC_OSD_PB && max_frames > 0) return pb_reserve(ctx, (hipStream_t)stream, max_frames, params->order);
     return LDPC_OK;
 }
@@ -987,126 +1083,17 @@ int ldpc_osd_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, cons
     return LDPC_OK;
 }
 
-// launches the search kernel selected by p->algo on front-end results (d_perm, d_parity)
-// label / counts / fused: the success counters of ldpc_osd_counts accumulated by the search kernel itself where it can
-// (*fused is set then, and the caller skips the separate counting launch)
-static int launch_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
-                         const unsigned char *d_perm, const u64 *d_parity, const ldpc_osd_params *p, uint64_t *d_cw,
-                         float *d_metric, int32_t *d_best, int32_t *d_ntep, hipStream_t s, const uint64_t *d_label = nullptr,
-                         int64_t *d_counts = nullptr, bool *fused = nullptr)
-{
-    if (fused) *fused = false;
-    OsdState *st = state(ctx);
-    if (p->algo == LDPC_OSD_PB) {
-        return launch_pb(ctx, d_y, d_index, d_count, F, d_perm, d_parity, p, d_cw, d_metric, d_best, d_ntep, s);
-    } else if (p->algo == LDPC_OSD_FS) {
-        FsParams fp;
-        fp.order = p->order; fp.quirk = p->fs_reference_quirk != 0;
-        fp.beta_term = (float)((double)p->fs_beta * (double)(kOsdN - kOsdK));   // fs_testing.py:138
-        fp.tau_e = p->fs_tau_e; fp.tau_psc = p->fs_tau_psc;
-        for (int w = 0; w < 4; ++w) { fp.cls_off[w] = st->fs_off[w]; fp.cls_cnt[w] = st->fs_cnt[w]; }
-        hipLaunchKernelGGL(osd_fs_kernel, dim3((unsigned)(F < 65536 ? F : 65536)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
-                           d_perm, d_parity, st->d_tep_fs, fp, reinterpret_cast<u64 *>(d_cw), d_metric, d_best,
-                           d_ntep);
-    } else if (p->order == 2 && !(p->reserved & 1) && ctx->dpp_wave_rol_dir != 0 && !(p->reserved & 8)) {
-        // 4 wavefronts per SIMD are resident (10 KiB of LDS each); the grid is 6x that, ~1.5 frames per workgroup at the
-        // headline size: the dispatcher then evens out the different scan times, and the prefetch still covers the second
-        // frame (measured, 33 487 frames: 1x 119 us, 2x 117, 3x 108, 4x 107, 6x 100, 9x 102 per call incl. events)
-        const long long grid = (long long)ctx->cu_count * 16 * 6;
-        hipLaunchKernelGGL(osd_search2r_kernel, dim3((unsigned)(F < grid ? F : grid)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
-                           d_perm, d_parity, ctx->dpp_wave_rol_dir, st->d_base2, reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_ntep,
-                           reinterpret_cast<const u64 *>(d_label), d_label ? reinterpret_cast<u64 *>(d_counts) : nullptr);
-        if (fused && d_label && d_counts) *fused = true;
-    } else if (p->order == 2 && !(p->reserved & 1)) {
-        hipLaunchKernelGGL(osd_search2_kernel, dim3((unsigned)(F < 65536 ? F : 65536)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
-                           d_perm, d_parity, st->d_base2, reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_ntep);
-    } else {   // table-driven scan: any order (and order 2 when params->reserved = 1, the cross-check path)
-        if (p->order >= 2)
-            hipLaunchKernelGGL(osd_search_kernel<1>, dim3((unsigned)(F < 65536 ? F : 65536)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
-                               d_perm, d_parity, reinterpret_cast<const uchar4 *>(ctx->d_tep), (int)st->ntep[p->order],
-                               reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_ntep);
-        else
-            hipLaunchKernelGGL(osd_search_kernel<4>, dim3(osd_grid(F)), dim3(256), 0, s, d_y, d_index, d_count, (long long)F,
-                               d_perm, d_parity, reinterpret_cast<const uchar4 *>(ctx->d_tep), (int)st->ntep[p->order],
-                               reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_ntep);
-    }
-    LDPC_HIP(hipGetLastError());
-    return LDPC_OK;
-}
-
-}  // extern "C"
-
-namespace ldpc {
-// ldpc_osd_decode (+ ldpc_osd_counts where the kernel can count itself: *counted_by_search).  The conventional order-2 OSD runs
-// front end and scan in ONE kernel with no workspace (osd_fused2r_kernel); everything else the front end into the stream's
-// workspace, then the search.  (params->reserved bits 0 / 3, the cross-check scans, keep the two-kernel route.)
-int osd_decode_counted(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
-                       const ldpc_osd_params *p, uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_ntep,
-                       const uint64_t *d_label, int64_t *d_counts, hipStream_t s, bool *counted_by_search)
-{
-    if (counted_by_search) *counted_by_search = false;
-    int rc;
-    if ((rc = guarded_index(ctx, p, d_index, d_count, F, s, &d_index))) return rc;
-    if (p->algo == LDPC_OSD_CONVENTIONAL && p->order == 2 && !(p->reserved & 9) && ctx->dpp_wave_rol_dir != 0) {
-        const long long grid = (long long)ctx->cu_count * 16 * 6;      // (as the scan alone: 6x the resident wavefronts)
-        const bool cnt = d_label && d_counts;
-        hipLaunchKernelGGL(osd_fused2r_kernel, dim3((unsigned)(F < grid ? F : grid)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
-                           reinterpret_cast<const u64 *>(ctx->d_Gcols), ctx->dpp_wave_rol_dir, state(ctx)->d_base2,
-                           reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_ntep, cnt ? reinterpret_cast<const u64 *>(d_label) : nullptr,
-                           cnt ? reinterpret_cast<u64 *>(d_counts) : nullptr);
-        LDPC_HIP(hipGetLastError());
-        if (counted_by_search) *counted_by_search = cnt;
-        return LDPC_OK;
-    }
-    // PB-OSD with reserved bit 0: the front end runs INSIDE the first PB kernel and nothing goes through a workspace (round 4;
-    // not with bit 2, the list-replay route, which writes no records to set a frame up from).  Measured against the two kernels
-    // (osd_front + pb_singles, per 131 072-frame step): 170 against 164 us at 2.5 dB, 507 against 481 us at 1.0 dB, 58 against 102 MB
-    // and 236 against 400 MB of HBM traffic -- the path is instruction-bound, the traffic was never its limiter: an option, not
-    // the default.
-    if (p->algo == LDPC_OSD_PB && (p->reserved & 5) == 1)
-        return launch_pb(ctx, d_y, d_index, d_count, F, nullptr, nullptr, p, d_cw, d_metric, d_best, d_ntep, s);
-    StreamWs *w;
-    if ((rc = stream_ws(ctx, s, F, &w))) return rc;
-    hipLaunchKernelGGL(osd_front_kernel, dim3((unsigned)(F < 65536 ? F : 65536)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
-                       reinterpret_cast<const u64 *>(ctx->d_Gcols), w->d_perm, w->d_parity, (int *)nullptr);
-    return launch_search(ctx, d_y, d_index, d_count, F, w->d_perm, w->d_parity, p, d_cw, d_metric, d_best, d_ntep, s);
-}
-
-// ldpc_osd_search + ldpc_osd_counts for ldpc_pipeline_run: one launch where the search kernel can count itself
-int osd_search_counted(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
-                       const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *p, uint64_t *d_cw, float *d_metric,
-                       int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label, int64_t *d_counts, hipStream_t s, bool *counted_by_search)
-{
-    if (counted_by_search) *counted_by_search = false;
-    if (!ctx || !p || F < 0 || (F > 0 && (!d_y || !d_cw || !d_perm || !d_parity)))
-        return fail(LDPC_E_ARG, "ldpc_osd_search: bad arguments");
-    int rc = check_params(ctx, p, "ldpc_osd_search");
-    if (rc) return rc;
-    if (F == 0) return LDPC_OK;
-    if ((rc = guarded_index(ctx, p, d_index, d_count, F, s, &d_index))) return rc;
-    bool fused = false;
-    rc = launch_search(ctx, d_y, d_index, d_count, F, d_perm, reinterpret_cast<const u64 *>(d_parity), p, d_cw, d_metric, d_best, d_ntep,
-                       s, d_label, d_counts, &fused);
-    if (counted_by_search) { *counted_by_search = fused; return rc; }     // (the caller places the counting launch itself)
-    if (rc || fused || !d_label || !d_counts) return rc;
-    return ldpc_osd_counts(ctx, d_cw, d_label, d_index, d_count, d_ntep, F, d_counts, s);
-}
-}  // namespace ldpc
-
-extern "C" {
-
 int ldpc_osd_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
                     const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *p, uint64_t *d_cw,
                     float *d_metric, int32_t *d_best, int32_t *d_ntep, void *stream)
 {
     if (!ctx || !p || F < 0 || (F > 0 && (!d_y || !d_cw || !d_perm || !d_parity)))
         return fail(LDPC_E_ARG, "ldpc_osd_search: bad arguments");
-    int rc = check_params(ctx, p, "ldpc_osd_search");
-    if (rc) return rc;
-    if (F == 0) return LDPC_OK;
-    if ((rc = guarded_index(ctx, p, d_index, d_count, F, (hipStream_t)stream, &d_index))) return rc;
-    return launch_search(ctx, d_y, d_index, d_count, F, d_perm, reinterpret_cast<const u64 *>(d_parity), p, d_cw, d_metric,
-                         d_best, d_ntep, (hipStream_t)stream);
+    int rc = check_params(ctx, p, true, "ldpc_osd_search");
+    if (rc || F == 0) return rc;
+    bool counted;
+    return osd_launch(ctx, d_y, d_index, d_count, F, d_perm, d_parity, p, d_cw, d_metric, d_best, d_ntep, nullptr, nullptr,
+                      (hipStream_t)stream, &counted);
 }
 
 int ldpc_osd_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
@@ -1114,10 +1101,11 @@ int ldpc_osd_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, con
                     void *stream)
 {
     if (!ctx || !p || F < 0 || (F > 0 && (!d_y || !d_cw))) return fail(LDPC_E_ARG, "ldpc_osd_decode: bad arguments");
-    int rc = check_params(ctx, p, "ldpc_osd_decode");
-    if (rc) return rc;
-    if (F == 0) return LDPC_OK;
-    return osd_decode_counted(ctx, d_y, d_index, d_count, F, p, d_cw, d_metric, d_best, d_ntep, nullptr, nullptr, (hipStream_t)stream, nullptr);
+    int rc = check_params(ctx, p, false, "ldpc_osd_decode");
+    if (rc || F == 0) return rc;
+    bool counted;
+    return osd_launch(ctx, d_y, d_index, d_count, F, nullptr, nullptr, p, d_cw, d_metric, d_best, d_ntep, nullptr, nullptr,
+                      (hipStream_t)stream, &counted);
 }
 
 int ldpc_osd_index_errors(ldpc_ctx *ctx, int64_t *count)

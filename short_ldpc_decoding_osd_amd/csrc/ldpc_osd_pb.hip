@@ -3034,7 +3034,14 @@ ldpc_pb_tuning pb_default_tuning()
 
 int pb_ctx_init(ldpc_ctx *ctx)
 {
-    state(ctx)->pb_tuning = pb_default_tuning();
+    OsdState *st = state(ctx);
+    st->pb_tuning = pb_default_tuning();
+    // LDPC_PB_PROFILE (diagnostics, scripts/pb_profile_run.py): launch_pb runs the stamped builds and prints their counters
+    st->pb_profile = getenv("LDPC_PB_PROFILE") != nullptr;
+    if (st->pb_profile) {
+        const int slots[3] = {8, kPwSlots, kPcSlots};
+        for (int k = 0; k < 3; ++k) LDPC_HIP(hipMalloc((void **)&st->d_pb_prof[k], sizeof(unsigned long long) * slots[k]));
+    }
     static_assert(sizeof(PbCoopLds<kPbCoopW>) * (16 / kPbCoopW) <= 160 * 1024, "16 wavefronts of this kernel per CU");
     LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pb_coop_kernel<kPbCoopW, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)sizeof(PbCoopLds<kPbCoopW>)));
@@ -3101,11 +3108,22 @@ int pb_reserve(ldpc_ctx *ctx, hipStream_t s, int64_t frames, int order)
     return stream_ws_pb(ctx, s, frames, stride, &w);
 }
 
+// LDPC_PB_PROFILE: the counters of a stamped launch, after waiting for it
+static int pb_prof_read(const unsigned long long *d, unsigned long long *h, int n, hipStream_t s)
+{
+    LDPC_HIP(hipMemcpyAsync(h, d, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, s));
+    LDPC_HIP(hipStreamSynchronize(s));
+    return LDPC_OK;
+}
+
 int launch_pb(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
-              const unsigned char *d_perm, const u64 *d_parity, const ldpc_osd_params *p, uint64_t *d_cw, float *d_metric,
-              int32_t *d_best, int32_t *d_ntep, hipStream_t s)
+              const unsigned char *d_perm, const u64 *d_parity, const ldpc_osd_params *p, int pb_mode, bool front_inside,
+              uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_ntep, hipStream_t s)
 {
     OsdState *st = state(ctx);
+    const bool prof = st->pb_profile;
+    if (prof && stream_capturing(s))
+        return fail(LDPC_E_ARG, "PB-OSD: LDPC_PB_PROFILE waits for its counters after each kernel, which a stream capture forbids");
     const int64_t nmax = st->ntep[p->order];
     int64_t spill_slots, stride;
     int rc = pb_spill_layout(ctx, p->order, &spill_slots, &stride);
@@ -3136,7 +3154,6 @@ int launch_pb(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int
     pp.late_min = tn.late_min; pp.late_maxlen = tn.late_maxlen; pp.late_pct = tn.late_pct; pp.late_div = tn.late_div;
     pp.handoff_maxlen = tn.handoff_maxlen;
     pp.c4 = (float)(-4.0 * (1.0 / pow(10.0, (double)p->snr_db / 10.0)));    // -4 * noise_variance, pb_testing.py:50-52
-    const int mode = (p->reserved & 4) ? 2 : ((p->reserved & 2) ? 1 : 0);
     PbOut O{reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_ntep, reinterpret_cast<int *>(p->d_aux)};
     const int64_t list_len = (int64_t)kPbSub * w->pb_sub_cap;   // >= pb_cap
     int *listA = w->d_pb_list, *listB = w->d_pb_list + list_len;
@@ -3146,88 +3163,70 @@ int launch_pb(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int
     hipLaunchKernelGGL(pb_ctl_clear_kernel, dim3(1), dim3(64), 0, s, w->d_pb_ctl);
     const int64_t want = (F + 3) / 4;
     const unsigned g1 = (unsigned)(F < 1 ? 1 : (F < 32768 ? F : 32768));
-    static const bool profile_s = getenv("LDPC_PB_PROFILE") != nullptr;
-    // d_perm == nullptr (ldpc_osd_decode's route): the front end runs inside the singles kernel, nothing goes through a workspace
-    // -- the frames of list B are then set up from the singles records (mode 2, every frame to the list replay, writes none:
-    // the caller keeps the two-kernel route for it)
-    const bool fused_front = d_perm == nullptr;
-    if (fused_front && (mode == 2 || d_parity != nullptr))
-        return fail(LDPC_E_ARG, "PB-OSD: the fused front end needs both front-end buffers absent and is not the list-replay route");
+    // front_inside (ldpc_osd_decode's option): the front end runs inside the singles kernel, nothing goes through a workspace --
+    // the frames of list B are then set up from the singles records (mode 2, every frame to the list replay, writes none)
     const u64 *const Gcols = reinterpret_cast<const u64 *>(ctx->d_Gcols);
-    if (fused_front) {
-        hipLaunchKernelGGL((pb_singles_kernel<false, true>), dim3(g1), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, d_parity, Gcols, pp, mode,
-                           st->d_cdf_half, w->d_pb_ctl, listA, listB, sub_cap, recs, O, (unsigned long long *)nullptr);
-    } else if (!profile_s) {
-        hipLaunchKernelGGL((pb_singles_kernel<false, false>), dim3(g1), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, d_parity, Gcols, pp, mode,
-                           st->d_cdf_half, w->d_pb_ctl, listA, listB, sub_cap, recs, O, (unsigned long long *)nullptr);
+    unsigned long long h[kPcSlots > kPwSlots ? kPcSlots : kPwSlots];
+    if (front_inside) {
+        hipLaunchKernelGGL((pb_singles_kernel<false, true>), dim3(g1), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, d_parity, Gcols, pp,
+                           pb_mode, st->d_cdf_half, w->d_pb_ctl, listA, listB, sub_cap, recs, O, (unsigned long long *)nullptr);
+        if (prof) fprintf(stderr, "[LDPC_PB_PROFILE] singles kernel with the front end inside: no stamped build, no counters\n");
+    } else if (!prof) {
+        hipLaunchKernelGGL((pb_singles_kernel<false, false>), dim3(g1), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, d_parity, Gcols, pp,
+                           pb_mode, st->d_cdf_half, w->d_pb_ctl, listA, listB, sub_cap, recs, O, (unsigned long long *)nullptr);
     } else {
-        static unsigned long long *d_ps = nullptr;
-        if (!d_ps) LDPC_HIP(hipMalloc((void **)&d_ps, sizeof(unsigned long long) * 8));
-        LDPC_HIP(hipMemsetAsync(d_ps, 0, sizeof(unsigned long long) * 8, s));
-        hipLaunchKernelGGL((pb_singles_kernel<true, false>), dim3(g1), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, d_parity, Gcols, pp, mode,
-                           st->d_cdf_half, w->d_pb_ctl, listA, listB, sub_cap, recs, O, d_ps);
-        unsigned long long h[8];
-        LDPC_HIP(hipMemcpyAsync(h, d_ps, sizeof(h), hipMemcpyDeviceToHost, s));
-        LDPC_HIP(hipStreamSynchronize(s));
+        LDPC_HIP(hipMemsetAsync(st->d_pb_prof[0], 0, sizeof(unsigned long long) * 8, s));
+        hipLaunchKernelGGL((pb_singles_kernel<true, false>), dim3(g1), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, d_parity, Gcols, pp,
+                           pb_mode, st->d_cdf_half, w->d_pb_ctl, listA, listB, sub_cap, recs, O, st->d_pb_prof[0]);
+        if ((rc = pb_prof_read(st->d_pb_prof[0], h, 8, s))) return rc;
         fprintf(stderr, "[LDPC_PB_PROFILE] singles kernel, cycles of lane 0 summed over wavefronts: start+perm/P' loads=%llu y loads+LUT=%llu frame_setup=%llu rules=%llu hand_on=%llu write=%llu\n",
                 h[5], h[0], h[1], h[2], h[3], h[4]);
     }
-    // chunk kernel: one workgroup (= one wavefront) per (sub-list, entry); a multiple of 16 workgroups, at most 65 536 (a
-    // workgroup then takes every 4096th entry of its sub-list).  Workgroups beyond their sub-list's length leave at once.
     // (three instantiations by what the context's probe of the wave_rol:1 DPP control found -- the walk rotates a copy of the
     //  weights through the wavefront: -1 = a lane receives its upper neighbour's value, +1 = its lower neighbour's, 0 = not a
     //  rotation: LDS reads instead)
     const int rot = ctx->dpp_wave_rol_dir;
-#define PB_WAVE_LAUNCH(PROFILED, prof_ptr)                                                                                           \
-    do {                                                                                                                             \
-        if (rot < 0) hipLaunchKernelGGL((pb_wave_kernel<kPbWaveCap, PROFILED, -1>), dim3(g2), dim3(64), 0, s, pp, st->d_cdf_half, w->d_pb_ctl, \
-                                        listA, listB, sub_cap, carry, recs, O, prof_ptr);                                            \
-        else if (rot > 0) hipLaunchKernelGGL((pb_wave_kernel<kPbWaveCap, PROFILED, 1>), dim3(g2), dim3(64), 0, s, pp, st->d_cdf_half, w->d_pb_ctl, \
-                                             listA, listB, sub_cap, carry, recs, O, prof_ptr);                                       \
-        else hipLaunchKernelGGL((pb_wave_kernel<kPbWaveCap, PROFILED, 0>), dim3(g2), dim3(64), 0, s, pp, st->d_cdf_half, w->d_pb_ctl, \
-                                listA, listB, sub_cap, carry, recs, O, prof_ptr);                                                    \
-    } while (0)
     // chunk kernel: one workgroup (= one wavefront) per (sub-list, entry); a multiple of 16 workgroups, at most 65 536 (a
     // workgroup then takes every 4096th entry of its sub-list).  Workgroups beyond their sub-list's length leave at once.
     const int64_t g2w = ((F + kPbSub - 1) / kPbSub) * kPbSub;
     const unsigned g2 = (unsigned)(g2w < 65536 ? g2w : 65536);
-    if (!profile_s) {
-        PB_WAVE_LAUNCH(false, (unsigned long long *)nullptr);
+    auto wave_launch = [&](auto profiled, unsigned long long *prof_out) {
+        constexpr bool PROF = decltype(profiled)::value;
+        if (rot < 0) hipLaunchKernelGGL((pb_wave_kernel<kPbWaveCap, PROF, -1>), dim3(g2), dim3(64), 0, s, pp, st->d_cdf_half, w->d_pb_ctl,
+                                        listA, listB, sub_cap, carry, recs, O, prof_out);
+        else if (rot > 0) hipLaunchKernelGGL((pb_wave_kernel<kPbWaveCap, PROF, 1>), dim3(g2), dim3(64), 0, s, pp, st->d_cdf_half, w->d_pb_ctl,
+                                             listA, listB, sub_cap, carry, recs, O, prof_out);
+        else hipLaunchKernelGGL((pb_wave_kernel<kPbWaveCap, PROF, 0>), dim3(g2), dim3(64), 0, s, pp, st->d_cdf_half, w->d_pb_ctl,
+                                listA, listB, sub_cap, carry, recs, O, prof_out);
+    };
+    if (!prof) {
+        wave_launch(std::false_type(), nullptr);
     } else {
-        static unsigned long long *d_pw = nullptr;
-        if (!d_pw) LDPC_HIP(hipMalloc((void **)&d_pw, sizeof(unsigned long long) * kPwSlots));
-        LDPC_HIP(hipMemsetAsync(d_pw, 0, sizeof(unsigned long long) * kPwSlots, s));
-        PB_WAVE_LAUNCH(true, d_pw);
-        unsigned long long h[kPwSlots];
-        LDPC_HIP(hipMemcpyAsync(h, d_pw, sizeof(h), hipMemcpyDeviceToHost, s));
-        LDPC_HIP(hipStreamSynchronize(s));
+        LDPC_HIP(hipMemsetAsync(st->d_pb_prof[1], 0, sizeof(unsigned long long) * kPwSlots, s));
+        wave_launch(std::true_type(), st->d_pb_prof[1]);
+        if ((rc = pb_prof_read(st->d_pb_prof[1], h, kPwSlots, s))) return rc;
         static const char *names[kPwSlots] = {"setup", "walk", "sort", "tie", "eval", "rules", "combine", "finish", "FRAMES", "CHUNKS", "WALKS", "KEYS", "sweepA", "sweepB", "dense", "ROUNDS", "TRIPS", "scan", "SORTEDCHUNKS", "load1", "load2", "store"};
         fprintf(stderr, "[LDPC_PB_PROFILE] chunk kernel, shader-clock ticks summed over wavefronts:");
         for (int q = 0; q < kPwSlots; ++q) fprintf(stderr, " %s=%llu", names[q], h[q]);
         fprintf(stderr, "\n");
     }
-#undef PB_WAVE_LAUNCH
     // the long searches the chunk kernel handed on (at most kPbHeavyCap, in two halves; the workgroups find an empty list otherwise)
     const unsigned g4 = (unsigned)(F < kPbCoopGrid ? F : kPbCoopGrid);
-    if (!profile_s) {
+    if (!prof) {
         hipLaunchKernelGGL((pb_coop_kernel<kPbCoopW, false>), dim3(g4), dim3(64 * kPbCoopW), sizeof(PbCoopLds<kPbCoopW>), s,
                            pp, st->d_cdf_half, w->d_pb_ctl, listB, carry, O, (unsigned long long *)nullptr);
     } else {
-        static unsigned long long *d_pc = nullptr;
-        if (!d_pc) LDPC_HIP(hipMalloc((void **)&d_pc, sizeof(unsigned long long) * kPcSlots));
-        LDPC_HIP(hipMemsetAsync(d_pc, 0, sizeof(unsigned long long) * kPcSlots, s));
+        LDPC_HIP(hipMemsetAsync(st->d_pb_prof[2], 0, sizeof(unsigned long long) * kPcSlots, s));
         hipLaunchKernelGGL((pb_coop_kernel<kPbCoopW, true>), dim3(g4), dim3(64 * kPbCoopW), sizeof(PbCoopLds<kPbCoopW>), s,
-                           pp, st->d_cdf_half, w->d_pb_ctl, listB, carry, O, d_pc);
-        unsigned long long h[kPcSlots];
-        LDPC_HIP(hipMemcpyAsync(h, d_pc, sizeof(h), hipMemcpyDeviceToHost, s));
-        LDPC_HIP(hipStreamSynchronize(s));
+                           pp, st->d_cdf_half, w->d_pb_ctl, listB, carry, O, st->d_pb_prof[2]);
+        if ((rc = pb_prof_read(st->d_pb_prof[2], h, kPcSlots, s))) return rc;
         static const char *names[kPcSlots] = {"setup", "walk", "scan", "solo", "out", "FRAMES", "CHUNKS", "SOLOS", "SOLOKEYS", "KEYS", "COUNTS", "-", "-", "count", "generate", "count_exchange", "bound", "s_probe", "s_keys", "-", "s_survivors", "s_exchange", "s_candidates", "s_min", "s_positions"};
         fprintf(stderr, "[LDPC_PB_PROFILE] workgroup kernel, shader-clock ticks of thread 0 summed over workgroups:");
         for (int q = 0; q < kPcSlots; ++q) fprintf(stderr, " %s=%llu", names[q], h[q]);
         fprintf(stderr, "\n");
     }
     const unsigned g3 = (unsigned)(want < kPbSeqBlocks ? (want < 1 ? 1 : want) : kPbSeqBlocks);
-    hipLaunchKernelGGL(pb_seq_kernel, dim3(g3), dim3(256), 0, s, d_y, d_index, d_perm, d_parity, fused_front ? recs : (const unsigned *)nullptr, pp, st->d_cdf_half,
+    hipLaunchKernelGGL(pb_seq_kernel, dim3(g3), dim3(256), 0, s, d_y, d_index, d_perm, d_parity, front_inside ? recs : (const unsigned *)nullptr, pp, st->d_cdf_half,
                        reinterpret_cast<PbEntry *>(w->d_pb_spill), (long long)w->pb_spill_stride, w->d_pb_ctl, listB, O);
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;

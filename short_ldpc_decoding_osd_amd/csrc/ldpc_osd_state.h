@@ -49,15 +49,19 @@ struct OsdState {
     std::mutex mu;                    // guards `ws`, `reserve_frames` and `pb_tuning`
     std::unordered_map<hipStream_t, StreamWs> ws;
     int64_t reserve_frames = 0;       // ldpc_osd_reserve: smallest capacity any workspace is created with
+    bool pb_profile = false;          // LDPC_PB_PROFILE was set when the context was created: the PB kernels' stamped builds
+    unsigned long long *d_pb_prof[3] = {nullptr, nullptr, nullptr};   // their counters: singles, chunk and workgroup kernel
 };
 
 static inline OsdState *state(ldpc_ctx *ctx) { return reinterpret_cast<OsdState *>(ctx->osd_state); }
 
 // ldpc_osd_pb.hip
 int pb_ctx_init(ldpc_ctx *ctx);
+// pb_mode: 0 = staged, 1 = every frame through the chunk kernel, 2 = through the list replay; front_inside: the front end runs
+// inside pb_singles_kernel (d_perm, d_parity NULL; pb_mode 0 or 1).  select_route makes these choices.
 int launch_pb(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
-              const unsigned char *d_perm, const u64 *d_parity, const ldpc_osd_params *p, uint64_t *d_cw, float *d_metric,
-              int32_t *d_best, int32_t *d_ntep, hipStream_t s);
+              const unsigned char *d_perm, const u64 *d_parity, const ldpc_osd_params *p, int pb_mode, bool front_inside,
+              uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_ntep, hipStream_t s);
 int pb_reserve(ldpc_ctx *ctx, hipStream_t s, int64_t frames, int order);
 // ldpc_osd.hip
 bool stream_capturing(hipStream_t s);

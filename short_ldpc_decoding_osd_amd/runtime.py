@@ -222,8 +222,11 @@ class Decoder:
         y_frames: debug bound for caller-made frame lists (0 = off): entries of ``index`` outside [0, y_frames) are
         replaced by 0 and counted (``osd_index_errors``);
         pb_front_inside: PB-OSD through ``osd_decode`` with the front end inside the first PB kernel (nothing goes through a
-        workspace: 43 % less HBM traffic for front end + head, 4-5 % more time; the same bit as table_scan)."""
-        flags = (1 if (table_scan or pb_front_inside) else 0) | {None: 0, "block": 2, "replay": 4}[pb_path] | (8 if readlane_scan else 0)
+        workspace: 43 % less HBM traffic for front end + head, 4-5 % more time).
+        The keywords only set ``flags``; the library validates the combination (LdpcError)."""
+        flags = ((_lib.OSD_F_TABLE_SCAN if table_scan else 0) | (_lib.OSD_F_READLANE_SCAN if readlane_scan else 0) |
+                 {None: 0, "block": _lib.OSD_F_PB_BLOCK, "replay": _lib.OSD_F_PB_REPLAY}[pb_path] |
+                 (_lib.OSD_F_PB_FRONT_INSIDE if pb_front_inside else 0))
         return _lib.OsdParams(int(order), int(algo), float(snr_db), float(fs_beta), float(fs_tau_e),
                               float(fs_tau_psc), int(fs_reference_quirk), flags,
                               aux.data_ptr() if aux is not None else None, int(y_frames))

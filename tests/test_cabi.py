@@ -10,7 +10,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_header_and_binding_agree():
+def test_header_and_binding_agree_at_abi5():
     from short_ldpc_decoding_osd_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "ldpc_osd.h")).read()
     declared = set(re.findall(r"\b(ldpc_[A-Za-z0-9_]+)\s*\(", hdr))
@@ -18,16 +18,25 @@ def test_header_and_binding_agree():
     L = _lib.load()
     for name in declared:
         assert getattr(L, name) is not None
-    assert L.ldpc_abi_version() == int(re.search(r"#define LDPC_OSD_ABI_VERSION (\d+)", hdr).group(1)) == 4
+    assert L.ldpc_abi_version() == int(re.search(r"#define LDPC_OSD_ABI_VERSION (\d+)", hdr).group(1)) == 5
     # struct layouts the binding mirrors (a silent drift here corrupts every OSD call)
     import ctypes as C
     assert C.sizeof(_lib.OsdParams) == 48 and _lib.OsdParams.d_aux.offset == 32 and _lib.OsdParams.y_frames.offset == 40
+    assert _lib.OsdParams.flags.offset == 28
+    flags = dict(re.findall(r"#define LDPC_OSD_F_(\w+)\s+\(1u << (\d+)\)", hdr))
+    assert len(flags) == 5 and {k: getattr(_lib, "OSD_F_" + k) for k in flags} == {k: 1 << int(v) for k, v in flags.items()}
     # ldpc_pb_tuning: thirteen int32 in the header's order (ABI 4)
     m = re.search(r"typedef struct ldpc_pb_tuning \{(.*?)\} ldpc_pb_tuning;", hdr, re.S)
     names = [n.strip() for decl in re.findall(r"int32_t ([^;]+);", m.group(1)) for n in decl.split(",")]
     assert names == [n for n, _ in _lib.PbTuning._fields_] and C.sizeof(_lib.PbTuning) == 4 * len(names) == 52
     assert _lib.PbTuning.t1.offset == 20 and _lib.PbTuning.handoff_maxlen.offset == 48
-    assert "getenv" not in re.sub(r'getenv\("LDPC_PB_PROFILE"\)', "", open(os.path.join(ROOT, "short_ldpc_decoding_osd_amd", "csrc", "ldpc_osd_pb.hip")).read())
+    # the one environment variable, LDPC_PB_PROFILE, is read at context creation and never on the decode path
+    csrc = os.path.join(ROOT, "short_ldpc_decoding_osd_amd", "csrc")
+    srcs = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".cpp", ".h"))}
+    assert sum(t.count("getenv") for t in srcs.values()) == 1 and 'getenv("LDPC_PB_PROFILE")' in srcs["ldpc_osd_pb.hip"]
+    pb = srcs["ldpc_osd_pb.hip"]
+    launch_pb = pb[pb.index("\nint launch_pb("):]
+    assert "getenv" not in launch_pb[:launch_pb.index("\n}\n")]
 
 
 @pytest.mark.parametrize("name,alist", [

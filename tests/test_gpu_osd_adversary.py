@@ -188,7 +188,8 @@ def test_fs_on_hard_inputs(dec, crafted, extremes, which):
     _fs_check(dec, y, cw, 2, 0.1, 14.5, 30.0)                  # loose tau_e: the tau_e stop and the quirk
 
 
-PB_ROUTES = [dict(), dict(pb_path="block"), dict(pb_path="replay"), dict(pb_front_inside=True)]
+PB_ROUTES = [dict(), dict(pb_path="block"), dict(pb_path="replay"), dict(pb_front_inside=True),
+             dict(pb_front_inside=True, pb_path="block")]
 
 
 def _pb_check(dec, y, cw, order, snr):

@@ -188,7 +188,7 @@ def test_pb_workgroup_kernel_ties(dec, quant):
 
 @pytest.mark.parametrize("snr,order,quant", [(2.5, 3, 0.0), (1.0, 3, 0.0), (2.0, 2, 0.0), (1.5, 3, 512.0)])
 def test_pb_front_end_inside_the_first_kernel(dec, snr, order, quant):
-    """With params.reserved bit 0, ldpc_osd_decode runs the OSD front end inside the PB singles kernel (round 4: no workspace
+    """With LDPC_OSD_F_PB_FRONT_INSIDE, ldpc_osd_decode runs the OSD front end inside the PB singles kernel (round 4: no workspace
     between them; a frame of the list replay is then set up from its singles record); by default the front end is a kernel of
     its own, and ldpc_osd_front + ldpc_osd_search is the third way to the same search: all three agree word for word, on an
     index list too.  (quant: quantised channel values -- massive ties, the list replay.)"""

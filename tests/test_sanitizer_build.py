@@ -8,7 +8,7 @@ import pytest
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++ with libasan")
-def test_host_code_under_asan_ubsan():
+def test_host_code_and_abi5_binding_under_asan_ubsan():
     from short_ldpc_decoding_osd_amd import build
     r = build.run_asan_tests()
     tail = (r.stdout[-2500:] + "\n" + r.stderr[-2500:])
