@@ -148,6 +148,34 @@ int ldpc_nms_decode(ldpc_ctx *ctx, const float *d_llr, int64_t B, int32_t T, con
 int ldpc_nms_traj_rows(ldpc_ctx *ctx, const float *d_llr, const int32_t *d_index, const int32_t *d_count, int64_t F,
                        int32_t T, const float *alpha, float w_in, float w_out, float *d_rows, int32_t kernel, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * NMS training step: loss and gradient of Decoding_model with respect to the EFFECTIVE factors, forward and backward
+ * in one launch.  Replaces the training graph of Ldpc_128_training/ms_decoder_dense.py -- Decoder_Layer.call and the
+ * unrolled loop :102-119, :232-241, compute_vc :121-134, compute_cv2 :177-208, marginalize :217-226,
+ * calculation_loss :210-215 -- and the tape.gradient of training_block.
+ *   L[f] = sum_{t=1..T} sum_v sigmoid_cross_entropy(logits = -soft_t[v], labels = bit[v])
+ * The forward pass is ldpc_nms_decode's generic kernel, same device code and float order: d_traj / d_hard / d_fail
+ * equal its outputs bit for bit, for either kernel of ldpc_nms_decode.  The gradient follows TensorFlow's rules for
+ * the reference's ops (stop_gradient signs, top_k ties to the lower variable index, clip pass-through on [0, 1e30]);
+ * they are not pinned against TensorFlow.  No gradient with respect to the channel values.
+ *   d_llr         [B][n] f32 channel values, as ldpc_nms_decode
+ *   d_label_bits  [B][ceil(n/64)] u64 packed code bits (the layout of ldpc_eval_counts)
+ *   alpha         host [T] effective check normalisers; w_in / w_out as ldpc_nms_decode
+ * Outputs, all nullable:
+ *   d_loss        [B] f32 per-frame loss
+ *   d_grad        [B][T+2] f32 per frame: dL/dalpha_0..T-1, dL/dw_in, dL/dw_out
+ *   d_loss_sum    [1] f64, d_grad_sum [T+2] f64: the sums over the batch, a tree whose shape depends on B alone (no
+ *                 atomics): repeated calls give the same bits on any stream
+ *   d_traj / d_hard / d_fail  as ldpc_nms_decode
+ * The backward pass keeps a tape of (n + (3 + 2 ceil(dc/32)) m) 4-B words per iteration next to the 4 (E + 2n) B of
+ * messages of each frame in LDS: T <= 64, check degree dc <= 64, and one frame must fit LDPC_NMS_TRAIN_LDS_BUDGET bytes,
+ * otherwise LDPC_E_UNSUPPORTED with the byte count (CCSDS (128,64): 3 KiB + 1.75 KiB per iteration, 115 KiB at T = 64).
+ * ------------------------------------------------------------------------------------- */
+#define LDPC_NMS_TRAIN_LDS_BUDGET (160u * 1024u)
+int ldpc_nms_train_grad(ldpc_ctx *ctx, const float *d_llr, const uint64_t *d_label_bits, int64_t B, int32_t T,
+                        const float *alpha, float w_in, float w_out, float *d_loss, float *d_grad, double *d_loss_sum,
+                        double *d_grad_sum, float *d_traj, uint64_t *d_hard, uint8_t *d_fail, void *stream);
+
 /* Error statistics, Decoding_model.get_eval, ms_test.py:36-54.
  * d_counts[5] += {frames, frames_in_error, bit_errors, undetected, syndrome_failures}.
  * The caller zeroes d_counts; d_fail may be NULL (then undetected/syndrome are not counted). */

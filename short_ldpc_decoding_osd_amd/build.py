@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libldpcosd.so")
-SOURCES = ["ldpc_host.cpp", "ldpc_api.hip", "ldpc_nms.hip", "ldpc_util.hip", "ldpc_osd.hip",
+SOURCES = ["ldpc_host.cpp", "ldpc_api.hip", "ldpc_nms.hip", "ldpc_nms_train.hip", "ldpc_util.hip", "ldpc_osd.hip",
            "ldpc_osd_pb.hip", "ldpc_hosd.hip", "ldpc_dia.hip"]
 # -ffp-contract=off: the float order of the NMS / OSD metric is part of the contract (no FMA fusion)
 # -fno-slp-vectorize: packed v_pk_add_f32 is no faster than two v_add_f32 on gfx950 and blocks the
@@ -46,7 +46,7 @@ def _stale(target, deps):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, h) for h in ("ldpc_internal.h", "ldpc_wave.h", "ldpc_search.h", "ldpc_front.h", "ldpc_osd_state.h")]
+    headers = [os.path.join(CSRC, h) for h in ("ldpc_internal.h", "ldpc_nms_generic.h", "ldpc_wave.h", "ldpc_search.h", "ldpc_front.h", "ldpc_osd_state.h")]
     headers.append(os.path.join(HERE, "..", "include", "ldpc_osd.h"))
     jobs = []
     for src in SOURCES:

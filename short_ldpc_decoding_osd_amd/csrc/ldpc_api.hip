@@ -114,6 +114,18 @@ int ldpc_nms_traj_rows(ldpc_ctx *ctx, const float *d_llr, const int32_t *d_index
     return launch_nms(ctx, d_llr, F, T, alpha, w_in, w_out, nullptr, nullptr, nullptr, nullptr, kernel, (hipStream_t)stream, d_index, d_count, d_rows);
 }
 
+int ldpc_nms_train_grad(ldpc_ctx *ctx, const float *d_llr, const uint64_t *d_label_bits, int64_t B, int32_t T, const float *alpha,
+                        float w_in, float w_out, float *d_loss, float *d_grad, double *d_loss_sum, double *d_grad_sum, float *d_traj,
+                        uint64_t *d_hard, uint8_t *d_fail, void *stream)
+{
+    if (!ctx || B < 0 || ((!d_llr || !d_label_bits) && B > 0)) return fail(LDPC_E_ARG, "ldpc_nms_train_grad: bad arguments");
+    if (T < 0 || T > kMaxIters) return fail(LDPC_E_ARG, "ldpc_nms_train_grad: T=%d outside 0..%d", T, kMaxIters);
+    if (T > 0 && !alpha) return fail(LDPC_E_ARG, "ldpc_nms_train_grad: alpha is NULL");
+    if (B == 0) return LDPC_OK;
+    return launch_nms_train(ctx, d_llr, d_label_bits, B, T, alpha, w_in, w_out, d_loss, d_grad, d_loss_sum, d_grad_sum, d_traj,
+                            d_hard, d_fail, (hipStream_t)stream);
+}
+
 int ldpc_pipeline_run(ldpc_ctx *ctx, const ldpc_pipeline *p, void *stream)
 {
     if (!ctx || !p) return fail(LDPC_E_ARG, "ldpc_pipeline_run: null argument");

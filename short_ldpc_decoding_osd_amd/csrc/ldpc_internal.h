@@ -80,6 +80,10 @@ int launch_nms(ldpc_ctx *ctx, const float *d_llr, int64_t B, int T, const float 
                float *d_soft, float *d_traj, uint64_t *d_hard, uint8_t *d_fail, int kernel, hipStream_t st,
                const int32_t *d_index = nullptr, const int32_t *d_count = nullptr, float *d_rows = nullptr);
 int probe_dpp(bool *ror_up, int *wave_rol_dir);
+// NMS training forward + backward and the batch sums (ldpc_nms_train.hip); arguments validated by the caller
+int launch_nms_train(ldpc_ctx *ctx, const float *d_llr, const uint64_t *d_label, int64_t B, int T, const float *alpha,
+                     float w_in, float w_out, float *d_loss, float *d_grad, double *d_loss_sum, double *d_grad_sum,
+                     float *d_traj, uint64_t *d_hard, uint8_t *d_fail, hipStream_t st);
 // OSD (ldpc_osd.hip).  check_params runs first on every OSD entry point: the order, the algorithm and the flags
 // (LDPC_OSD_F_*) against each other and against front_outside -- the caller supplies or wants the front-end results
 // (ldpc_osd_search; ldpc_pipeline_run with d_perm and d_parity) -- before anything is launched.

@@ -13,7 +13,8 @@
 //
 // Two kernels:
 //   nms_generic : any Tanner graph; one frame per wavefront, edge messages + variable totals
-//                 staged in LDS, lanes sweep variables, then checks.
+//                 staged in LDS, lanes sweep variables, then checks (device code in ldpc_nms_generic.h,
+//                 shared with the training kernel of ldpc_nms_train.hip).
 //   nms_qc16    : H made of 16x16 circulants in the CCSDS (128,64) arrangement.  A frame
 //                 occupies ONE 16-lane DPP row (4 frames per wavefront): lane j of the row is
 //                 check (br, j) for the 4 block rows and variable (bc, j) for the 8 block
@@ -21,27 +22,13 @@
 //                 add/sub that consumes it.  All 32 edge messages per lane live in VGPRs;
 //                 the iteration loop touches neither LDS nor memory.  No MFMA: there is no
 //                 contraction here, the kernel is VALU-issue bound.
-#include "ldpc_internal.h"
+#include "ldpc_nms_generic.h"
 
 namespace ldpc {
 
 // =======================================================================================
 // generic kernel
 // =======================================================================================
-// magnitude of `mag` with the sign bit of `s`: copysign lowers to one v_bfi_b32
-__device__ __forceinline__ unsigned sign_insert(unsigned mag, unsigned s)
-{
-    return __float_as_uint(__builtin_copysignf(__uint_as_float(mag), __uint_as_float(s)));
-}
-
-__device__ __forceinline__ void wave_lds_fence()
-{
-    // one wavefront = one frame: LDS operations of a wave execute in program order, so only
-    // the compiler has to be kept from reordering across the phase boundary.
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // (index / count / rows: the failed-frame form, ldpc_nms_traj_rows -- frame f of the launch is llr[index[f]], f < min(*count, B),
 //  and the only output is rows[f][0..T][n]: row 0 the channel values, row t the posterior after iteration t)
 __global__ __launch_bounds__(256) void nms_generic_kernel(
@@ -71,40 +58,13 @@ __global__ __launch_bounds__(256) void nms_generic_kernel(
         wave_lds_fence();
         for (int it = 0; it < T; ++it) {
             const float a_it = alpha.a[it];
-            for (int v = lane; v < n; v += 64) {
-                float acc = 0.0f;
-                for (int q = var_ptr[v]; q < var_ptr[v + 1]; ++q) acc = acc + cv[var_edge[q]];
-                tot[v] = acc + yb[v] * w_in;
-            }
+            nms_gen_totals(cv, tot, yb, w_in, var_ptr, var_edge, n, lane);
             wave_lds_fence();
-            for (int c = lane; c < m; c += 64) {
-                const int e0 = chk_ptr[c], e1 = chk_ptr[c + 1];
-                float m1 = __builtin_inff(), m2 = __builtin_inff();
-                unsigned sx = 0;
-                for (int e = e0; e < e1; ++e) {
-                    float vc = tot[chk_var[e]] - cv[e];
-                    cv[e] = vc;
-                    float a = __builtin_fabsf(vc);
-                    m2 = __builtin_fminf(m2, __builtin_fmaxf(m1, a));
-                    m1 = __builtin_fminf(m1, a);
-                    sx ^= __float_as_uint(vc);
-                }
-                // clamping the order statistics == clamping every |vc| (monotone); a zero
-                // minimum means sign(0) = 0 wipes the whole check row (ms_test.py:187-191)
-                const float m1s = a_it * __builtin_fminf(m1, 1e30f);
-                const float m2s = (m1 == 0.0f) ? 0.0f : a_it * __builtin_fminf(m2, 1e30f);
-                for (int e = e0; e < e1; ++e) {
-                    float vc = cv[e];
-                    float mag = (__builtin_fabsf(vc) > m1) ? m1s : m2s;
-                    cv[e] = __uint_as_float(sign_insert(__float_as_uint(mag), sx ^ __float_as_uint(vc)));
-                }
-            }
+            nms_gen_checks<false>(cv, tot, a_it, chk_ptr, chk_var, m, lane);
             wave_lds_fence();
             if (traj || rows || it == T - 1) {
                 for (int v = lane; v < n; v += 64) {
-                    float acc = 0.0f;
-                    for (int q = var_ptr[v]; q < var_ptr[v + 1]; ++q) acc = acc + cv[var_edge[q]];
-                    float o = acc + w_out * yb[v];
+                    float o = nms_gen_marginal(cv, yb, w_out, var_ptr, var_edge, v);
                     if (traj) traj[((long long)it * B + f) * n + v] = o;
                     if (rows) rows[(f * (T + 1) + it + 1) * n + v] = o;
                     if (it == T - 1) tot[v] = o;

@@ -38,3 +38,44 @@ def make_tfrecord(data, out_filename):
     """One Example per row (data_generating.py:16-26)."""
     feats, labels = data
     write_examples(out_filename, feats, labels)
+
+
+def _f_w(x, mid_sigma):
+    return np.exp(-abs(x - mid_sigma))
+
+
+def training_data_generating(code, SNRs, max_frame, rng=None):
+    """Training frames (Training_data_gen_128/data_generating.py:41-81): for snr_lo != snr_hi the noise is scaled by the
+    sigma and shifted by the mean of the exp(-|sigma - mid|)-weighted sigma density over [sigma1, sigma2] (scipy quad);
+    for snr_lo == snr_hi sigma = sigma1 and mean 1.  Pass ``rng`` (np.random.Generator) for reproducible sets (the
+    reference seeds the global NumPy RNG with 0)."""
+    from scipy import integrate
+
+    n, k = code.check_matrix_column, code.k
+    randn = rng.standard_normal if rng is not None else (lambda size: np.random.randn(*size))
+    integers = (lambda lo, hi, size: rng.integers(lo, hi, size=size)) if rng is not None else \
+        (lambda lo, hi, size: np.random.randint(lo, hi, size=size, dtype=int))
+    training_data_labels = np.zeros((max_frame, n), dtype=np.int64)
+    noise = randn((max_frame, n))
+    SNR1, SNR2 = SNRs[0], SNRs[1]
+    sig = lambda snr: np.sqrt(1. / (2 * (float(k) / float(n)) * 10 ** (snr / 10)))   # noqa: E731
+    sigma1, sigma2, mid_sigma = sig(SNR1), sig(SNR2), sig((SNR1 + SNR2) / 2)
+    if SNR1 != SNR2:
+        tmp, _ = integrate.quad(_f_w, sigma1, sigma2, args=(mid_sigma,))
+        weight_coefficient = 1 / tmp
+        tmp_mean, _ = integrate.quad(lambda x, s: 2 / (x ** 2) * _f_w(x, s), sigma1, sigma2, args=(mid_sigma,))
+        new_mean = weight_coefficient * tmp_mean
+        tmp_variance, _ = integrate.quad(lambda x, s: 4 * (1 / (x ** 2) + 1 / (x ** 4)) * _f_w(x, s), sigma1, sigma2, args=(mid_sigma,))
+        new_variance = weight_coefficient * tmp_variance - new_mean ** 2
+        sigma = np.sqrt(new_variance)
+    else:
+        sigma, new_mean = sigma1, 1
+    noise *= sigma
+    noise += new_mean
+    if GL.get_map('ALL_ZEROS_CODEWORD_TRAINING', False):
+        training_data = noise
+    else:
+        codewords = integers(0, 2, [max_frame, k]).dot(code.G) % 2
+        training_data = np.where(codewords == 0, noise, -noise)
+        training_data_labels = codewords.astype(np.int64)
+    return training_data, training_data_labels

@@ -107,3 +107,62 @@ def set_predict_model(DIA):   # noqa: N803
 def pattern_log_dir():
     """Directory of ``dist-error-pattern-<nn>.pkl`` (nn_testing.py:96-99: the 2.7-2.7 dB statistics)."""
     return _training_root() + 'log/' + get_map('selected_decoder_type') + '/2.7-2.7dB/'
+
+
+def training_setting_global(argv):
+    """Settings of the NMS training stage: ``prog snr_lo snr_hi unit_batch num_batch_train T Hfile type``
+    (Ldpc_128_training/globalmap.py:28-56) with the reference's defaults."""
+    from .fill_matrix_info import Code
+
+    set_map('snr_lo', float(argv[1]))
+    set_map('snr_hi', float(argv[2]))
+    set_map('unit_batch_size', int(argv[3]))
+    set_map('num_batch_train', int(argv[4]))
+    set_map('num_iterations', int(argv[5]))
+    set_map('H_filename', argv[6])
+    set_map('selected_decoder_type', argv[7])
+    set_map('loss_process_indicator', True)
+    set_map('ALL_ZEROS_CODEWORD_TRAINING', False)
+    set_map('epochs', 100)
+    set_map('initial_learning_rate', 0.01)
+    set_map('decay_rate', 0.95)
+    set_map('decay_step', 500)
+    set_map('termination_step', 1200)
+    set_map('code_parameters', Code(get_map('H_filename')))
+    set_map('print_interval', 50)
+    set_map('record_interval', 50)
+
+
+def training_logistic_setting(root='.'):
+    """[ckpts_dir, ckpt_nm, ckpts_dir_par, restore_step] of the training stage (Ldpc_128_training/globalmap.py:58-68)."""
+    import os
+    T, decoder_type = get_map('num_iterations'), get_map('selected_decoder_type')
+    ckpts_dir = os.path.join(root, 'ckpts', decoder_type, f'{T}th') + os.sep
+    ckpts_dir_par = os.path.join(ckpts_dir, 'par') + os.sep
+    os.makedirs(ckpts_dir_par, exist_ok=True)
+    return [ckpts_dir, 'ldpc-ckpt', ckpts_dir_par, 'latest']
+
+
+def training_setting():
+    """[start_step, multiplier, train_steps] (Ldpc_128_training/globalmap.py:70-77)."""
+    return [0, 1, get_map('num_batch_train') * get_map('epochs')]
+
+
+def training_data_setting(code, unit_batch_size, data_root):
+    """(retrain directory, training dataset) (Ldpc_128_training/globalmap.py:79-99); ``data_root`` stands for the
+    reference's '../Training_data_gen_<n>/data'."""
+    import os
+
+    from .read_TFdata import data_handler
+    n, T, decoder_type = code.check_matrix_column, get_map('num_iterations'), get_map('selected_decoder_type')
+    data_dir = os.path.join(data_root, f"snr{round(get_map('snr_lo'), 2)}-{round(get_map('snr_hi'), 2)}dB")
+    name = 'ldpc-train-allzero.tfrecord' if get_map('ALL_ZEROS_CODEWORD_TRAINING') else 'ldpc-train-nonzero.tfrecord'
+    gen_data_dir = os.path.join(data_dir, f'{T}th', decoder_type) + os.sep
+    os.makedirs(gen_data_dir, exist_ok=True)
+    return gen_data_dir, data_handler(n, os.path.join(data_dir, name), unit_batch_size)
+
+
+def optimizer_setting():
+    """ExponentialDecay(initial_learning_rate, decay_step, decay_rate, staircase=True) (Ldpc_128_training/globalmap.py:101-107)."""
+    from .nms_train import ExponentialDecay
+    return ExponentialDecay(get_map('initial_learning_rate'), get_map('decay_step'), get_map('decay_rate'), staircase=True)

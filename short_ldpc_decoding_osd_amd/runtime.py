@@ -99,6 +99,35 @@ class Decoder:
                                              int(kernel), self._stream()), "ldpc_nms_traj_rows")
         return rows
 
+    def nms_grad(self, llr, label_bits, T, alpha, w_in=1.0, w_out=1.0, want_loss=True, want_grad=True, want_sums=True,
+                 want_traj=False, want_hard=False, want_fail=False, out=None):
+        """Training step of NMS (ldpc_nms_train_grad): loss of Decoding_model (ms_decoder_dense.py:210-215) and its
+        gradient with respect to the effective factors, forward and backward in one launch.  ``label_bits``: packed code
+        bits [B, words] int64 (``pack_bits``).  Returns dict(loss [B] f32, grad [B, T+2] f32 = dL/dalpha_0..T-1,
+        dL/dw_in, dL/dw_out, loss_sum [1] f64, grad_sum [T+2] f64, traj [T, B, n], hard, fail) -- None where not asked
+        for; ``traj`` / ``hard`` / ``fail`` are ``nms``'s, bit for bit."""
+        self._chk(llr, torch.float32, (self.n,), "llr")
+        self._chk(label_bits, torch.int64, (self.words,), "label_bits")
+        B = llr.shape[0]
+        if label_bits.shape[0] != B:
+            raise ValueError(f"label_bits: {label_bits.shape[0]} frames for {B} channel frames")
+        a = np.asarray(alpha, dtype=np.float32)
+        a = np.ascontiguousarray(np.broadcast_to(a, (max(T, 1),)) if T > 0 else np.zeros(1, np.float32))
+        out = dict(out or {})
+        shapes = {"loss": ((B,), torch.float32, want_loss), "grad": ((B, T + 2), torch.float32, want_grad),
+                  "loss_sum": ((1,), torch.float64, want_sums), "grad_sum": ((T + 2,), torch.float64, want_sums),
+                  "traj": ((T, B, self.n), torch.float32, want_traj), "hard": ((B, self.words), torch.int64, want_hard),
+                  "fail": ((B,), torch.uint8, want_fail)}
+        for k, (shape, dtype, want) in shapes.items():
+            if want and out.get(k) is None:
+                out[k] = self.empty(shape, dtype)
+            out.setdefault(k, None)
+        _lib.check(self.L.ldpc_nms_train_grad(self._ctx, _ptr(llr), _ptr(label_bits), B, T, a.ctypes.data_as(C.POINTER(C.c_float)),
+                                              float(w_in), float(w_out), _ptr(out["loss"]), _ptr(out["grad"]),
+                                              _ptr(out["loss_sum"]), _ptr(out["grad_sum"]), _ptr(out["traj"]),
+                                              _ptr(out["hard"]), _ptr(out["fail"]), self._stream()), "ldpc_nms_train_grad")
+        return out
+
     # ------------------------------------------------------------------ statistics / plumbing kernels
     def eval_counts(self, hard, label_bits, fail=None, counts=None):
         """counts[5] += {frames, frame_err, bit_err, undetected, synd_fail} (int64 tensor)."""
