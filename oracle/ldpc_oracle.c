@@ -192,6 +192,9 @@ void orc_nms(const int32_t *H, int m, int n, const float *y, int64_t B, int T, c
                     neg ^= (vc < 0.0f);
                     zero |= (vc == 0.0f);
                 }
+                /* a check with one edge: the reference pads non-edges with -1e30 - 1 before top_k (ms_test.py:193-203), */
+                /* so its second value is 1e30, not inf                                                                 */
+                m2 = fminf(m2, 1e30f);
                 for (int e = e0; e < e1; ++e) {
                     float vc = cv[e];
                     float a = fminf(fabsf(vc), 1e30f);

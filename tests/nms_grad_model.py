@@ -108,7 +108,8 @@ def grad_model(H, y, bits, T, alpha, w_in=1.0, w_out=1.0, check_dense=True):
         x = -outs[t].astype(np.float64)
         loss += (np.maximum(x, 0) - x * bits + np.log1p(np.exp(-np.abs(x)))).sum(axis=1)
         s = outs[t].astype(np.float64)       # z - sigmoid(-s) without cancellation: sigmoid(s) for z = 1, -sigmoid(-s) for z = 0
-        gsoft.append(np.where(bits == 1, 1.0 / (1.0 + np.exp(-s)), -1.0 / (1.0 + np.exp(s))))
+        with np.errstate(over="ignore"):     # exp(1e30-scale) = inf gives the limit, 0 or 1
+            gsoft.append(np.where(bits == 1, 1.0 / (1.0 + np.exp(-s)), -1.0 / (1.0 + np.exp(s))))
     grad = np.zeros((B, T + 2))
     mass = np.zeros((B, T + 2))
     shape = (B, g.m, g.chk_var.shape[1])
@@ -172,7 +173,7 @@ def loss64(H, y, bits, T, alpha, w_in=1.0, w_out=1.0):
         vc = np.where(g.valid[None], g.gather(tot) - cv, 0)
         a = np.where(g.valid[None], np.minimum(np.abs(vc), 1e30), np.inf)
         srt = np.sort(a, axis=2)
-        m1, m2 = srt[:, :, 0:1], srt[:, :, 1:2]
+        m1, m2 = srt[:, :, 0:1], np.minimum(srt[:, :, 1:2], 1e30)     # (a check with one edge: the reference's padding, 1e30)
         S = np.prod(np.where(g.valid[None], np.sign(vc), 1), axis=2, keepdims=True)
         mag = np.where(a > m1, m1, m2)
         cv = np.where(g.valid[None], alpha[t] * mag * S * np.sign(vc), 0)

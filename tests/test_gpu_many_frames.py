@@ -4,16 +4,21 @@ the previous one left, and the register-resident order-2 kernels prefetch a late
 here asserts that its frame count gives at least three trips of the kernel it targets (TRIPS below), then compares the
 outputs with the oracle (every frame, or a sample stratified over the trips) and with the same frames decoded in calls of
 at most one trip each (no workgroup gets a second frame)."""
+import math
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import c_oracle, np_oracle
 from tests import dlosd_model as DM
+from tests import nms_graphs as Z
 from tests import osd_adversary as adv
 from tests.gpu_util import pack_np, to_dev, words_np
+from tests.nms_grad_model import grad_model
 from tests.test_gpu_dlosd import _blocks, _check_sliding
 from tests.test_gpu_hosd import PATH
+from tests.test_gpu_nms_train import rel_bound
 from tests.test_gpu_osd import _rows_packed
 
 pytestmark = pytest.mark.gpu
@@ -35,6 +40,7 @@ TRIPS = {
     "hosd_search": lambda cu: 8192,           # ldpc_hosd.hip:463 grid_for(F, 1), one frame per workgroup
     "hosd_sliding": lambda cu: 8192,          # ldpc_hosd.hip:463 grid_for(F, 1)
     "nms_generic": lambda cu: 8192 * 4,       # ldpc_nms.hip:443, 4 waves per workgroup
+    "nms_train": lambda cu: 32768 // 2 * 2,   # ldpc_nms_train.hip:288, 32768 / waves workgroups of waves frames; waves = 2 below
 }
 COMPACT_FPT8_ABOVE = 256 * 1024 * 2           # ldpc_util.hip:218: compact_kernel<EVAL, 8> above this many flags
 
@@ -498,3 +504,48 @@ def test_nms_generic_beyond_two_trips(dec):
     soft_o, traj_o = c_oracle.nms(dec.code.H, y[sd].cpu().numpy(), T, ALPHA0, want_traj=True)
     assert np.array_equal(gen["soft"][sd].cpu().numpy().view(np.uint32), soft_o.view(np.uint32))
     assert np.array_equal(gen["traj"][:, sd].cpu().numpy().view(np.uint32), np.asarray(traj_o[1:]).view(np.uint32))
+
+
+def test_nms_train_beyond_three_trips(dec):
+    """nms_train_kernel at CCSDS T = 12 (two frames per workgroup, 16 384 workgroups): from the second trip on a wavefront
+    builds its tape over the previous frame's.  Per-frame loss / gradient / hard / fail against one-trip slices (bits), a
+    stratified sample against the float64 model and the C oracle, the batch sums against math.fsum, and the call without
+    the gradient (a frame ends after its forward pass) against the full one."""
+    B, T = 100000, 12
+    alpha = np.array([0.669435 * (1 + 0.03 * (t % 5)) for t in range(T)], np.float32)
+    w_in, w_out = 0.9, 1.1
+    H = dec.code.H
+    assert Z.train_waves(H, T) == 2
+    grid = per_trip(dec, "nms_train")
+    assert_trips(dec, "nms_train", B, 3)
+    y, cw = device_frames(dec, B, 2.0, 91)
+    lab = dec.pack_bits(cw.to(torch.int64))
+    keys = ("loss", "grad", "hard", "fail")
+    whole = dec.nms_grad(y, lab, T, alpha, w_in, w_out, want_hard=True, want_fail=True)
+    parts = sliced(lambda lo, hi: {k: v for k, v in dec.nms_grad(y[lo:hi], lab[lo:hi], T, alpha, w_in, w_out, want_sums=False,
+                                                              want_hard=True, want_fail=True).items() if k in keys}, B, grid)
+    fwd = dec.nms_grad(y, lab, T, alpha, w_in, w_out, want_grad=False, want_sums=False, want_hard=True, want_fail=True)
+    torch.cuda.synchronize()
+    for k in keys:
+        assert torch.equal(whole[k].view(torch.uint8), parts[k].view(torch.uint8)), k
+        if k != "grad":
+            assert torch.equal(whole[k].view(torch.uint8), fwd[k].view(torch.uint8)), k
+    sel = stratified(B, grid, np.random.default_rng(92), extra=100, tail=32)
+    sd = torch.from_numpy(sel).to(dec.device)
+    yh, cwh = y[sd].cpu().numpy(), cw[sd].to(torch.uint8).cpu().numpy()
+    model = grad_model(H, yh, cwh, T, alpha, w_in, w_out)
+    bound = rel_bound(T)
+    loss = whole["loss"][sd].cpu().numpy().astype(np.float64)
+    grad = whole["grad"][sd].cpu().numpy().astype(np.float64)
+    assert np.all(np.abs(loss - model["loss"]) <= bound * model["loss"] + 1e-30)
+    assert np.all(np.abs(grad - model["grad"]) <= bound * model["mass"] + 1e-30)
+    soft_o = c_oracle.nms(H, yh, T, alpha, w_in, w_out)
+    hard_o, fail_o, _ = c_oracle.evaluate(H, soft_o, None)
+    assert np.array_equal(words_np(whole["hard"][sd]), pack_np(hard_o))
+    assert np.array_equal(whole["fail"][sd].cpu().numpy(), fail_o)
+    ls, gs = whole["loss_sum"].cpu().numpy(), whole["grad_sum"].cpu().numpy()
+    lossh, gradh = whole["loss"].cpu().numpy().astype(np.float64), whole["grad"].cpu().numpy().astype(np.float64)
+    assert abs(ls[0] - math.fsum(lossh)) <= 1e-12 * abs(ls[0])
+    for k in range(T + 2):
+        want = math.fsum(gradh[:, k])
+        assert abs(gs[k] - want) <= 1e-12 * max(abs(want), math.fsum(np.abs(gradh[:, k])))
