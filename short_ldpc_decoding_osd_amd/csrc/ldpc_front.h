@@ -1,6 +1,6 @@
 // OSD front end of one frame on one wavefront: reliability sort, column gather, GF(2) elimination, MRB bookkeeping
 // (swapped_info / identify_mrb, PB_OSD/pb_testing.py:268-320).  Shared by osd_front_kernel, the fused order-2 kernel
-// (ldpc_osd.hip) and the fused PB-OSD head (ldpc_osd_pb.hip).
+// (ldpc_osd.hip) and the fused PB-OSD head (pb_singles_kernel, ldpc_pb_singles.h).
 #pragma once
 #include "ldpc_internal.h"
 #include "ldpc_wave.h"

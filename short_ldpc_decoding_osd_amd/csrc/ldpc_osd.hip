@@ -27,7 +27,7 @@
 //                       the oracle uses, see oracle/np_oracle.py weighted_distance), first minimum.
 //   osd_fs_kernel       FS-OSD (FS_OSD/fs_testing.py:22-64,129-161), 64 TEPs per round.
 //   osd_ge_kernel       full_gf2elim on caller-supplied matrices; osd_counts_kernel: success counters.
-//   (PB-OSD: ldpc_osd_pb.hip; shared per-frame set-up: ldpc_search.h; host state: ldpc_osd_state.h)
+//   (PB-OSD: ldpc_osd_pb.hip, the host side, and ldpc_pb_*.h, its kernels; shared per-frame set-up: ldpc_search.h; host state: ldpc_osd_state.h)
 #include <math.h>
 #include <stdlib.h>
 
@@ -799,7 +799,6 @@ void osd_ctx_release(ldpc_ctx *ctx)
         (void)hipFree(st->d_base2);
         (void)hipFree(st->d_cdf_half);
         (void)hipFree(st->d_index_errors);
-        for (unsigned long long *d : st->d_pb_prof) (void)hipFree(d);
         delete st;
     }
     ctx->osd_state = nullptr;

@@ -1,4 +1,4 @@
-// Host-side OSD state of a context: TEP tables and the per-stream workspaces (ldpc_osd.hip, ldpc_osd_pb.hip).
+// Host-side OSD state of a context: TEP tables and the per-stream workspaces (ldpc_osd.hip, ldpc_osd_pb.hip; the PB kernels, ldpc_pb_*.h, read the control-word layout).
 #pragma once
 
 #include "ldpc_wave.h"
@@ -49,8 +49,6 @@ struct OsdState {
     std::mutex mu;                    // guards `ws`, `reserve_frames` and `pb_tuning`
     std::unordered_map<hipStream_t, StreamWs> ws;
     int64_t reserve_frames = 0;       // ldpc_osd_reserve: smallest capacity any workspace is created with
-    bool pb_profile = false;          // LDPC_PB_PROFILE was set when the context was created: the PB kernels' stamped builds
-    unsigned long long *d_pb_prof[3] = {nullptr, nullptr, nullptr};   // their counters: singles, chunk and workgroup kernel
 };
 
 static inline OsdState *state(ldpc_ctx *ctx) { return reinterpret_cast<OsdState *>(ctx->osd_state); }

@@ -1,4 +1,4 @@
-"""NumPy model of the batch-parallel PB-OSD engine of csrc/ldpc_osd_pb.hip -- TEST INFRASTRUCTURE.
+"""NumPy model of the batch-parallel PB-OSD engine of csrc/ldpc_pb_*.h (translation unit: ldpc_osd_pb.hip) -- TEST INFRASTRUCTURE.
 
 The reference's PB-OSD (PB_OSD/pb_testing.py:100-149, optimal_tep_sequence :366-397) pops test error
 patterns from a growing frontier list, "first minimum of the reliability sums in list order".  The kernel does

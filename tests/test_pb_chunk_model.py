@@ -1,4 +1,4 @@
-"""The sorted-chunk formulation of PB-OSD (tests/pb_chunk_model.py = the algorithm of csrc/ldpc_osd_pb.hip in NumPy)
+"""The sorted-chunk formulation of PB-OSD (tests/pb_chunk_model.py = the algorithm of csrc/ldpc_pb_*.h in NumPy)
 against the literal frontier-list restatement of the C oracle (pb_testing.py:100-149, :366-397): TEP counts, stop
 reasons, frontier comparisons, both success counters, winner index and metric must agree on every frame the
 chunk model accepts; frames it declines (massive ties) are the ones the kernel hands to the list replay."""
@@ -52,7 +52,7 @@ def test_visit_order_comparator_on_ties():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The direct enumeration of a sum range (csrc/ldpc_osd_pb.hip, PbItems): item layout, table-id formulas, the binary
+# The direct enumeration of a sum range (csrc/ldpc_pb_wave.h, PbwItem): item layout, table-id formulas, the binary
 # search and the empty-item shortcut, restated in NumPy float32 and checked against a brute-force filter of the kernel's
 # TEP table.
 # ---------------------------------------------------------------------------------------------------------------------
@@ -127,7 +127,7 @@ def test_sum_range_enumeration(order):
 
 
 def _items():
-    """The 2017 items of csrc/ldpc_osd_pb.hip (pbw_item): item (row q, lane l) -> fixed positions and the base of its members
+    """The 2017 items of csrc/ldpc_pb_wave.h (pbw_item_rt): item (row q, lane l) -> fixed positions and the base of its members
     (members are the last positions m in (base, 63])."""
     out = {}
     for q in range(32):
@@ -156,7 +156,7 @@ def test_items_partition_the_tep_table():
 
 
 def test_workgroup_kernel_dealing_is_a_bijection():
-    """coop_item (csrc/ldpc_osd_pb.hip): item j of lane `lane` in wavefront v is row q = 16 j + lane / 4, lane
+    """coop_item (csrc/ldpc_pb_coop.h): item j of lane `lane` in wavefront v is row q = 16 j + lane / 4, lane
     l = (13 (v - 3 q) mod 16) + 16 (lane mod 4), i.e. the items with (5 l + 3 q) mod 16 = v: every (q, l) exactly once."""
     seen = set()
     for v in range(16):
@@ -204,7 +204,7 @@ def test_workgroup_kernel_dealing_balances_a_chunk(np_code):
 
 
 def test_bisection_count_equals_enumeration():
-    """coop_count (csrc/ldpc_osd_pb.hip): inside an item the float32 sums sb + w[m] fall as m rises (w is sorted descending,
+    """coop_count (csrc/ldpc_pb_coop.h): inside an item the float32 sums sb + w[m] fall as m rises (w is sorted descending,
     float addition is monotone), so the members <= T beyond the cursor a are the positions [first, a) and seven bisection
     steps find `first` for any base in [-1, 63] and cursor in [base + 1, 64] -- also with equal reliabilities."""
     rng = np.random.default_rng(11)
