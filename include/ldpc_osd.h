@@ -131,6 +131,8 @@ int ldpc_ctx_nms_kernel(const ldpc_ctx *ctx);
  *             soft_output_list without its slot 0, which is d_llr itself)
  *   d_hard    [B][ceil(n/64)] u64 packed hard decisions (soft > 0 ? 0 : 1) (nullable)
  *   d_fail    [B] u8, 1 = non-zero syndrome (nullable)
+ * Each of the four outputs is switched off on its own; the others do not change.  With all four NULL the call still
+ * succeeds (LDPC_OK): the kernel runs and writes nothing.  d_llr (B > 0) and alpha (T > 0) are required.
  * ------------------------------------------------------------------------------------- */
 int ldpc_nms_decode(ldpc_ctx *ctx, const float *d_llr, int64_t B, int32_t T, const float *alpha, float w_in,
                     float w_out, float *d_soft, float *d_traj, uint64_t *d_hard, uint8_t *d_fail, int32_t kernel,
@@ -140,7 +142,8 @@ int ldpc_nms_decode(ldpc_ctx *ctx, const float *d_llr, int64_t B, int32_t T, con
  * ms_test.py:55-64 (driven by Decoding_model.call :30-34 with the index of get_eval :51) -- T + 1 rows per failed
  * frame, row 0 the channel values (soft_output_list[0]), row t the posterior after iteration t.
  *   d_index / d_count  the frame list as ldpc_compact writes it; the number of frames is min(*d_count, F), read ON THE
- *                      DEVICE; F is the capacity of d_rows
+ *                      DEVICE; F is the capacity of d_rows.  All of d_llr, d_index, d_count and d_rows are required
+ *                      (F > 0); *d_count must be >= 0, as everywhere a count is read on the device (see the OSD section)
  *   d_rows             [F][T+1][n] f32
  * The frames are decoded again (same kernel, same arithmetic: every row equals the corresponding row of
  * ldpc_nms_decode's d_traj); nothing else is written.  At 2.5 dB a quarter of the frames fail: 1.4 KiB of rows per
@@ -198,7 +201,11 @@ int ldpc_unpack_bits(ldpc_ctx *ctx, const uint64_t *d_words, int64_t B, void *d_
 /* ---------------------------------------------------------------------------------------
  * OSD (n = 128, k = 64 codes).  Frames are addressed as d_y[ d_index ? d_index[f] : f ].
  * If d_count is non-NULL the number of frames is min(*d_count, F) read ON THE DEVICE (so a
- * compaction can feed the OSD without a host round trip); F is then the capacity.
+ * compaction can feed the OSD without a host round trip); F is then the capacity: a count above F is truncated to F,
+ * and nothing at or beyond frame min(*d_count, F) of any output is written.  *d_count must be >= 0 (ldpc_compact writes
+ * nothing else); the kernels do not check for a negative count.
+ * A NULL in a pointer that is not marked nullable is LDPC_E_ARG (the message names the entry point) before anything is
+ * launched.
  * The entries of d_index are frame numbers of d_y and are NOT range-checked by default (the entry points do
  * not know how many frames d_y holds): a caller-made list must stay inside d_y; ldpc_compact /
  * ldpc_pipeline_run write only valid, ascending frame numbers.  Debug aid: ldpc_osd_params.y_frames.
@@ -208,7 +215,8 @@ int ldpc_unpack_bits(ldpc_ctx *ctx, const uint64_t *d_words, int64_t B, void *d_
  * d_rows_in/out: [F][64][2] u64 (row r of frame f, columns 0..127); d_swaps: [F][64][2] u8
  * recorded (j, col) pairs; d_nswaps: [F] i32, the number of exchanges, or -1 for a rank-deficient
  * matrix (its reduced rows and exchange records are then unspecified: the kernel does not drop
- * all-zero rows as the host GE does).                                                         */
+ * all-zero rows as the host GE does).  d_rows_in and d_rows_out are required; d_swaps and
+ * d_nswaps are nullable (each on its own).                                                    */
 int ldpc_osd_ge(ldpc_ctx *ctx, const uint64_t *d_rows_in, int64_t F, uint64_t *d_rows_out, uint8_t *d_swaps,
                 int32_t *d_nswaps, void *stream);
 
@@ -305,7 +313,8 @@ int ldpc_osd_release_stream(ldpc_ctx *ctx, void *stream);
  *                         (conventional), or its rank in visit order (FS/PB; 0 = all-zero TEP)
  *   d_ntep    [F] i32     number of TEPs evaluated (FS: num_teps, fs_testing.py:141; PB: cost_tep_num
  *                         or N_max when no rule fired, pb_testing.py:152-155)
- * Any of d_metric/d_best/d_ntep may be NULL.
+ * Any of d_metric/d_best/d_ntep may be NULL, and so may params->d_aux, each on its own: the other outputs do not change.
+ * d_y, params and d_cw are required; d_index / d_count are optional as described above.
  * Concurrency: calls on different streams may overlap, whatever the algorithm (scratch is per stream,
  * see ldpc_ctx_create).                                                                       */
 int ldpc_osd_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
@@ -318,7 +327,8 @@ int ldpc_osd_index_errors(ldpc_ctx *ctx, int64_t *count);
 
 /* The search alone, on front-end results supplied by the caller (ldpc_osd_front, or any
  * (perm, P') pair: with perm = identity and d_y already in the primed order this is exactly
- * convention_osd_main / the fs_osd / pb_osd inner loops applied to (updated_inputs, reduced_G)). */
+ * convention_osd_main / the fs_osd / pb_osd inner loops applied to (updated_inputs, reduced_G)).
+ * Nullable as for ldpc_osd_decode; d_perm and d_parity are required.                               */
 int ldpc_osd_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
                     const uint8_t *d_perm /*[F][128]*/, const uint64_t *d_parity /*[F][64]*/,
                     const ldpc_osd_params *params, uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_ntep,
@@ -336,7 +346,8 @@ int ldpc_osd_tep_eval(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, c
 /* OSD statistics against labels: d_counts[3] += {frames, frames_wrong, teps_total}.
  * (the success test of convention_osd.py:65-66 / pb_testing.py:158 / fs_testing.py:162)
  * teps_total sums d_ntep and stays unchanged when d_ntep is NULL -- on every route, also where the search kernel counts
- * (ldpc_pipeline_run's d_osd_counts).                                                      */
+ * (ldpc_pipeline_run's d_osd_counts).  d_cw, d_label_bits and d_counts are required; d_index NULL = labels are
+ * addressed directly (label f for codeword f); d_count NULL = exactly F frames.            */
 int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label_bits, const int32_t *d_index,
                     const int32_t *d_count, const int32_t *d_ntep, int64_t F, int64_t *d_counts, void *stream);
 
@@ -371,11 +382,14 @@ int ldpc_hosd_front(ldpc_ctx *ctx, const float *d_order_llr, int64_t F, uint8_t 
  * to the hard decisions of d_metric_llr, weights |d_metric_llr|                              (:159-160,180-182).
  * Float order of the metric: positions in updated order, bytes of 8, each byte summed ascending
  * from 0, the 16 byte sums added ascending (oracle/np_oracle.py hosd_cost).
- *   d_block_min [F][nblk] f32, d_block_arg [F][nblk] i32 (nullable; index into d_teps of the first minimum)
+ *   d_block_min [F][nblk] f32 (required when nblk > 0: it is the call's primary output and is stored unguarded),
+ *   d_block_arg [F][nblk] i32 (nullable; index into d_teps of the first minimum)
  *   d_truth  [F] f32 (nullable, needs d_label_bits [F][2] u64): the metric of the label      (:181-183)
  *   d_cw     [F][2] u64 (nullable): best candidate over all blocks, ORIGINAL bit order
  *   d_metric [F] f32, d_best [F] i32 (nullable): its metric and index into d_teps (first minimum)
- * d_teps: DEVICE [ntep][4] u8 as ldpc_hosd_pattern_teps writes them; d_block_off: DEVICE [nblk+1] i32. */
+ * d_cw, d_metric and d_best are nullable each on its own.
+ * d_teps: DEVICE [ntep][4] u8 as ldpc_hosd_pattern_teps writes them (required when nblk > 0); d_block_off: DEVICE [nblk+1] i32
+ * (required).                                                                                                         */
 int ldpc_hosd_search(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F,
                      const uint8_t *d_lri, const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps,
                      const int32_t *d_block_off, int32_t nblk, const uint64_t *d_label_bits, float *d_block_min,
@@ -434,7 +448,10 @@ int ldpc_dia_cnn(ldpc_ctx *ctx, const float *d_rows, int64_t F, int32_t L, const
  *   -> OSD counters.
  * The results of the sequence ldpc_nms_decode, ldpc_eval_counts, ldpc_compact, ldpc_osd_front,
  * ldpc_osd_search, ldpc_osd_counts on one stream (the counters ride in the compaction's counting pass), without a host round trip in between (the OSD
- * kernels read the failure count on the device).  Nullable members switch their stage off.
+ * kernels read the failure count on the device).  Nullable members switch their stage off: without d_label_bits or
+ * d_nms_counts no NMS counters, without d_label_bits or d_osd_counts no OSD counters (teps_total moves only with d_ntep, on
+ * every route); the other outputs do not change.  With osd_enable = 0 every member from `osd` on is ignored and may be NULL.
+ * d_llr, alpha (T > 0), d_hard and d_fail are always required, d_index, d_count and d_cw when the OSD stage is on.
  * With timing_slot >= 0 the library brackets the three hot kernels with its own HIP events on
  * `stream`; after synchronising, ldpc_pipeline_timing returns their durations.
  * ------------------------------------------------------------------------------------- */
@@ -453,7 +470,8 @@ typedef struct ldpc_pipeline {
     ldpc_osd_params osd;
     int32_t *d_index, *d_count;    /* [B], [1]                                             */
     uint8_t *d_perm;               /* [B][128] nullable: both NULL = ldpc_osd_decode on the     */
-    uint64_t *d_parity;            /* [B][64]  context workspace (no per-kernel OSD timing)     */
+    uint64_t *d_parity;            /* [B][64]  context workspace (no per-kernel OSD timing);
+                                      exactly ONE of the two NULL is LDPC_E_ARG (OSD stage on)  */
     uint64_t *d_cw;                /* [B][2]                                               */
     float *d_metric;               /* [B] nullable                                         */
     int32_t *d_best, *d_ntep;      /* [B] nullable / [B]                                   */

@@ -129,12 +129,17 @@ int ldpc_nms_train_grad(ldpc_ctx *ctx, const float *d_llr, const uint64_t *d_lab
 int ldpc_pipeline_run(ldpc_ctx *ctx, const ldpc_pipeline *p, void *stream)
 {
     if (!ctx || !p) return fail(LDPC_E_ARG, "ldpc_pipeline_run: null argument");
+    if (p->B < 0 || (p->B > 0 && !p->d_llr)) return fail(LDPC_E_ARG, "ldpc_pipeline_run: d_llr is NULL or B < 0");
+    if (p->T > 0 && !p->alpha) return fail(LDPC_E_ARG, "ldpc_pipeline_run: alpha is NULL");
     if (!p->d_hard || !p->d_fail) return fail(LDPC_E_ARG, "ldpc_pipeline_run: d_hard and d_fail are required");
     const bool front = p->d_perm && p->d_parity;   // the caller wants the front-end results: front end and search apart
     int rc;
     if (p->osd_enable) {
         if (!p->d_index || !p->d_count || !p->d_cw)
             return fail(LDPC_E_ARG, "ldpc_pipeline_run: OSD stage needs d_index, d_count, d_cw");
+        if (!p->d_perm != !p->d_parity)
+            return fail(LDPC_E_ARG, "ldpc_pipeline_run: d_perm and d_parity go together (both, or both NULL); %s is NULL",
+                        p->d_perm ? "d_parity" : "d_perm");
         if ((rc = check_params(ctx, &p->osd, front, "ldpc_pipeline_run"))) return rc;
     }
     hipStream_t s = (hipStream_t)stream;

@@ -494,7 +494,8 @@ int ldpc_hosd_search(ldpc_ctx *ctx, const float *d_order_llr, const float *d_met
                      void *stream)
 {
     if (!ctx || F < 0 || nblk < 0 ||
-        (F > 0 && (!d_order_llr || !d_metric_llr || !d_lri || !d_uidx || !d_M || !d_block_off || (nblk > 0 && !d_block_min))))
+        (F > 0 && (!d_order_llr || !d_metric_llr || !d_lri || !d_uidx || !d_M || !d_block_off ||
+                   (nblk > 0 && (!d_block_min || !d_teps)))))     // (the kernels read d_teps[0 .. d_block_off[nblk]), device data)
         return fail(LDPC_E_ARG, "ldpc_hosd_search: bad arguments");
     if (d_truth && !d_label_bits) return fail(LDPC_E_ARG, "ldpc_hosd_search: d_truth needs d_label_bits");
     if (!ctx->hosd_ok)
