@@ -23,6 +23,7 @@
 //                 the iteration loop touches neither LDS nor memory.  No MFMA: there is no
 //                 contraction here, the kernel is VALU-issue bound.
 #include "ldpc_nms_generic.h"
+#include "ldpc_wave.h"
 
 namespace ldpc {
 
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(256) void nms_generic_kernel(
     float *yb = tot + n;
     const int words = (n + 63) >> 6;
 
-    if (count) { const long long c = *count; B = c < B ? c : B; }
+    B = frame_count(count, B);
     for (long long f = (long long)blockIdx.x * 4 + wave; f < B; f += (long long)gridDim.x * 4) {
         const long long src = index ? index[f] : f;
         for (int v = lane; v < n; v += 64) {

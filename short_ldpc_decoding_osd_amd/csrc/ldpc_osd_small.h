@@ -1,0 +1,98 @@
+// OSD kernels, the short ones (one frame per wavefront, no MFMA: bit and compare work): osd_ge_kernel, osd_front_kernel and
+//   osd_search_kernel   conventional order-p search over the reference's TEP table: per frame a byte-indexed LUT of partial |y'|
+//                       sums in LDS (8 x 256 floats), each lane evaluates one TEP per round: parity word = d0 ^ P'[i] ^ P'[j] ...,
+//                       metric = flipped-MRB weights + 8 LUT terms in a FIXED order (the canonical order the oracle uses, see
+//                       oracle/np_oracle.py weighted_distance), first minimum.
+#pragma once
+
+#include "ldpc_search.h"
+#include "ldpc_front.h"
+
+namespace ldpc {
+
+// ---------------------------------------------------------------------------------------
+// ldpc_osd_ge: elimination of caller-supplied matrices (row-major in, row-major out)
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void osd_ge_kernel(const u64 *__restrict__ rows_in, long long F, u64 *__restrict__ rows_out,
+        unsigned char *__restrict__ swaps, int *__restrict__ nswaps)
+{
+    const int lane = threadIdx.x & 63;
+    const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    for (long long f = wave; f < F; f += (long long)gridDim.x * 4) {
+        const u64 *src = rows_in + f * 128;
+        u64 C1 = transpose64(src[lane * 2], lane);      // row r, columns 0..63  -> column lane, bit r
+        u64 C2 = transpose64(src[lane * 2 + 1], lane);
+        int rho = lane, idx1 = lane, idx2 = lane + 64;
+        const int ns = ge_columns(C1, C2, rho, idx1, idx2, lane, swaps ? swaps + f * 128 : nullptr);
+        // back to row-major, logical row order: lane = physical row after the transpose
+        const u64 R1 = transpose64(C1, lane), R2 = transpose64(C2, lane);
+        rows_out[f * 128 + lane * 2] = shfl64(R1, rho);
+        rows_out[f * 128 + lane * 2 + 1] = shfl64(R2, rho);
+        if (nswaps && lane == 0) nswaps[f] = ns;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// OSD front end (the per-frame device code: ldpc_front.h)
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void osd_front_kernel(const float *__restrict__ y, const int *__restrict__ index, const int *__restrict__ count,
+        long long F, const u64 *__restrict__ Gcols, unsigned char *__restrict__ perm_out, u64 *__restrict__ parity_out, int *__restrict__ nswaps)
+{
+    __shared__ FrontLds L;   // one wavefront per workgroup
+    const int lane = threadIdx.x;
+    const long long nframes = frame_count(count, F);
+
+    for (long long f = blockIdx.x; f < nframes; f += gridDim.x) {
+        const long long src = index ? index[f] : f;
+        const FrontResult res = front_device(L, y, src, Gcols, lane);
+        perm_out[f * 128 + lane] = (unsigned char)res.o1;
+        perm_out[f * 128 + 64 + lane] = (unsigned char)res.o2;
+        parity_out[f * 64 + lane] = res.Prow;
+        if (nswaps && lane == 0) nswaps[f] = res.ns;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// conventional order-p search (convention_osd_main, convention_osd.py:49-76)
+// ---------------------------------------------------------------------------------------
+// WAVES = 1 for the long scans (one wavefront per workgroup: compile-time LDS base for the LUT reads, frames
+// balanced by the dispatcher), 4 for orders 0 and 1, where a frame is too little work to pay for a workgroup
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void osd_search_kernel(const float *__restrict__ y, const int *__restrict__ index,
+        const int *__restrict__ count, long long F, const unsigned char *__restrict__ perm_in, const u64 *__restrict__ parity_in,
+        const uchar4 *__restrict__ teps, int ntep, u64 *__restrict__ cw_out, float *__restrict__ metric_out, int *__restrict__ best_out,
+        int *__restrict__ ntep_out)
+{
+    __shared__ SearchLds lds[WAVES];
+    const int lane = threadIdx.x & 63;
+    SearchLds &L = lds[WAVES == 1 ? 0 : threadIdx.x >> 6];
+    const long long nframes = frame_count(count, F);
+    const long long wave = (long long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+
+    for (long long f = wave; f < nframes; f += (long long)gridDim.x * WAVES) {
+        const long long src = index ? index[f] : f;
+        const SearchFrame S = search_prepare(L, y, src, perm_in, parity_in, f, lane);
+        // scan the TEP table, one TEP per lane per round; strict '<' keeps the first minimum
+        float best = __builtin_inff();
+        int bestt = 0x7FFFFFFF;
+        u64 bestD = 0, bestE = 0;
+        // (exact early exit on the metric prefix, see tep_cost_bounded; `bound` = the wave's best so far)
+        float bound = __builtin_inff();
+        int trip = 0;
+        for (int t0 = 0; t0 < ntep; t0 += 64, ++trip) {
+            const int t = t0 + lane;
+            if (t < ntep) {
+                u64 D, E;
+                float mrb, c;
+                tep_apply(L, teps[t], S.d0, D, E, mrb);
+                if (tep_cost_bounded(L, mrb, D, bound, c) && c < best) { best = c; bestt = t; bestD = D; bestE = E; }
+            }
+            if ((trip & 7) == 0) bound = wave_min_f32(best);
+        }
+        wave_argmin(best, bestt, bestD, bestE, lane);
+        search_finish(L, S, bestE, bestD, f, lane, cw_out);
+        store_results(f, lane, best, bestt, ntep, metric_out, best_out, ntep_out);
+    }
+}
+
+}  // namespace ldpc

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void pb
     long long nframes = F;
     const long long wave = blockIdx.x;
     if (mode == 2) {   // every frame to the list replay, in frame order
-        if (count) { const long long c = *count; nframes = c < F ? c : F; }
+        nframes = frame_count(count, F);
         for (long long f = wave * 64 + lane; f < nframes; f += (long long)gridDim.x * 64) listB[f] = (int)f;
         if (wave == 0 && lane == 0) ctl[kPbCtlLenB] = (int)nframes;
         return;

@@ -153,6 +153,16 @@ __device__ __forceinline__ void search_finish(LDS &L, const SearchFrame &S, u64 
     wave_fence();
 }
 
+// the per-frame results beside the codeword: lane 0 stores those the caller asked for
+__device__ __forceinline__ void store_results(long long f, int lane, float metric, int best, int ntep, float *metric_out, int *best_out,
+                                              int *ntep_out)
+{
+    if (lane != 0) return;
+    if (metric_out) metric_out[f] = metric;
+    if (best_out) best_out[f] = best;
+    if (ntep_out) ntep_out[f] = ntep;
+}
+
 // one TEP (ascending support s.x < s.y < s.z, weight s.w) -> parity discrepancy, flip mask, MRB weight sum
 __device__ __forceinline__ void tep_apply(const SearchLds &L, uchar4 s, u64 d0, u64 &D, u64 &E, float &mrb)
 {

@@ -10,6 +10,14 @@ typedef unsigned long long u64;
 
 constexpr int kOsdN = 128, kOsdK = 64;
 
+// frames of a launch: F, or min(*count, F) with a device-side count (a count left over from an earlier, larger call cannot overrun)
+__device__ __forceinline__ long long frame_count(const int *count, long long F)
+{
+    long long nframes = F;
+    if (count) { const long long c = *count; nframes = c < F ? c : F; }
+    return nframes;
+}
+
 // ---------------------------------------------------------------------------------------
 // wave-level helpers
 // ---------------------------------------------------------------------------------------

@@ -62,6 +62,33 @@ class Decoder:
     def empty(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
 
+    def _outputs(self, out, table):
+        """``out`` (dict or None) as a dict with every key of ``table`` (name -> (shape, dtype, want)): a wanted output
+        that is missing or None is allocated, one neither wanted nor given is None."""
+        out = dict(out or {})
+        for k, (shape, dtype, want) in table.items():
+            if want and out.get(k) is None:
+                out[k] = self.empty(shape, dtype)
+            out.setdefault(k, None)
+        return out
+
+    def _osd_outputs(self, out, F):
+        return self._outputs(out, {"cw": ((F, 2), torch.int64, True), "metric": ((F,), torch.float32, True),
+                                   "best": ((F,), torch.int32, True), "ntep": ((F,), torch.int32, True)})
+
+    def _hosd_args(self, order_llr, metric_llr, front, teps, block_off):
+        """The checks hosd_search and hosd_sliding share.  Returns (lri, uidx, M, F, nblk)."""
+        self._chk(order_llr, torch.float32, (self.n,), "order_llr")
+        self._chk(metric_llr, torch.float32, (self.n,), "metric_llr")
+        lri, uidx, M = front[:3]
+        F = order_llr.shape[0]
+        if metric_llr.shape[0] != F or lri.shape[0] != F:
+            raise ValueError("order_llr, metric_llr and the front-end results must hold the same frames")
+        self._chk(teps, torch.uint8, (4,), "teps")
+        if block_off.dtype != torch.int32 or block_off.device != self.device or block_off.dim() != 1 or block_off.numel() < 1:
+            raise ValueError("block_off: expected a 1-D int32 tensor [nblk+1] on the device")
+        return lri, uidx, M, F, block_off.numel() - 1
+
     # ------------------------------------------------------------------ NMS
     def nms(self, llr, T, alpha, w_in=1.0, w_out=1.0, want_soft=True, want_traj=False, want_hard=True,
             want_fail=True, kernel=_lib.NMS_AUTO, out=None):
@@ -70,17 +97,8 @@ class Decoder:
         self._chk(llr, torch.float32, (self.n,), "llr")
         B = llr.shape[0]
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, dtype=np.float32), (max(T, 1),)))
-        out = dict(out or {})
-        if want_soft and out.get("soft") is None:
-            out["soft"] = self.empty((B, self.n), torch.float32)
-        if want_traj and out.get("traj") is None:
-            out["traj"] = self.empty((T, B, self.n), torch.float32)
-        if want_hard and out.get("hard") is None:
-            out["hard"] = self.empty((B, self.words), torch.int64)
-        if want_fail and out.get("fail") is None:
-            out["fail"] = self.empty((B,), torch.uint8)
-        for k in ("soft", "traj", "hard", "fail"):
-            out.setdefault(k, None)
+        out = self._outputs(out, {"soft": ((B, self.n), torch.float32, want_soft), "traj": ((T, B, self.n), torch.float32, want_traj),
+                                  "hard": ((B, self.words), torch.int64, want_hard), "fail": ((B,), torch.uint8, want_fail)})
         _lib.check(self.L.ldpc_nms_decode(self._ctx, _ptr(llr), B, T, a.ctypes.data_as(C.POINTER(C.c_float)),
                                           float(w_in), float(w_out), _ptr(out["soft"]), _ptr(out["traj"]),
                                           _ptr(out["hard"]), _ptr(out["fail"]), int(kernel), self._stream()),
@@ -113,15 +131,10 @@ class Decoder:
             raise ValueError(f"label_bits: {label_bits.shape[0]} frames for {B} channel frames")
         a = np.asarray(alpha, dtype=np.float32)
         a = np.ascontiguousarray(np.broadcast_to(a, (max(T, 1),)) if T > 0 else np.zeros(1, np.float32))
-        out = dict(out or {})
-        shapes = {"loss": ((B,), torch.float32, want_loss), "grad": ((B, T + 2), torch.float32, want_grad),
-                  "loss_sum": ((1,), torch.float64, want_sums), "grad_sum": ((T + 2,), torch.float64, want_sums),
-                  "traj": ((T, B, self.n), torch.float32, want_traj), "hard": ((B, self.words), torch.int64, want_hard),
-                  "fail": ((B,), torch.uint8, want_fail)}
-        for k, (shape, dtype, want) in shapes.items():
-            if want and out.get(k) is None:
-                out[k] = self.empty(shape, dtype)
-            out.setdefault(k, None)
+        out = self._outputs(out, {"loss": ((B,), torch.float32, want_loss), "grad": ((B, T + 2), torch.float32, want_grad),
+                                  "loss_sum": ((1,), torch.float64, want_sums), "grad_sum": ((T + 2,), torch.float64, want_sums),
+                                  "traj": ((T, B, self.n), torch.float32, want_traj), "hard": ((B, self.words), torch.int64, want_hard),
+                                  "fail": ((B,), torch.uint8, want_fail)})
         _lib.check(self.L.ldpc_nms_train_grad(self._ctx, _ptr(llr), _ptr(label_bits), B, T, a.ctypes.data_as(C.POINTER(C.c_float)),
                                               float(w_in), float(w_out), _ptr(out["loss"]), _ptr(out["grad"]),
                                               _ptr(out["loss_sum"]), _ptr(out["grad_sum"]), _ptr(out["traj"]),
@@ -266,15 +279,7 @@ class Decoder:
         self._chk(y, torch.float32, (self.n,), "y")
         F = (index.shape[0] if index is not None else y.shape[0]) if F is None else F
         p = params if params is not None else self.osd_params(order, algo)
-        out = dict(out or {})
-        if out.get("cw") is None:
-            out["cw"] = self.empty((F, 2), torch.int64)
-        if out.get("metric") is None:
-            out["metric"] = self.empty((F,), torch.float32)
-        if out.get("best") is None:
-            out["best"] = self.empty((F,), torch.int32)
-        if out.get("ntep") is None:
-            out["ntep"] = self.empty((F,), torch.int32)
+        out = self._osd_outputs(out, F)
         _lib.check(self.L.ldpc_osd_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, C.byref(p), _ptr(out["cw"]),
                                           _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]), self._stream()),
                    "ldpc_osd_decode")
@@ -286,11 +291,7 @@ class Decoder:
         self._chk(perm, torch.uint8, (128,), "perm")
         self._chk(parity, torch.int64, (64,), "parity")
         F = perm.shape[0] if F is None else F
-        out = dict(out or {})
-        for name, shape, dt in (("cw", (F, 2), torch.int64), ("metric", (F,), torch.float32),
-                                ("best", (F,), torch.int32), ("ntep", (F,), torch.int32)):
-            if out.get(name) is None:
-                out[name] = self.empty(shape, dt)
+        out = self._osd_outputs(out, F)
         _lib.check(self.L.ldpc_osd_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
                                           C.byref(params), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
                                           _ptr(out["ntep"]), self._stream()), "ldpc_osd_search")
@@ -326,16 +327,7 @@ class Decoder:
     def hosd_search(self, order_llr, metric_llr, front, teps, block_off, label_bits=None, want_arg=True, want_best=True):
         """Block minima over the TEP blocks ``teps[block_off[b]:block_off[b+1]]`` (device tensors: [Nt,4] u8,
         [nblk+1] int32).  Returns dict(block_min[F,nblk], block_arg, truth, cw, metric, best)."""
-        self._chk(order_llr, torch.float32, (self.n,), "order_llr")
-        self._chk(metric_llr, torch.float32, (self.n,), "metric_llr")
-        lri, uidx, M = front[:3]
-        F = order_llr.shape[0]
-        if metric_llr.shape[0] != F or lri.shape[0] != F:
-            raise ValueError("order_llr, metric_llr and the front-end results must hold the same frames")
-        self._chk(teps, torch.uint8, (4,), "teps")
-        if block_off.dtype != torch.int32 or block_off.device != self.device or block_off.dim() != 1 or block_off.numel() < 1:
-            raise ValueError("block_off: expected a 1-D int32 tensor [nblk+1] on the device")
-        nblk = block_off.numel() - 1
+        lri, uidx, M, F, nblk = self._hosd_args(order_llr, metric_llr, front, teps, block_off)
         out = dict(block_min=self.empty((F, nblk), torch.float32),
                    block_arg=self.empty((F, nblk), torch.int32) if want_arg else None,
                    truth=self.empty((F,), torch.float32) if label_bits is not None else None,
@@ -355,17 +347,8 @@ class Decoder:
         (``fcn_weights``: dense1 [win+1,win+1] then dense2 [win+1,2], packed f32) fires with p1 > soft_margin.  Returns
         dict(deep_limit[F] int32, global_min[F], truth[F], success[F] bool, cw[F,2], metric[F], best[F] (first minimum over
         the blocks the reference evaluates), teps[F] int32 (TEPs scanned, speculative ones included))."""
-        self._chk(order_llr, torch.float32, (self.n,), "order_llr")
-        self._chk(metric_llr, torch.float32, (self.n,), "metric_llr")
-        lri, uidx, M = front[:3]
-        F = order_llr.shape[0]
-        if metric_llr.shape[0] != F or lri.shape[0] != F:
-            raise ValueError("order_llr, metric_llr and the front-end results must hold the same frames")
-        self._chk(teps, torch.uint8, (4,), "teps")
-        if block_off.dtype != torch.int32 or block_off.device != self.device or block_off.dim() != 1 or block_off.numel() < 1:
-            raise ValueError("block_off: expected a 1-D int32 tensor [nblk+1] on the device")
+        lri, uidx, M, F, nblk = self._hosd_args(order_llr, metric_llr, front, teps, block_off)
         w = np.ascontiguousarray(np.asarray(fcn_weights, dtype=np.float32).reshape(-1))
-        nblk = block_off.numel() - 1
         lab = label_bits is not None
         out = dict(deep_limit=self.empty((F,), torch.int32), global_min=self.empty((F,), torch.float32),
                    truth=self.empty((F,), torch.float32) if lab else None,

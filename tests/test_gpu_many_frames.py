@@ -26,16 +26,16 @@ ALPHA0 = 0.669435
 
 # Frames per trip of each kernel (frames a full grid takes in one pass), from its launcher.  "cu" = the device's CU count.
 TRIPS = {
-    "osd_fused2r": lambda cu: cu * 16 * 6,    # ldpc_osd.hip:967 grid2r, one frame per workgroup
-    "osd_search2r": lambda cu: cu * 16 * 6,   # ldpc_osd.hip:967
-    "osd_front": lambda cu: 65536,            # ldpc_osd.hip:956 / :1079, one wavefront per workgroup
-    "osd_search2": lambda cu: 65536,          # ldpc_osd.hip:968 g64 (readlane order-2 scan)
-    "osd_search<1>": lambda cu: 65536,        # ldpc_osd.hip:968 g64 (table scan, orders 2 and 3)
-    "osd_fs": lambda cu: 65536,               # ldpc_osd.hip:968 g64
-    "osd_search<4>": lambda cu: 4096 * 4,     # ldpc_osd.hip:890 osd_grid, 4 waves per workgroup (orders 0 and 1)
-    "osd_ge": lambda cu: 4096 * 4,            # ldpc_osd.hip:890
-    "osd_tep_eval": lambda cu: 4096 * 4,      # ldpc_osd.hip:890
-    "index_guard": lambda cu: 1024 * 256,     # ldpc_osd.hip:883, one entry per thread
+    "osd_fused2r": lambda cu: cu * 16 * 6,    # ldpc_osd.hip grid2r(), one frame per workgroup
+    "osd_search2r": lambda cu: cu * 16 * 6,   # ldpc_osd.hip grid2r()
+    "osd_front": lambda cu: 65536,            # ldpc_osd.hip launch_front(): frame_grid(), one wavefront per workgroup
+    "osd_search2": lambda cu: 65536,          # ldpc_osd.hip frame_grid() (readlane order-2 scan)
+    "osd_search<1>": lambda cu: 65536,        # ldpc_osd.hip frame_grid() (table scan, orders 2 and 3)
+    "osd_fs": lambda cu: 65536,               # ldpc_osd.hip frame_grid()
+    "osd_search<4>": lambda cu: 4096 * 4,     # ldpc_osd.hip osd_grid(), 4 waves per workgroup (orders 0 and 1)
+    "osd_ge": lambda cu: 4096 * 4,            # ldpc_osd.hip osd_grid()
+    "osd_tep_eval": lambda cu: 4096 * 4,      # ldpc_osd.hip osd_grid()
+    "index_guard": lambda cu: 1024 * 256,     # ldpc_osd.hip guarded_index(), one entry per thread
     "hosd_front": lambda cu: 8192 * 4,        # ldpc_hosd.hip:463 grid_for(F, 4)
     "hosd_search": lambda cu: 8192,           # ldpc_hosd.hip:463 grid_for(F, 1), one frame per workgroup
     "hosd_sliding": lambda cu: 8192,          # ldpc_hosd.hip:463 grid_for(F, 1)
