@@ -352,6 +352,42 @@ int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label
                     const int32_t *d_count, const int32_t *d_ntep, int64_t F, int64_t *d_counts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * OSD for short codes of any shape: the front end (swapped_info / identify_mrb / full_gf2elim,
+ * PB_OSD/pb_testing.py:231-320) and the conventional order-p search (convention_osd_main,
+ * FS_OSD/convention_osd.py:49-76) for every code with 1 <= k <= 64 and 1 <= n-k <= 64 (hence n <= 128): the
+ * reference's (96,48) and (121,60) alist codes, and (128,64) itself, where the results equal those of the entry
+ * points above bit for bit.  Everything else of this header that says OSD -- FS-OSD, PB-OSD, the elimination and
+ * one-TEP primitives, the H-form primitives, the one-call pipeline and ldpc_osd_params with its flags -- stays with
+ * (n = 128, k = 64) and keeps answering LDPC_E_UNSUPPORTED on other shapes.
+ * Same rules as above for d_index / d_count (min(*d_count, F) frames, read on the device; nothing at or beyond that
+ * frame is written), for ties of the sort (lower index first), the TEP table (the one of this code's k, orders 0..3,
+ * first minimum) and the float order of the metric: flipped MRB weights ascending from 0.0f, then bytes of eight
+ * parity positions from primed position k (the last may be partial), each ascending from 0.0f, added in order.
+ *   d_y       [*][n] f32, stride n: the layout of ldpc_nms_decode's d_soft
+ *   d_perm    [F][128] u8 : original bit at primed position p < n (MRB 0..k-1, parity k..n-1); 0 for p >= n
+ *   d_parity  [F][64] u64 : row r < k, bit c < n-k = P'[r][c]; rows >= k and bits >= n-k are written as 0
+ *   d_nswaps  [F] i32 (nullable): recorded column exchanges
+ *   d_cw      [F][ceil(n/64)] u64 best codeword, ORIGINAL bit order (the layout of ldpc_pack_bits)
+ *   d_metric  [F] f32, d_best [F] i32 (index into the table), d_ntep [F] i32: nullable, each on its own
+ *   d_label_bits [*][ceil(n/64)] u64 addressed through d_index, d_counts[3] += {frames, frames_wrong, teps_total}
+ *             as the counting entry point above does: both or neither (nullable); teps_total moves only with d_ntep
+ * The decode entry point is two launches through the caller's d_perm / d_parity, which are scratch AND outputs and
+ * required: there is no library workspace and no per-stream state.  Before any launch: an unsupported shape is
+ * LDPC_E_UNSUPPORTED (the message names the limits and the code's (n,k)), an order outside 0..3 and a NULL in a
+ * required pointer are LDPC_E_ARG, F == 0 is LDPC_OK.  The tables (G columns, the order-3 TEP table of k) are
+ * uploaded by ldpc_ctx_create; nothing is allocated and nothing synchronises in a call (graph-capturable).
+ * ------------------------------------------------------------------------------------- */
+int ldpc_osdx_supported(const ldpc_ctx *ctx); /* 1: the three entry points below serve this code; 0: they refuse it */
+int ldpc_osdx_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                    uint8_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, void *stream);
+int ldpc_osdx_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                     const uint8_t *d_perm, const uint64_t *d_parity, int32_t order, uint64_t *d_cw, float *d_metric,
+                     int32_t *d_best, int32_t *d_ntep, void *stream);
+int ldpc_osdx_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                     int32_t order, uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw, float *d_metric,
+                     int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits, int64_t *d_counts, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H):
  * DL_OSD_Testing_serial/ordered_statistics_decoding.py and nn_net.py: the per-frame sort / elimination /
  * candidate scan, the scan with the sliding-window early stop, and the bit-wise CNN.

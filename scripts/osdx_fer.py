@@ -1,0 +1,120 @@
+"""NMS + order-p OSD of any short code (1 <= k <= 64, 1 <= n-k <= 64): FER before and after the OSD, and the two OSD kernels timed.
+
+    python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2
+
+Frame generator -> ldpc_nms_decode -> ldpc_compact -> ldpc_osdx_decode on the failures (the reference's loop: NMS, then
+convention_osd_main on the frames with a non-zero syndrome).  Times are HIP events around --calls back-to-back launches on the
+failures of the whole batch, after a warm-up, --repeats times (every repeat is printed: their spread is the noise).  On a
+(128,64) code the specialised osd_front_kernel and the table-scan osd_search_kernel are timed on the same frames in the same run.
+One JSON line at the end."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np   # noqa: E402
+import torch         # noqa: E402
+
+from short_ldpc_decoding_osd_amd import Code                    # noqa: E402
+from short_ldpc_decoding_osd_amd.runtime import Decoder         # noqa: E402
+
+
+def make_frames(dec, B, seed, snr_db):
+    """Synthetic frames on the device (data_generating.py:13-51): y = (1 - 2c)(1 + sigma N(0,1)), packed labels."""
+    g = torch.Generator(device=dec.device).manual_seed(seed)
+    G = torch.from_numpy(np.asarray(dec.code.G)).to(device=dec.device, dtype=torch.float32)
+    sigma = float(np.sqrt(1.0 / (2.0 * (dec.k / dec.n) * 10.0 ** (snr_db / 10.0))))
+    y = torch.empty((B, dec.n), dtype=torch.float32, device=dec.device)
+    labels = torch.empty((B, dec.words), dtype=torch.int64, device=dec.device)
+    for s in range(0, B, 1 << 16):
+        e = min(B, s + (1 << 16))
+        msg = torch.randint(0, 2, (e - s, dec.k), device=dec.device, generator=g).to(torch.float32)
+        cw = (msg @ G).remainder_(2)
+        y[s:e] = (1 - 2 * cw) * (1 + sigma * torch.randn((e - s, dec.n), device=dec.device, generator=g))
+        labels[s:e] = dec.pack_bits(cw.to(torch.uint8))
+    return y, labels
+
+
+def timed(fn, calls, repeats, warmup):
+    """us per call of fn(): HIP events around `calls` back-to-back calls, `repeats` times after `warmup` calls."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    out = []
+    for _ in range(repeats):
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / calls * 1e3)
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--alist", default=None, help="alist file of the code (default: the packaged CCSDS (128,64) code)")
+    ap.add_argument("--snr", type=float, default=2.5)
+    ap.add_argument("--frames", type=int, default=131072)
+    ap.add_argument("--T", type=int, default=10)
+    ap.add_argument("--alpha", type=float, default=0.669435, help="effective check normaliser of NMS-1")
+    ap.add_argument("--order", type=int, default=2)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=5)
+    args = ap.parse_args(argv)
+
+    dec = Decoder(Code(args.alist) if args.alist else Code(), 0)
+    if not dec.osdx_supported:
+        raise SystemExit(f"osdx_fer: the OSD kernels serve 1 <= k <= 64 and 1 <= n-k <= 64; this code is ({dec.n},{dec.k})")
+    B = args.frames
+    y, labels = make_frames(dec, B, args.seed, args.snr)
+    res = dec.nms(y, args.T, args.alpha)
+    nms_counts = dec.eval_counts(res["hard"], labels, res["fail"])
+    index, count = dec.compact(res["fail"])
+    torch.cuda.synchronize()
+    nf = int(count.cpu()[0])
+    idx = index[:max(nf, 1)].contiguous()
+    counts = torch.zeros(3, dtype=torch.int64, device=dec.device)
+    out = dec.osdx_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
+    torch.cuda.synchronize()
+    nc = nms_counts.cpu().tolist()
+    oc = counts.cpu().tolist()
+    # a frame is wrong after the stage if NMS left an undetected error (zero syndrome: never listed) or the OSD missed it
+    fer_nms = nc[1] / B
+    fer_osd = (nc[3] + oc[1]) / B
+    print(f"({dec.n},{dec.k}) {args.snr} dB, {B} frames, NMS-{args.T}: FER {fer_nms:.3e} ({nc[1]} wrong, {nf} with a non-zero syndrome, "
+          f"{nc[3]} undetected)", flush=True)
+    print(f"  order-{args.order} OSD on the {nf} failures: FER {fer_osd:.3e} ({oc[1]} still wrong, {oc[2] // max(oc[0], 1)} TEPs per frame)",
+          flush=True)
+    result = dict(n=dec.n, k=dec.k, snr_db=args.snr, frames=B, T=args.T, order=args.order, failures=nf, fer_nms=fer_nms, fer_osd=fer_osd,
+                  kernels={})
+    if nf == 0:
+        print(json.dumps(result), flush=True)
+        return 0
+    front = (out["perm"], out["parity"], None)
+    legs = [("osdx_front_kernel", lambda: dec.osdx_front(y, index=idx, count=count, out=front)),
+            ("osdx_search_kernel", lambda: dec.osdx_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=out))]
+    if (dec.n, dec.k) == (128, 64):                      # the specialised kernels on the same frames, in the same run
+        p = dec.osd_params(args.order, table_scan=True)
+        perm2, par2, ns2 = dec.osd_front(y, index=idx, count=count)
+        out2 = dec.osd_search(y, perm2, par2, p, index=idx, count=count)
+        legs += [("osd_front_kernel", lambda: dec.osd_front(y, index=idx, count=count, out=(perm2, par2, ns2))),
+                 ("osd_search_kernel(table)", lambda: dec.osd_search(y, perm2, par2, p, index=idx, count=count, out=out2))]
+    for _ in range(2):                                   # the legs alternate: two passes over all of them
+        for name, fn in legs:
+            us = timed(fn, args.calls, args.repeats, args.warmup)
+            med = float(np.median(us))
+            result["kernels"].setdefault(name, []).append(dict(us_per_call=us, median_us=med, frames_per_s=nf / med * 1e6))
+            print(f"  {name:26s} {med:9.1f} us per call (min {min(us):.1f}, max {max(us):.1f}), {nf / med:8.2f} M frames/s", flush=True)
+    print(json.dumps(result), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

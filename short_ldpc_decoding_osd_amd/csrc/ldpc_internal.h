@@ -62,6 +62,7 @@ struct ldpc_ctx {
     bool osd_ok = false;
     bool hosd_ok = false;
     void *osd_state = nullptr;     // ldpc::OsdState (TEP tables; per-stream workspaces behind its mutex)
+    void *osdx_state = nullptr;    // ldpc::OsdxState (ldpc_osdx.hip): G columns and TEP table of any shape with k, n-k <= 64
     hipEvent_t *timing = nullptr;  // [LDPC_TIMING_SLOTS][6] events of ldpc_pipeline_run, created with the context
     unsigned timing_recorded[LDPC_TIMING_SLOTS] = {};   // bit i: event i of the slot was recorded by the last run that used it
 };

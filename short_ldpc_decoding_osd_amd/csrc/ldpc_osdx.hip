@@ -1,0 +1,142 @@
+// OSD for short codes of any shape: the host side of ldpc_osdx_* (context tables, validation, launches).
+// Conventional order-p OSD with its front end for every code with 1 <= k <= 64 and 1 <= n - k <= 64; the device code lies in
+// ldpc_osdx.h.  FS-OSD, PB-OSD and the one-call pipeline stay with the (128,64) kernels of ldpc_osd.hip / ldpc_osd_pb.hip.
+// There is no library workspace: ldpc_osdx_decode runs its two launches through the caller's d_perm / d_parity, so the calls
+// hold no per-stream state, allocate nothing and are graph-capturable as they are.
+#include "ldpc_osdx.h"
+
+namespace ldpc {
+
+struct OsdxState {
+    u64 *d_Gcols = nullptr;      // [n] column v of G as a k-bit word (bit r = G[r][v])
+    uchar4 *d_tep = nullptr;     // the order-3 TEP table for this k: (i, j, l, weight); orders 0..2 are its prefixes
+    int64_t ntep[4] = {0, 0, 0, 0};
+};
+
+static inline OsdxState *xstate(const ldpc_ctx *ctx) { return reinterpret_cast<OsdxState *>(ctx->osdx_state); }
+
+static bool osdx_shape_ok(const ldpc_code &c) { return c.k >= 1 && c.k <= 64 && c.n - c.k >= 1 && c.n - c.k <= 64; }
+
+// tables of every eligible shape, uploaded with the context (nothing is allocated by a decode call)
+int osdx_ctx_init(ldpc_ctx *ctx)
+{
+    const ldpc_code &c = ctx->code;
+    ctx->osdx_state = nullptr;
+    if (!osdx_shape_ok(c) || c.G.size() != (size_t)c.k * c.n) return LDPC_OK;   // the entry points will report UNSUPPORTED
+    OsdxState *st = new OsdxState();
+    ctx->osdx_state = st;
+    std::vector<u64> cols(c.n, 0);
+    for (int r = 0; r < c.k; ++r)
+        for (int v = 0; v < c.n; ++v)
+            if (c.G[(size_t)r * c.n + v]) cols[v] |= 1ull << r;
+    LDPC_HIP(hipMalloc((void **)&st->d_Gcols, sizeof(u64) * c.n));
+    LDPC_HIP(hipMemcpy(st->d_Gcols, cols.data(), sizeof(u64) * c.n, hipMemcpyHostToDevice));
+    int64_t bounds[4];
+    const int64_t total = tep_table(c.k, 3, nullptr, bounds);
+    if (total < 0) return (int)total;
+    std::vector<uint8_t> sup((size_t)total * 3), packed((size_t)total * 4);
+    tep_table(c.k, 3, sup.data(), nullptr);
+    for (int64_t t = 0; t < total; ++t) {
+        int w = 0;
+        for (int q = 0; q < 3; ++q) { packed[4 * t + q] = sup[3 * t + q] == 0xFF ? 0 : sup[3 * t + q]; w += sup[3 * t + q] != 0xFF; }
+        packed[4 * t + 3] = (uint8_t)w;
+    }
+    for (int o = 0; o < 4; ++o) st->ntep[o] = bounds[o];
+    LDPC_HIP(hipMalloc((void **)&st->d_tep, packed.size()));
+    LDPC_HIP(hipMemcpy(st->d_tep, packed.data(), packed.size(), hipMemcpyHostToDevice));
+    return LDPC_OK;
+}
+
+void osdx_ctx_release(ldpc_ctx *ctx)
+{
+    if (OsdxState *st = xstate(ctx)) {
+        (void)hipFree(st->d_Gcols);
+        (void)hipFree(st->d_tep);
+        delete st;
+    }
+    ctx->osdx_state = nullptr;
+}
+
+static int need_osdx(const ldpc_ctx *ctx)
+{
+    return xstate(ctx) ? LDPC_OK
+                       : fail(LDPC_E_UNSUPPORTED, "the any-shape OSD kernels need 1 <= k <= 64 and 1 <= n-k <= 64; this code is (%d,%d)",
+                              ctx->code.n, ctx->code.k);
+}
+
+// one wavefront per workgroup, a workgroup per frame up to 65536 (then strided: a wavefront decodes several frames in turn)
+static unsigned osdx_grid(int64_t F) { return (unsigned)(F < 65536 ? F : 65536); }
+
+static int osdx_launch_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F, uint8_t *d_perm,
+                             uint64_t *d_parity, int32_t *d_nswaps, hipStream_t s)
+{
+    const OsdxState *st = xstate(ctx);
+    hipLaunchKernelGGL(osdx_front_kernel, dim3(osdx_grid(F)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, ctx->code.n,
+                       ctx->code.k, st->d_Gcols, d_perm, reinterpret_cast<u64 *>(d_parity), d_nswaps);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+static int osdx_launch_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                              const uint8_t *d_perm, const uint64_t *d_parity, int order, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                              int32_t *d_ntep, const uint64_t *d_label, int64_t *d_counts, hipStream_t s)
+{
+    const OsdxState *st = xstate(ctx);
+    const bool counting = d_label && d_counts;
+    hipLaunchKernelGGL(osdx_search_kernel, dim3(osdx_grid(F)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, ctx->code.n,
+                       ctx->code.k, d_perm, reinterpret_cast<const u64 *>(d_parity), st->d_tep, (int)st->ntep[order],
+                       reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_ntep,
+                       counting ? reinterpret_cast<const u64 *>(d_label) : nullptr, counting ? reinterpret_cast<u64 *>(d_counts) : nullptr);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+}  // namespace ldpc
+
+using namespace ldpc;
+
+extern "C" {
+
+int ldpc_osdx_supported(const ldpc_ctx *ctx) { return ctx && xstate(ctx) ? 1 : 0; }
+
+int ldpc_osdx_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F, uint8_t *d_perm,
+                    uint64_t *d_parity, int32_t *d_nswaps, void *stream)
+{
+    if (!ctx || F < 0) return fail(LDPC_E_ARG, "ldpc_osdx_front: bad arguments");
+    if (int rc = need_osdx(ctx)) return rc;
+    if (F > 0 && (!d_y || !d_perm || !d_parity))
+        return fail(LDPC_E_ARG, "ldpc_osdx_front: %s is NULL", !d_y ? "d_y" : (!d_perm ? "d_perm" : "d_parity"));
+    if (F == 0) return LDPC_OK;
+    return osdx_launch_front(ctx, d_y, d_index, d_count, F, d_perm, d_parity, d_nswaps, (hipStream_t)stream);
+}
+
+int ldpc_osdx_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F, const uint8_t *d_perm,
+                     const uint64_t *d_parity, int32_t order, uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_ntep,
+                     void *stream)
+{
+    if (!ctx || F < 0) return fail(LDPC_E_ARG, "ldpc_osdx_search: bad arguments");
+    if (int rc = need_osdx(ctx)) return rc;
+    if (order < 0 || order > 3) return fail(LDPC_E_ARG, "ldpc_osdx_search: order %d outside 0..3", order);
+    if (F > 0 && (!d_y || !d_perm || !d_parity || !d_cw))
+        return fail(LDPC_E_ARG, "ldpc_osdx_search: %s is NULL", !d_y ? "d_y" : (!d_perm ? "d_perm" : (!d_parity ? "d_parity" : "d_cw")));
+    if (F == 0) return LDPC_OK;
+    return osdx_launch_search(ctx, d_y, d_index, d_count, F, d_perm, d_parity, order, d_cw, d_metric, d_best, d_ntep, nullptr, nullptr,
+                              (hipStream_t)stream);
+}
+
+int ldpc_osdx_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F, int32_t order,
+                     uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_ntep,
+                     const uint64_t *d_label_bits, int64_t *d_counts, void *stream)
+{
+    if (!ctx || F < 0) return fail(LDPC_E_ARG, "ldpc_osdx_decode: bad arguments");
+    if (int rc = need_osdx(ctx)) return rc;
+    if (order < 0 || order > 3) return fail(LDPC_E_ARG, "ldpc_osdx_decode: order %d outside 0..3", order);
+    if (F > 0 && (!d_y || !d_perm || !d_parity || !d_cw))
+        return fail(LDPC_E_ARG, "ldpc_osdx_decode: %s is NULL", !d_y ? "d_y" : (!d_perm ? "d_perm" : (!d_parity ? "d_parity" : "d_cw")));
+    if (F == 0) return LDPC_OK;
+    if (int rc = osdx_launch_front(ctx, d_y, d_index, d_count, F, d_perm, d_parity, nullptr, (hipStream_t)stream)) return rc;
+    return osdx_launch_search(ctx, d_y, d_index, d_count, F, d_perm, d_parity, order, d_cw, d_metric, d_best, d_ntep, d_label_bits,
+                              d_counts, (hipStream_t)stream);
+}
+
+}  // extern "C"

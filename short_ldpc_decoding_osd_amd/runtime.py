@@ -310,6 +310,62 @@ class Decoder:
                                             _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["hd"]), self._stream()), "ldpc_osd_tep_eval")
         return out
 
+    # ------------------------------------------------------------------ OSD for short codes of any shape
+    @property
+    def osdx_supported(self):
+        """Whether ``osdx_front`` / ``osdx_search`` / ``osdx_decode`` serve this code (1 <= k <= 64 and 1 <= n-k <= 64)."""
+        return bool(self.L.ldpc_osdx_supported(self._ctx))
+
+    def _osdx_outputs(self, out, F):
+        return self._outputs(out, {"cw": ((F, self.words), torch.int64, True), "metric": ((F,), torch.float32, True),
+                                   "best": ((F,), torch.int32, True), "ntep": ((F,), torch.int32, True)})
+
+    def osdx_front(self, y, index=None, count=None, F=None, out=None):
+        """``osd_front`` for any supported shape.  Returns (perm[F,128] u8: original bit at primed position p < n, MRB
+        first, 0 beyond n; parity[F,64] int64: rows r < k of P', bits c < n-k, 0 elsewhere; nswaps[F] int32); ``out`` may
+        carry those three preallocated (nswaps may be None)."""
+        self._chk(y, torch.float32, (self.n,), "y")
+        F = (index.shape[0] if index is not None else y.shape[0]) if F is None else F
+        if out is not None:
+            perm, parity, ns = out
+        else:
+            perm = self.empty((F, 128), torch.uint8)
+            parity = self.empty((F, 64), torch.int64)
+            ns = self.empty((F,), torch.int32)
+        _lib.check(self.L.ldpc_osdx_front(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
+                                          _ptr(ns), self._stream()), "ldpc_osdx_front")
+        return perm, parity, ns
+
+    def osdx_search(self, y, perm, parity, order, index=None, count=None, F=None, out=None):
+        """Conventional order-``order`` search on front-end results (perm [F,128] u8, parity [F,64] int64) of any supported
+        shape.  Returns dict(cw[F,words] int64 original bit order, metric[F] f32, best[F] i32, ntep[F] i32)."""
+        self._chk(y, torch.float32, (self.n,), "y")
+        self._chk(perm, torch.uint8, (128,), "perm")
+        self._chk(parity, torch.int64, (64,), "parity")
+        F = perm.shape[0] if F is None else F
+        out = self._osdx_outputs(out, F)
+        _lib.check(self.L.ldpc_osdx_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), int(order),
+                                           _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
+                                           self._stream()), "ldpc_osdx_search")
+        return out
+
+    def osdx_decode(self, y, order, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
+                    out=None):
+        """Front end + conventional order-``order`` search of the frames y[index[f]] (or y[f]) for any supported shape, two
+        launches through ``perm`` / ``parity`` (allocated when not given; returned in the dict).  With ``label_bits``
+        ([*, words] int64, addressed through ``index``) and ``counts`` ([3] int64) the search accumulates
+        counts += {frames, frames_wrong, teps_total}."""
+        self._chk(y, torch.float32, (self.n,), "y")
+        F = (index.shape[0] if index is not None else y.shape[0]) if F is None else F
+        perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
+        parity = self.empty((F, 64), torch.int64) if parity is None else self._chk(parity, torch.int64, (64,), "parity")
+        out = self._osdx_outputs(out, F)
+        _lib.check(self.L.ldpc_osdx_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, int(order), _ptr(perm), _ptr(parity),
+                                           _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
+                                           _ptr(label_bits), _ptr(counts), self._stream()), "ldpc_osdx_decode")
+        out["perm"], out["parity"] = perm, parity
+        return out
+
     # ------------------------------------------------------------------ H-form OSD (DL-OSD stage)
     def hosd_front(self, order_llr):
         """check_matrix_reorder + identify_mrb on [F,128] ordering values.  Returns (lri[F,128] u8,
