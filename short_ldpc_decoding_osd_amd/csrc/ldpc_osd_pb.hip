@@ -1,8 +1,13 @@
 // PB-OSD kernels for (128,64) codes on gfx950 (MI355X): the translation unit.  Here: the host side (workspace, tuning, launch_pb).
-// The device code lies in five headers, included in the order of the stages (ONE translation unit on purpose: the kernels share
+// The device code lies in eight headers, included in the order of the stages (ONE translation unit on purpose: the kernels share
 // inlined device code, and the order of the definitions is the order of the code object):
 //   ldpc_pb_common.h   the algorithm; float conventions, per-frame quantities, the two rules, TEP algebra, records
-//   ldpc_pb_singles.h  pb_singles_kernel    ldpc_pb_wave.h  pb_wave_kernel    ldpc_pb_coop.h  pb_coop_kernel    ldpc_pb_seq.h  pb_seq_kernel
+//   ldpc_pb_singles.h  pb_singles_kernel
+//   ldpc_pb_wave.h     pb_wave_kernel and the two functions of its rare paths; it includes, in this order,
+//     ldpc_pb_walk.h     a frame's LDS, the items and cursors, the walk that produces a chunk and the choice of its bound
+//     ldpc_pb_rules.h    what the three sort-free scans share, and where they differ on purpose
+//     ldpc_pb_pass.h     the cost of a candidate, the two wavefront scans, the sorted path
+//   ldpc_pb_coop.h     pb_coop_kernel (the workgroup scan)    ldpc_pb_seq.h  pb_seq_kernel
 #include <math.h>
 
 #include "ldpc_pb_common.h"

@@ -98,7 +98,7 @@ __device__ __forceinline__ void search2_device(Search2Lds &LL, const SearchFrame
         const u64 km = __ballot(keep);
         if (km) {
             if (keep) {
-                const int slot = (qhead + qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, 0))) & 127;
+                const int slot = (qhead + qn + wave_lane_rank(km)) & 127;
                 LL.q[slot] = make_uint4((unsigned)D, (unsigned)(D >> 32), __float_as_uint(acc), (unsigned)(r * 64 + lane));
             }
             qn += __popcll(km);

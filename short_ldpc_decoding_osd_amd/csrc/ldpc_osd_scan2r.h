@@ -77,7 +77,7 @@ __device__ __forceinline__ bool search2r_round(Search2rLds &LL, Scan2r &s, int R
     const u64 km = __ballot(keep);
     if (!km) return false;
     if (keep) {
-        const int slot = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, (unsigned)s.qn));
+        const int slot = wave_lane_rank(km, (unsigned)s.qn);
         LL.q[slot] = make_uint2(__float_as_uint(acc), (unsigned)(R * 64 + lane));
     }
     s.qn += __popcll(km);

@@ -1,6 +1,6 @@
 // PB-OSD stage 2c, pb_coop_kernel: the long searches pb_wave_kernel hands on, ONE WORKGROUP OF NW WAVEFRONTS PER FRAME (round 3);
 // chunks of <= 4096 TEPs counted by bisection and generated once, every wavefront judging the keys it generated; one workgroup
-// barrier per count and one per ordinary chunk.  The chunk pass of ldpc_pb_wave.h (above in the translation unit) needs no sort, so a
+// barrier per count and one per ordinary chunk.  The chunk pass of ldpc_pb_pass.h (above in the translation unit) needs no sort, so a
 // chunk is embarrassingly parallel over its keys, and the walk is parallel over the item rows: wavefront v owns 32 / NW of
 // the 32 rows (dealt so that light and heavy rows pair up), walks them into the workgroup's ONE key buffer (slots reserved by
 // an LDS atomic per trip, so the buffer fills evenly whatever the rows give) and scans every NW-th 64-key slice of it.
@@ -250,7 +250,7 @@ __device__ __forceinline__ int coop_next_chunk(PbCoopLds<NW> &L, CoopRed<NW> &R,
         const u64 am = __ballot(cj[j] > 0);
         const int na = __popcll(am);
         if (cj[j] > 0)
-            desc[(int)__builtin_amdgcn_mbcnt_hi((unsigned)(am >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)am, 0u))] =
+            desc[wave_lane_rank(am)] =
                 make_uint4((unsigned)I.a[j] | ((unsigned)cj[j] << 8) | ((unsigned)I.sh[j] << 16), (unsigned)o[j], __float_as_uint(I.sb[j]), I.code[j]);
         wave_fence();
         for (int p0 = 0; p0 < na; p0 += 8) {
@@ -285,21 +285,8 @@ __device__ __forceinline__ int coop_scan_chunk(PbCoopLds<NW> &L, CoopRed<NW> &R,
     const PbWaveLds<CAP> &T0 = L.one;
     if (S.nlive <= 1) return -1;
     const float best0 = S.best;
-    float r_safe;     // rule 1 by probes (pbw_scan_chunk)
-    {
-        const float rp = lane == 63 ? mx : mn + (mx - mn) * ((float)(lane + 1) * (1.0f / 64.0f));
-        float w1;
-        const float bs = pb_promising_bs(rp, best0, Fr, P.c4, T0.cdfA, T0.cdfH, w1);
-        const u64 unsafe = ~__ballot((double)bs > Fr.p_t_pro * 1.001);
-        const int u = unsafe ? __builtin_ctzll(unsafe) : 64;
-        r_safe = u == 0 ? -1.0f : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rp), u - 1));
-    }
-    const auto parity = [&](const PbTep &t) {
-        u64 D = d0 ^ T0.P[t.p0];
-        if (t.wt > 1) D ^= T0.P[t.p1];
-        if (t.wt > 2) D ^= T0.P[t.p2];
-        return D;
-    };
+    const float r_safe = pb_rule1_safe_sum(mn, mx, best0, Fr, P.c4, T0.cdfA, T0.cdfH, lane);      // rule 1 by probes
+    const auto parity = [&](const PbTep &t) { return pb_tep_parity(T0.P, d0, t); };
     const auto sumbits = [](u64 key) { return (unsigned)(key >> 32); };
     // a is visited before b (a != b): by sum, equal sums by the list-slot order (pb_visit_less: through the parents).  Round 4: a tie
     // against a reference key used to send the whole chunk, ~2700 keys, to wavefront 0 alone -- 1-4 times per launch at 2.5 dB,
@@ -322,7 +309,7 @@ __device__ __forceinline__ int coop_scan_chunk(PbCoopLds<NW> &L, CoopRed<NW> &R,
             const bool surv = valid && pbw_cost_floor<CAP>(T0, rs, parity(t)) < best0;
             const u64 sm = __ballot(surv);
             if (sm) {
-                if (surv) slist[nsurv + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(sm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)sm, 0u))] = (unsigned short)(kbase + k * 64 + lane);
+                if (surv) slist[nsurv + wave_lane_rank(sm)] = (unsigned short)(kbase + k * 64 + lane);
                 nsurv += __popcll(sm);
             }
             const int dl = valid ? pb_delta(t, P.order) : 0;
@@ -366,7 +353,7 @@ __device__ __forceinline__ int coop_scan_chunk(PbCoopLds<NW> &L, CoopRed<NW> &R,
                 int base = 0;
                 if (lane == 0) base = atomicAdd(&L.ncand[par], __popcll(cm));
                 base = __builtin_amdgcn_readfirstlane(base);
-                const int idx = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(cm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm, 0u));
+                const int idx = base + wave_lane_rank(cm);
                 if (cand && idx < kCoopMaxCand) { L.ck[idx] = key; L.cc[idx] = c; }
             }
         }
@@ -388,17 +375,14 @@ __device__ __forceinline__ int coop_scan_chunk(PbCoopLds<NW> &L, CoopRed<NW> &R,
     if (S.nlive - negtot <= 1) return -1;
     if (ncand > kCoopMaxCand) return -1;
     if (ncand == 0) {
-        if (sF == 0x7FFFFFFFu) {     // no candidate, no key fires: the whole chunk is visited and nothing else happens
-            S.cmp += 2 * n; S.suc1 += n;
-            S.j += n; S.nlive += deltot;
-            return 0;
-        }
+        // no candidate, no key fires: the whole chunk is visited and nothing else happens
+        if (sF == 0x7FFFFFFFu) return pbw_commit_counts(S, 0, 0, 0, n, deltot, stop, ntep);
         // no candidate, rule 1 fires: the search stops at the first key of the smallest firing sum (every key of that sum fires)
         int cs = 0;
 #pragma unroll
         for (int k = 0; k < PER; ++k)
             if (k * 64 < kcount) cs += sumbits(key_at(k)) < sF;
-        const int rank_stop = coop_sum<NW>(R, wave_add_i32(cs));
+        const int rank_stop = coop_sum<NW>(R, wave_add_i32(cs));      // (pbw_commit_counts(S, 0, 1, rank_stop, ...), written out: the call moves six lines of this kernel)
         S.cmp += 2 * (rank_stop + 1);
         S.suc1 += rank_stop;
         stop = 1; ntep = S.j + rank_stop + 1;
@@ -441,7 +425,7 @@ __device__ __forceinline__ int coop_scan_chunk(PbCoopLds<NW> &L, CoopRed<NW> &R,
     // record keep what the chunk-start best said (fs, if it lies before the first record).
     if (nrec > 0) {
         const unsigned s0 = sumbits(L.rk[0]);
-        float r_safe2;
+        float r_safe2;     // (pb_rule1_safe_sum with the last record's cost, written out: the helper costs this kernel an instruction)
         {
             const float rp = lane == 63 ? mx : mn + (mx - mn) * ((float)(lane + 1) * (1.0f / 64.0f));
             float w1;
@@ -508,22 +492,13 @@ __device__ __forceinline__ int coop_scan_chunk(PbCoopLds<NW> &L, CoopRed<NW> &R,
     const int rank_best = pos & 0x1FFF, rank_stop = reason == 2 ? rank_best : (pos >> 13) & 0x1FFF;
     if (nbefore > 0) {
         const PbTep t = pbw_tep((unsigned)bk);
-        u64 E = 1ull << t.p0;
+        u64 E = 1ull << t.p0;          // (pb_tep_mask, written out: with the helper three moves of this kernel change places)
         if (t.wt > 1) E |= 1ull << t.p1;
         if (t.wt > 2) E |= 1ull << t.p2;
         S.best = bcost; S.bestD = parity(t); S.bestE = E;
         S.bestidx = S.j + rank_best + 1;
     }
-    S.suc2 += nbefore;
-    if (reason) {
-        S.cmp += 2 * (rank_stop + 1);
-        S.suc1 += reason == 1 ? rank_stop : rank_stop + 1;
-        stop = reason; ntep = S.j + rank_stop + 1;
-        return 1;
-    }
-    S.cmp += 2 * n; S.suc1 += n;
-    S.j += n; S.nlive += deltot;
-    return 0;
+    return pbw_commit_counts(S, nbefore, reason, rank_stop, n, deltot, stop, ntep);
 }
 
 // Wavefront 0 alone over the sums (lo, T] that hold n TEPs: the sorted path, in sub-chunks.  L.one.cur holds the cursors of

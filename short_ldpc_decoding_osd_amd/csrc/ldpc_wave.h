@@ -35,6 +35,12 @@ __device__ __forceinline__ u64 shfl64(u64 v, int src)
     return ((u64)hi << 32) | lo;
 }
 
+// base + the number of lanes below this one that are set in `mask`: the slot of a lane when the lanes of a ballot are compacted
+__device__ __forceinline__ int wave_lane_rank(u64 mask, unsigned base = 0u)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, base));
+}
+
 // ---- wave reductions on DPP (row/bank permutes inside the VALU, ~4 cycles per step) instead of
 // ds_bpermute shuffles (~30 cycles per wave-instruction on gfx950, profiles/r01/ubench_valu_issue.txt).
 // Pattern: xor-1, xor-2 quad permutes, row_half_mirror, row_mirror -> every lane holds its row's result;

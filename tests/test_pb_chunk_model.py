@@ -52,7 +52,7 @@ def test_visit_order_comparator_on_ties():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The direct enumeration of a sum range (csrc/ldpc_pb_wave.h, PbwItem): item layout, table-id formulas, the binary
+# The direct enumeration of a sum range (csrc/ldpc_pb_walk.h, PbwItem): item layout, table-id formulas, the binary
 # search and the empty-item shortcut, restated in NumPy float32 and checked against a brute-force filter of the kernel's
 # TEP table.
 # ---------------------------------------------------------------------------------------------------------------------
@@ -127,7 +127,7 @@ def test_sum_range_enumeration(order):
 
 
 def _items():
-    """The 2017 items of csrc/ldpc_pb_wave.h (pbw_item_rt): item (row q, lane l) -> fixed positions and the base of its members
+    """The 2017 items of csrc/ldpc_pb_walk.h (pbw_item_rt): item (row q, lane l) -> fixed positions and the base of its members
     (members are the last positions m in (base, 63])."""
     out = {}
     for q in range(32):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """TEST INFRASTRUCTURE (uses oracle/; CPU only).  Where the first guess of PB-OSD's chunk bounds comes from, and how many
-exact counts the bound picker of csrc/ldpc_pb_wave.h (pb_bound_guess, pbw_next_chunk) needs.
+exact counts the bound picker of csrc/ldpc_pb_walk.h (pb_bound_guess, pbw_next_chunk) needs.
 
     python tests/tools/pb_bound_model.py [--snr 2.5] [--frames 6000] [--sample 400]
 
