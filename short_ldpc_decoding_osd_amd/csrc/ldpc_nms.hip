@@ -180,15 +180,32 @@ __device__ __forceinline__ void var_sums(const float (&cv)[32], int j, float (&S
     }
 }
 
-// One block row of check nodes: lane j is check (BR, j).
-template <int BR, bool UP>
-__device__ __forceinline__ void check_row(float (&cv)[32], const float (&tot)[8], float a_it, unsigned signv)
+// vc = tot[var] - cv of one block row: lane j is check (BR, j); variable (bc, j + s) sits s lanes above: rotate down by s.
+// FIRST: iteration 1, where every cv is 0: x - (+0) is x bit for bit, zeros included, so vc is the rotated total itself
+// (12 of the 32 circulants have shift 0 and cost nothing, the other 20 are a bare DPP move) and cv is not read.
+template <int BR, bool UP, bool FIRST>
+__device__ __forceinline__ void row_vc(float (&vc)[32], const float (&cv)[32], const float (&tot)[8])
 {
-    float vc[8];
-    // vc = tot[var] - cv ; variable (bc, j + s) sits s lanes above: rotate down by s
-#define LDPC_VC(t) vc[t] = rot_f<16 - kTerms[BR * 8 + t].s, UP>(tot[kTerms[BR * 8 + t].bc]) - cv[BR * 8 + t];
+#define LDPC_VC(t)                                                                              \
+    {                                                                                           \
+        const float rt = rot_f<16 - kTerms[BR * 8 + t].s, UP>(tot[kTerms[BR * 8 + t].bc]);      \
+        if constexpr (FIRST) vc[BR * 8 + t] = rt;                                               \
+        else vc[BR * 8 + t] = rt - cv[BR * 8 + t];                                              \
+    }
     LDPC_VC(0) LDPC_VC(1) LDPC_VC(2) LDPC_VC(3) LDPC_VC(4) LDPC_VC(5) LDPC_VC(6) LDPC_VC(7)
 #undef LDPC_VC
+}
+
+// The new messages of one block row of check nodes from its eight vc.
+// EXACT: the reference's rule in full.  !EXACT: the same without "sign(0) = 0 wipes the row" -- right for every lane whose row
+// minimum is not 0; zmin collects the minimum over the rows seen so far (one v_min3 per row), and nms_iteration tests it
+// once and runs the EXACT form when some lane saw a zero.
+template <int BR, bool UP, bool EXACT>
+__device__ __forceinline__ void check_row(float (&cv)[32], const float (&vc32)[32], float a_it, unsigned signv, float &zmin)
+{
+    float vc[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) vc[t] = vc32[BR * 8 + t];
     // "minimum of the OTHER seven magnitudes" per edge == ((|vc| > m1) ? m1 : m2) of ms_test.py:200-206,
     // ties included, computed as a shared tree of v_min3: 4 pair minima (the 1e30 clip of :196 rides along as
     // their third operand -- every output contains at least one clipped node, so the clip reaches all of them),
@@ -201,8 +218,13 @@ __device__ __forceinline__ void check_row(float (&cv)[32], const float (&tot)[8]
     const float p01 = __builtin_fminf(__builtin_fminf(a[0], a[1]), 1e30f), p23 = __builtin_fminf(__builtin_fminf(a[2], a[3]), 1e30f);
     const float p45 = __builtin_fminf(__builtin_fminf(a[4], a[5]), 1e30f), p67 = __builtin_fminf(__builtin_fminf(a[6], a[7]), 1e30f);
     const float q03 = __builtin_fminf(p01, p23), q47 = __builtin_fminf(p45, p67);
-    // sign(0) = 0 wipes the whole check row (:187-191): a zero minimum zeroes the scale factor
-    const float aeff = (__builtin_fminf(q03, q47) == 0.0f) ? 0.0f : a_it;
+    float aeff = a_it;
+    if constexpr (EXACT) {
+        // sign(0) = 0 wipes the whole check row (:187-191): a zero minimum zeroes the scale factor
+        aeff = (__builtin_fminf(q03, q47) == 0.0f) ? 0.0f : a_it;
+    } else {
+        zmin = (BR == 0) ? __builtin_fminf(q03, q47) : __builtin_fminf(__builtin_fminf(zmin, q03), q47);
+    }
     float o[8];
     o[0] = __builtin_fminf(__builtin_fminf(a[1], p23), q47);
     o[1] = __builtin_fminf(__builtin_fminf(a[0], p23), q47);
@@ -228,6 +250,36 @@ __device__ __forceinline__ void check_row(float (&cv)[32], const float (&tot)[8]
     }
 }
 
+// One iteration's check-node half: cv <- the new messages, from the totals and the old cv.
+// The zero-row rule needs some |vc| to be exactly 0, which a noisy channel value essentially never gives, so the four rows run
+// without it and keep their 32 vc; one compare and one wave-uniform branch per iteration then decide whether some lane of the
+// wave met a zero, and only then the four rows are computed again from the kept vc with the rule (for all four frames of the
+// wave: the frames without a zero get the bits they already had, as the two forms differ in the scale factor of zero rows only).
+// The kept vc cost 32 VGPRs (the kernel is pinned to 4 waves per SIMD = 128 VGPRs, so occupancy does not move) and no
+// instruction: vc is written beside cv instead of over it.
+template <bool UP, bool FIRST>
+__device__ __forceinline__ void nms_iteration(float (&cv)[32], const float (&tot)[8], float a_it, unsigned signv)
+{
+    float vc[32], zmin = 0.0f, unused = 0.0f;
+    row_vc<0, UP, FIRST>(vc, cv, tot);
+    check_row<0, UP, false>(cv, vc, a_it, signv, zmin);
+    row_vc<1, UP, FIRST>(vc, cv, tot);
+    check_row<1, UP, false>(cv, vc, a_it, signv, zmin);
+    row_vc<2, UP, FIRST>(vc, cv, tot);
+    check_row<2, UP, false>(cv, vc, a_it, signv, zmin);
+    row_vc<3, UP, FIRST>(vc, cv, tot);
+    check_row<3, UP, false>(cv, vc, a_it, signv, zmin);
+    if (__builtin_expect(__ballot(zmin == 0.0f) != 0ull, 0)) {
+        // (the empty asm hides where vc came from, so that nothing of the fast rows is kept alive for this block)
+#pragma unroll
+        for (int e = 0; e < 32; ++e) asm volatile("" : "+v"(vc[e]));
+        check_row<0, UP, true>(cv, vc, a_it, signv, unused);
+        check_row<1, UP, true>(cv, vc, a_it, signv, unused);
+        check_row<2, UP, true>(cv, vc, a_it, signv, unused);
+        check_row<3, UP, true>(cv, vc, a_it, signv, unused);
+    }
+}
+
 template <int BR, bool UP>
 __device__ __forceinline__ int syndrome_row(const int (&h)[8])
 {
@@ -243,13 +295,13 @@ __device__ __forceinline__ int syndrome_row(const int (&h)[8])
 // output is traj[f][0..T][128] -- row 0 the channel values, row t the posterior after iteration t: the reference's buffer order.
 // The reference keeps T + 1 rows of the FAILED frames only; writing [T][B][128] for all frames (round 3's surface) was
 // 5.1 KiB per input frame against 1.4 KiB at 2.5 dB.  Same arithmetic, same order: the rows equal the full trajectory's.
-template <bool UP, bool ROWS = false>
+template <bool UP, bool ROWS, bool UNIT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void nms_qc16_kernel(const float *__restrict__ llr, long long B, int T,
                                                        AlphaArg alpha, float w_in, float w_out,
                                                        float *__restrict__ soft, float *__restrict__ traj,
                                                        unsigned long long *__restrict__ hard,
                                                        unsigned char *__restrict__ fail,
-                                                       const int *__restrict__ index = nullptr, const int *__restrict__ count = nullptr)
+                                                       const int *__restrict__ index, const int *__restrict__ count)
 {
     const int lane = threadIdx.x & 63;
     const int j = lane & 15, r = lane >> 4;
@@ -266,11 +318,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     float y[8], yin[8], yout[8], S[8], cv[32];
     const float *src = llr + (ROWS ? (long long)index[fl] : fl) * 128 + j;
 #pragma unroll
+    for (int bc = 0; bc < 8; ++bc) y[bc] = src[bc * 16];
+    // UNIT: bit weights of exactly 1 (NMS-1, what every caller of the package passes; launch_nms tests them).  y * 1.0f is y bit
+    // for bit (a signalling NaN apart, which no decoder output survives anyway), so yin, yout and y are one set of registers there
+    // and the 16 multiplies go (a uniform test inside the kernel only turned them into 16 moves).
+#pragma unroll
     for (int bc = 0; bc < 8; ++bc) {
-        y[bc] = src[bc * 16];
-        yin[bc] = y[bc] * w_in;
-        yout[bc] = w_out * y[bc];
-        S[bc] = 0.0f;
+        yin[bc] = UNIT ? y[bc] : y[bc] * w_in;
+        yout[bc] = UNIT ? y[bc] : w_out * y[bc];
     }
     if constexpr (ROWS) {
         if (live) {
@@ -279,22 +334,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             for (int bc = 0; bc < 8; ++bc) dst[bc * 16] = y[bc];
         }
     }
-#pragma unroll
-    for (int e = 0; e < 32; ++e) cv[e] = 0.0f;
 
     unsigned signv;  // 0x80000000 held in a VGPR on purpose (see check_row)
     asm volatile("v_mov_b32 %0, 0x80000000" : "=v"(signv));
-    for (int it = 0; it < T; ++it) {
-        float a_it;      // alpha[it] copied to a VGPR: VALU ops with an SGPR operand issue at half rate
-        asm volatile("v_mov_b32 %0, %1" : "=v"(a_it) : "s"(alpha.a[it]));
-        float tot[8];
-#pragma unroll
-        for (int bc = 0; bc < 8; ++bc) tot[bc] = S[bc] + yin[bc];
-        check_row<0, UP>(cv, tot, a_it, signv);
-        check_row<1, UP>(cv, tot, a_it, signv);
-        check_row<2, UP>(cv, tot, a_it, signv);
-        check_row<3, UP>(cv, tot, a_it, signv);
-        var_sums<UP>(cv, j, S);
+    // row it + 1 of the failed-frame form / slice it of the full trajectory
+    auto store_iteration = [&](int it) {
         if (ROWS || traj) {
             float *dst = ROWS ? traj + (fl * (long long)(T + 1) + it + 1) * 128 + j : traj + ((long long)it * B + fl) * 128 + j;
             if (live) {
@@ -302,16 +346,40 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 for (int bc = 0; bc < 8; ++bc) dst[bc * 16] = S[bc] + yout[bc];
             }
         }
+    };
+    float out[8];        // T == 0: the posterior is the channel value
+#pragma unroll
+    for (int bc = 0; bc < 8; ++bc) out[bc] = y[bc];
+    if (T > 0) {
+        // Iteration 1, peeled: cv = 0 and S = 0, so neither is filled or read.  The total keeps the one add of the loop,
+        // (+0) + yin: it turns a channel value of -0 into +0, and that sign is not lost afterwards -- vc = -0 would flip the
+        // sign of every zero message of its (wiped) check rows, sums of zero messages of one sign keep it, and "(-0) + yout"
+        // with yout = -0 is -0 where the loop gives +0.  So the add stays and the peeled iteration is the loop's, bit for bit.
+        float a_it;      // alpha[it] copied to a VGPR: VALU ops with an SGPR operand issue at half rate
+        asm volatile("v_mov_b32 %0, %1" : "=v"(a_it) : "s"(alpha.a[0]));
+        float tot[8];
+#pragma unroll
+        for (int bc = 0; bc < 8; ++bc) tot[bc] = 0.0f + yin[bc];
+        nms_iteration<UP, true>(cv, tot, a_it, signv);
+        var_sums<UP>(cv, j, S);
+        store_iteration(0);
+        for (int it = 1; it < T; ++it) {
+            asm volatile("v_mov_b32 %0, %1" : "=v"(a_it) : "s"(alpha.a[it]));
+#pragma unroll
+            for (int bc = 0; bc < 8; ++bc) tot[bc] = S[bc] + yin[bc];
+            nms_iteration<UP, false>(cv, tot, a_it, signv);
+            var_sums<UP>(cv, j, S);
+            store_iteration(it);
+        }
+        // (inside the T > 0 block: as "T > 0 ? S + yout : y" after it the choice was eight v_cndmask per wave)
+#pragma unroll
+        for (int bc = 0; bc < 8; ++bc) out[bc] = S[bc] + yout[bc];
     }
 
     if constexpr (ROWS) return;
-    float out[8];
     int h[8];
 #pragma unroll
-    for (int bc = 0; bc < 8; ++bc) {
-        out[bc] = (T > 0) ? S[bc] + yout[bc] : y[bc];
-        h[bc] = !(out[bc] > 0.0f);
-    }
+    for (int bc = 0; bc < 8; ++bc) h[bc] = !(out[bc] > 0.0f);
     if (soft && live) {
         float *dst = soft + fl * 128 + j;
 #pragma unroll
@@ -377,19 +445,19 @@ int launch_nms(ldpc_ctx *ctx, const float *d_llr, int64_t B, int T, const float 
     auto *hard = reinterpret_cast<unsigned long long *>(d_hard);
     if (kernel == LDPC_NMS_QC16) {
         const unsigned blocks = (unsigned)((B + 15) / 16);
-        if (d_rows) {
-            if (ctx->dpp_ror_up)
-                hipLaunchKernelGGL((nms_qc16_kernel<true, true>), dim3(blocks), dim3(256), 0, st, d_llr, (long long)B, T, a, w_in, w_out,
-                                   (float *)nullptr, d_rows, (unsigned long long *)nullptr, (unsigned char *)nullptr, d_index, d_count);
-            else
-                hipLaunchKernelGGL((nms_qc16_kernel<false, true>), dim3(blocks), dim3(256), 0, st, d_llr, (long long)B, T, a, w_in, w_out,
-                                   (float *)nullptr, d_rows, (unsigned long long *)nullptr, (unsigned char *)nullptr, d_index, d_count);
-        } else if (ctx->dpp_ror_up)
-            hipLaunchKernelGGL((nms_qc16_kernel<true, false>), dim3(blocks), dim3(256), 0, st, d_llr, (long long)B, T, a, w_in,
-                               w_out, d_soft, d_traj, hard, d_fail, (const int *)nullptr, (const int *)nullptr);
+        const bool unit = w_in == 1.0f && w_out == 1.0f;
+        void (*k)(const float *, long long, int, AlphaArg, float, float, float *, float *, unsigned long long *, unsigned char *, const int *,
+                  const int *);
+        if (d_rows) k = ctx->dpp_ror_up ? (unit ? nms_qc16_kernel<true, true, true> : nms_qc16_kernel<true, true, false>)
+                                        : (unit ? nms_qc16_kernel<false, true, true> : nms_qc16_kernel<false, true, false>);
+        else k = ctx->dpp_ror_up ? (unit ? nms_qc16_kernel<true, false, true> : nms_qc16_kernel<true, false, false>)
+                                 : (unit ? nms_qc16_kernel<false, false, true> : nms_qc16_kernel<false, false, false>);
+        if (d_rows)
+            hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, d_llr, (long long)B, T, a, w_in, w_out, (float *)nullptr, d_rows,
+                               (unsigned long long *)nullptr, (unsigned char *)nullptr, d_index, d_count);
         else
-            hipLaunchKernelGGL((nms_qc16_kernel<false, false>), dim3(blocks), dim3(256), 0, st, d_llr, (long long)B, T, a, w_in,
-                               w_out, d_soft, d_traj, hard, d_fail, (const int *)nullptr, (const int *)nullptr);
+            hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, d_llr, (long long)B, T, a, w_in, w_out, d_soft, d_traj, hard, d_fail,
+                               (const int *)nullptr, (const int *)nullptr);
     } else if (kernel == LDPC_NMS_GENERIC) {
         const size_t lds = sizeof(float) * 4 * ((size_t)c.E + 2 * (size_t)c.n);
         if (lds > 160 * 1024) return fail(LDPC_E_UNSUPPORTED, "code too large for the generic NMS kernel (%zu B of LDS)", lds);
