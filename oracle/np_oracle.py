@@ -383,6 +383,25 @@ def _weighted_distance_k(disc_bits, w, k):
     return acc
 
 
+def weighted_distance_rows(disc, w, k):
+    """``_weighted_distance_k`` of every row of disc [N, n] at once: the same float32 additions in the same order (a row
+    adds w[p] where its bit is set and is left alone elsewhere), so each result has the bits of the per-row loop."""
+    disc = np.asarray(disc).astype(bool)
+    w = np.asarray(w, dtype=F32)
+    n = w.shape[0]
+    acc = np.zeros(disc.shape[0], dtype=F32)
+    for p in range(k):
+        acc = np.where(disc[:, p], acc + w[p], acc).astype(F32)
+    p = k
+    while p < n:
+        part = np.zeros(disc.shape[0], dtype=F32)
+        for q in range(p, min(p + 8, n)):
+            part = np.where(disc[:, q], part + w[q], part).astype(F32)
+        acc = (acc + part).astype(F32)
+        p += 8
+    return acc
+
+
 def exact_distance(disc_bits, w):
     return float(np.dot(np.asarray(disc_bits, dtype=np.float64), np.asarray(w, dtype=np.float64)))
 
@@ -403,7 +422,7 @@ def convention_osd(yp, labelp, Gp, order, teps=None):
     cand = ((teps + hard[None, :k]) % 2).dot(Gp) % 2
     disc = (cand + hard[None, :]) % 2
     w = np.abs(yp)
-    cost = np.array([_weighted_distance_k(d, w, k) for d in disc], dtype=F32)
+    cost = weighted_distance_rows(disc, w, k)
     best = int(np.argmin(cost))
     correct = bool(np.array_equal(cand[best], np.asarray(labelp)))
     phase = -1

@@ -27,6 +27,12 @@ def failures(dec):
     return y[idx], cw[idx]
 
 
+def _best_without_quirk(ref):
+    """quirk = 0 returns the tau_e candidate itself: ``best`` is then its rank in visit order, num_teps - 1 (the order-0
+    candidate is rank 0); on a frame without such a stop it is the winner's rank, as with the quirk."""
+    return np.where(ref["hit"], ref["num_teps"] - 1, ref["best_index"])
+
+
 @pytest.mark.parametrize("order", [1, 2, 3])
 def test_fs_matches_oracle(dec, failures, order):
     from short_ldpc_decoding_osd_amd import _lib
@@ -46,6 +52,8 @@ def test_fs_matches_oracle(dec, failures, order):
         assert np.array_equal(out["metric"].cpu().numpy(), want_m)
         if quirk:
             assert np.array_equal(out["best"].cpu().numpy(), ref["best_index"])
+        else:
+            assert np.array_equal(out["best"].cpu().numpy(), _best_without_quirk(ref))
 
 
 def test_fs_tau_e_hits_and_thresholds(dec, failures):
@@ -64,5 +72,6 @@ def test_fs_tau_e_hits_and_thresholds(dec, failures):
             want_cw = ref["codeword_ref"] if quirk else ref["codeword_hit"]
             assert np.array_equal(words_np(out["cw"]), pack_np(want_cw))
             assert np.array_equal(out["metric"].cpu().numpy(), ref["metric_ref"] if quirk else ref["metric_hit"])
+            assert np.array_equal(out["best"].cpu().numpy(), ref["best_index"] if quirk else _best_without_quirk(ref))
         if tau_e > 10:
             assert ref["hit"].any()
