@@ -352,13 +352,16 @@ int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label
                     const int32_t *d_count, const int32_t *d_ntep, int64_t F, int64_t *d_counts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
- * OSD for short codes of any shape: the front end (swapped_info / identify_mrb / full_gf2elim,
- * PB_OSD/pb_testing.py:231-320) and the conventional order-p search (convention_osd_main,
- * FS_OSD/convention_osd.py:49-76) for every code with 1 <= k <= 64 and 1 <= n-k <= 64 (hence n <= 128): the
+ * OSD for short codes of any shape, i.e. every code with 1 <= k <= 64 and 1 <= n-k <= 64 (hence n <= 128): the
  * reference's (96,48) and (121,60) alist codes, and (128,64) itself, where the results equal those of the entry
- * points above bit for bit.  Everything else of this header that says OSD -- FS-OSD, PB-OSD, the elimination and
- * one-TEP primitives, the H-form primitives, the one-call pipeline and ldpc_osd_params with its flags -- stays with
- * (n = 128, k = 64) and keeps answering LDPC_E_UNSUPPORTED on other shapes.
+ * points above bit for bit.  Served:
+ *   the front end               swapped_info / identify_mrb / full_gf2elim, PB_OSD/pb_testing.py:231-320
+ *   the conventional search     convention_osd_main, FS_OSD/convention_osd.py:49-76, orders 0..3
+ *   FS-OSD                      fs_osd, FS_OSD/fs_testing.py:129-161, orders 0..min(3, k)
+ *   one given TEP per frame     one_tep_compare, FS_OSD/fs_testing.py:51-64
+ * Everything else of this header that says OSD -- PB-OSD, the elimination primitive, the H-form primitives, the
+ * one-call pipeline, the LDPC_OSD_F_* flags, d_aux and y_frames of ldpc_osd_params, and the entry points above
+ * themselves -- stays with (n = 128, k = 64) and keeps answering LDPC_E_UNSUPPORTED on other shapes.
  * Same rules as above for d_index / d_count (min(*d_count, F) frames, read on the device; nothing at or beyond that
  * frame is written), for ties of the sort (lower index first), the TEP table (the one of this code's k, orders 0..3,
  * first minimum) and the float order of the metric: flipped MRB weights ascending from 0.0f, then bytes of eight
@@ -371,13 +374,22 @@ int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label
  *   d_metric  [F] f32, d_best [F] i32 (index into the table), d_ntep [F] i32: nullable, each on its own
  *   d_label_bits [*][ceil(n/64)] u64 addressed through d_index, d_counts[3] += {frames, frames_wrong, teps_total}
  *             as the counting entry point above does: both or neither (nullable); teps_total moves only with d_ntep
- * The decode entry point is two launches through the caller's d_perm / d_parity, which are scratch AND outputs and
+ * The decode entry points are two launches through the caller's d_perm / d_parity, which are scratch AND outputs and
  * required: there is no library workspace and no per-stream state.  Before any launch: an unsupported shape is
- * LDPC_E_UNSUPPORTED (the message names the limits and the code's (n,k)), an order outside 0..3 and a NULL in a
- * required pointer are LDPC_E_ARG, F == 0 is LDPC_OK.  The tables (G columns, the order-3 TEP table of k) are
- * uploaded by ldpc_ctx_create; nothing is allocated and nothing synchronises in a call (graph-capturable).
+ * LDPC_E_UNSUPPORTED (the message names the limits and the code's (n,k)), an order outside its range and a NULL in a
+ * required pointer are LDPC_E_ARG, F == 0 is LDPC_OK.  The tables (G columns, the order-3 TEP table and the FS visit
+ * order of k) are uploaded by ldpc_ctx_create; nothing is allocated and nothing synchronises in a call
+ * (graph-capturable).
+ * The FS entry points read `params` for order, algo, fs_beta, fs_tau_e, fs_tau_psc and fs_reference_quirk, with the
+ * meaning they have in ldpc_osd_decode: the lower bound of weight w is the sum of the w least reliable MRB |y'|
+ * (positions k-w .. k-1, ascending from 0.0f) plus (float)((double)fs_beta * (n-k)); d_best is the rank in visit
+ * order (0 = the all-zero TEP), d_ntep is num_teps (:141); with fs_reference_quirk = 0 a tau_e stop returns the
+ * stopping candidate, its own metric and its rank.  LDPC_E_ARG, naming the offender, for algo != LDPC_OSD_FS, an
+ * order outside 0..min(3, k) (the bound has no meaning for w > k), flags != 0, d_aux != NULL and y_frames != 0.
+ * The one-TEP entry point is ldpc_osd_tep_eval with the split at k: d_mask [F] u64, bit p < k flips MRB position p
+ * (bits at or beyond k are ignored); d_cw [F][ceil(n/64)] u64; d_metric [F] f32 and d_hd [F] i32 are nullable.
  * ------------------------------------------------------------------------------------- */
-int ldpc_osdx_supported(const ldpc_ctx *ctx); /* 1: the three entry points below serve this code; 0: they refuse it */
+int ldpc_osdx_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
 int ldpc_osdx_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
                     uint8_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, void *stream);
 int ldpc_osdx_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
@@ -386,6 +398,17 @@ int ldpc_osdx_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, co
 int ldpc_osdx_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
                      int32_t order, uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw, float *d_metric,
                      int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits, int64_t *d_counts, void *stream);
+
+int ldpc_osdx_fs_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *params, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, void *stream);
+int ldpc_osdx_fs_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const ldpc_osd_params *params, uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits,
+                        int64_t *d_counts, void *stream);
+int ldpc_osdx_tep_eval(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                       const uint8_t *d_perm, const uint64_t *d_parity, const uint64_t *d_mask, uint64_t *d_cw,
+                       float *d_metric, int32_t *d_hd, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H):

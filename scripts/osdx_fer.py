@@ -1,14 +1,21 @@
 """NMS + order-p OSD of any short code (1 <= k <= 64, 1 <= n-k <= 64): FER before and after the OSD, and the two OSD kernels timed.
 
     python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2
+    python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2 \
+        --osd fs --tau-e 4.5
 
 Frame generator -> ldpc_nms_decode -> ldpc_compact -> ldpc_osdx_decode on the failures (the reference's loop: NMS, then
 convention_osd_main on the frames with a non-zero syndrome).  Times are HIP events around --calls back-to-back launches on the
 failures of the whole batch, after a warm-up, --repeats times (every repeat is printed: their spread is the noise).  On a
 (128,64) code the specialised osd_front_kernel and the table-scan osd_search_kernel are timed on the same frames in the same run.
+--osd fs: the search is FS-OSD (ldpc_osdx_fs_decode; fs_osd, FS_OSD/fs_testing.py:129-161) with --beta, --tau-e (floor((d_min - 1) / 2)
+as the reference evaluates it: required for an alist, whose d_min the script cannot know; 6.5 for the packaged CCSDS code) and
+--tau-psc.  Printed then: mean and maximum TEPs per frame next to the size of the order-p table, osdx_fs_kernel timed like the other
+legs and, on a (128,64) code, osd_fs_kernel through ldpc_osd_search on the same frames.
 One JSON line at the end."""
 import argparse
 import json
+import math
 import os
 import sys
 
@@ -18,7 +25,7 @@ sys.path.insert(0, ROOT)
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
 
-from short_ldpc_decoding_osd_amd import Code                    # noqa: E402
+from short_ldpc_decoding_osd_amd import Code, _lib              # noqa: E402
 from short_ldpc_decoding_osd_amd.runtime import Decoder         # noqa: E402
 
 
@@ -67,7 +74,16 @@ def main(argv=None):
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--osd", choices=("conv", "fs"), default="conv", help="the search: the conventional table scan, or FS-OSD")
+    ap.add_argument("--beta", type=float, default=0.1, help="FS-OSD: beta of the lower bound (Main_FS_OSD.py:20)")
+    ap.add_argument("--tau-e", type=float, default=None, help="FS-OSD: the stop threshold on the Hamming distance")
+    ap.add_argument("--tau-psc", type=float, default=30.0, help="FS-OSD: tau_psc (FS_OSD/globalmap.py:50)")
     args = ap.parse_args(argv)
+    fs = args.osd == "fs"
+    if fs and args.tau_e is None:
+        if args.alist:
+            ap.error("--osd fs needs --tau-e for an alist code (there is no default d_min)")
+        args.tau_e = 6.5
 
     dec = Decoder(Code(args.alist) if args.alist else Code(), 0)
     if not dec.osdx_supported:
@@ -81,7 +97,11 @@ def main(argv=None):
     nf = int(count.cpu()[0])
     idx = index[:max(nf, 1)].contiguous()
     counts = torch.zeros(3, dtype=torch.int64, device=dec.device)
-    out = dec.osdx_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
+    if fs:
+        fsp = dec.osd_params(args.order, _lib.OSD_FS, fs_beta=args.beta, fs_tau_e=args.tau_e, fs_tau_psc=args.tau_psc)
+        out = dec.osdx_fs_decode(y, fsp, index=idx, count=count, label_bits=labels, counts=counts)
+    else:
+        out = dec.osdx_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
     torch.cuda.synchronize()
     nc = nms_counts.cpu().tolist()
     oc = counts.cpu().tolist()
@@ -90,17 +110,30 @@ def main(argv=None):
     fer_osd = (nc[3] + oc[1]) / B
     print(f"({dec.n},{dec.k}) {args.snr} dB, {B} frames, NMS-{args.T}: FER {fer_nms:.3e} ({nc[1]} wrong, {nf} with a non-zero syndrome, "
           f"{nc[3]} undetected)", flush=True)
-    print(f"  order-{args.order} OSD on the {nf} failures: FER {fer_osd:.3e} ({oc[1]} still wrong, {oc[2] // max(oc[0], 1)} TEPs per frame)",
-          flush=True)
     result = dict(n=dec.n, k=dec.k, snr_db=args.snr, frames=B, T=args.T, order=args.order, failures=nf, fer_nms=fer_nms, fer_osd=fer_osd,
                   kernels={})
+    if fs:
+        table = sum(math.comb(dec.k, w) for w in range(args.order + 1))
+        ntep = out["ntep"][:nf].to(torch.float64)
+        mean, most = (float(ntep.mean()), int(ntep.max())) if nf else (0.0, 0)
+        print(f"  order-{args.order} FS-OSD (beta {args.beta}, tau_e {args.tau_e}, tau_psc {args.tau_psc}) on the {nf} failures: FER {fer_osd:.3e} "
+              f"({oc[1]} still wrong); TEPs per frame: mean {mean:.1f}, max {most}, table {table}", flush=True)
+        result.update(osd="fs", beta=args.beta, tau_e=args.tau_e, tau_psc=args.tau_psc, teps_mean=mean, teps_max=most, teps_table=table)
+    else:
+        print(f"  order-{args.order} OSD on the {nf} failures: FER {fer_osd:.3e} ({oc[1]} still wrong, {oc[2] // max(oc[0], 1)} TEPs per frame)",
+              flush=True)
     if nf == 0:
         print(json.dumps(result), flush=True)
         return 0
     front = (out["perm"], out["parity"], None)
     legs = [("osdx_front_kernel", lambda: dec.osdx_front(y, index=idx, count=count, out=front)),
             ("osdx_search_kernel", lambda: dec.osdx_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=out))]
-    if (dec.n, dec.k) == (128, 64):                      # the specialised kernels on the same frames, in the same run
+    if fs:
+        legs[1] = ("osdx_fs_kernel", lambda: dec.osdx_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out))
+        if (dec.n, dec.k) == (128, 64):                  # the specialised kernel on the same front-end results, in the same run
+            out2 = dec.osd_search(y, out["perm"], out["parity"], fsp, index=idx, count=count)
+            legs.append(("osd_fs_kernel", lambda: dec.osd_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out2)))
+    elif (dec.n, dec.k) == (128, 64):                      # the specialised kernels on the same frames, in the same run
         p = dec.osd_params(args.order, table_scan=True)
         perm2, par2, ns2 = dec.osd_front(y, index=idx, count=count)
         out2 = dec.osd_search(y, perm2, par2, p, index=idx, count=count)

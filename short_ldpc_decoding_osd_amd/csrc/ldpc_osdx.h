@@ -5,6 +5,8 @@
 // Layout of a frame on the wavefront: lane l owns sorted column l (live for l < k) and sorted column k + l (live for
 // l < n - k); idle slots carry zero columns, zero weights and zero rows, so every ballot, XOR reduction and LUT sum of the
 // (128,64) kernels keeps its meaning with the split at k.  The helpers of ldpc_wave.h / ldpc_search.h are used unchanged.
+// osdx_prepare / osdx_finish are the per-frame prologue and epilogue every search on such front-end results shares (the FS scan
+// and the one-TEP kernel: ldpc_osdx_fs.h).
 #pragma once
 
 #include "ldpc_search.h"
@@ -136,6 +138,63 @@ __global__ __launch_bounds__(64) void osdx_front_kernel(const float *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------
+// per-frame prologue and epilogue of every search on front-end results of any shape (search_prepare / search_finish of
+// ldpc_search.h with the split at k).  Idle lanes (lane >= k, lane >= n - k) stay out of the hard-decision ballots -- their
+// y = 0 would count as a hard 1 --, rows of P' are masked to n - k columns, and w[] is zero beyond the live positions.
+//   LDS: SearchLds (LUTS = true: the eight byte LUTs over w[64..] are built) or SearchLdsLean (LUTS = false).
+// ---------------------------------------------------------------------------------------
+struct OsdxFrame {
+    u64 hm, hp, d0;       // hard decisions (y' > 0 ? 0 : 1) of the MRB / the parity part, order-0 discrepancy
+    int o1, o2;           // original bit of primed positions lane / k + lane
+    bool live1, live2;    // lane < k, lane < n - k
+};
+
+template <bool LUTS = true, class LDS = SearchLds>
+__device__ __forceinline__ OsdxFrame osdx_prepare(LDS &L, const float *__restrict__ y, long long src, const unsigned char *__restrict__ perm_in,
+                                                  const u64 *__restrict__ parity_in, long long f, int n, int k, int lane)
+{
+    OsdxFrame S;
+    const int m = n - k;
+    const u64 colmask = m >= 64 ? ~0ull : ((1ull << m) - 1ull);
+    S.live1 = lane < k; S.live2 = lane < m;
+    S.o1 = perm_in[f * 128 + lane]; S.o2 = perm_in[f * 128 + k + lane];   // (k + lane <= 127)
+    const float y1 = S.live1 ? y[src * n + S.o1] : 0.0f, y2 = S.live2 ? y[src * n + S.o2] : 0.0f;
+    L.w[lane] = __builtin_fabsf(y1);
+    L.w[lane + 64] = __builtin_fabsf(y2);
+    const u64 Prow = S.live1 ? (parity_in[f * 64 + lane] & colmask) : 0ull;
+    L.P[lane] = Prow;
+    if (lane < 2) L.cw[lane] = 0;
+    S.hm = __ballot(S.live1 && !(y1 > 0.0f));
+    S.hp = __ballot(S.live2 && !(y2 > 0.0f));
+    wave_fence();
+    if constexpr (LUTS) build_byte_luts<8>(L.lut, &L.w[64], lane);
+    // d0 = (u0 . P') ^ h_parity : XOR-reduce the rows selected by the MRB hard decisions
+    S.d0 = wave_xor64(((S.hm >> lane) & 1) ? Prow : 0ull) ^ S.hp;
+    wave_fence();
+    return S;
+}
+
+// candidate (E = flipped MRB positions, D = parity discrepancy) -> codeword in ORIGINAL bit order, ceil(n / 64) words; L.cw
+// holds it afterwards (the callers compare it with the label before their closing wave_fence)
+template <class LDS>
+__device__ __forceinline__ void osdx_finish(LDS &L, const OsdxFrame &S, u64 E, u64 D, long long f, int words, int lane, u64 *__restrict__ cw_out)
+{
+    const u64 mrb_bits = S.hm ^ E, par_bits = D ^ S.hp;
+    if (S.live1 && ((mrb_bits >> lane) & 1)) atomicOr(&L.cw[S.o1 >> 6], 1ull << (S.o1 & 63));
+    if (S.live2 && ((par_bits >> lane) & 1)) atomicOr(&L.cw[S.o2 >> 6], 1ull << (S.o2 & 63));
+    wave_fence();
+    if (lane < words) cw_out[f * words + lane] = L.cw[lane];
+}
+
+template <class LDS>
+__device__ __forceinline__ bool osdx_wrong(const LDS &L, const u64 *__restrict__ label, long long src, int words)
+{
+    bool bad = false;
+    for (int w = 0; w < words; ++w) bad |= L.cw[w] != label[src * words + w];
+    return bad;
+}
+
+// ---------------------------------------------------------------------------------------
 // conventional order-p search over the reference's TEP table for THIS k (the scan of osd_search_kernel, split at k)
 //   SearchLds: w[0..k-1] = |y'| of the MRB, w[64..64+n-k-1] = |y'| of the parity part, zero elsewhere; the eight byte LUTs
 //   then hold the sums of np_oracle._weighted_distance_k (bytes of eight positions from primed position k, each ascending
@@ -151,28 +210,14 @@ __global__ __launch_bounds__(64) void osdx_search_kernel(const float *__restrict
 {
     __shared__ SearchLds L;   // one wavefront per workgroup: compile-time LDS base for the LUT reads
     const int lane = threadIdx.x;
-    const int m = n - k, words = (n + 63) >> 6;
-    const u64 colmask = m >= 64 ? ~0ull : ((1ull << m) - 1ull);
+    const int words = (n + 63) >> 6;
     const long long nframes = frame_count(count, F);
     unsigned long long seen = 0, wrong = 0, nteps = 0;
 
     for (long long f = blockIdx.x; f < nframes; f += gridDim.x) {
         const long long src = index ? index[f] : f;
-        const bool live1 = lane < k, live2 = lane < m;
-        const int o1 = perm_in[f * 128 + lane], o2 = perm_in[f * 128 + k + lane];   // (k + lane <= 127)
-        const float y1 = live1 ? y[src * n + o1] : 0.0f, y2 = live2 ? y[src * n + o2] : 0.0f;
-        L.w[lane] = __builtin_fabsf(y1);
-        L.w[lane + 64] = __builtin_fabsf(y2);
-        const u64 Prow = live1 ? (parity_in[f * 64 + lane] & colmask) : 0ull;
-        L.P[lane] = Prow;
-        if (lane < 2) L.cw[lane] = 0;
-        const u64 hm = __ballot(live1 && !(y1 > 0.0f));   // hard decisions (y' > 0 ? 0 : 1) of the MRB / the parity part
-        const u64 hp = __ballot(live2 && !(y2 > 0.0f));
-        wave_fence();
-        build_byte_luts<8>(L.lut, &L.w[64], lane);
-        // d0 = (u0 . P') ^ h_parity : XOR-reduce the rows selected by the MRB hard decisions
-        const u64 d0 = wave_xor64(((hm >> lane) & 1) ? Prow : 0ull) ^ hp;
-        wave_fence();
+        const OsdxFrame S = osdx_prepare(L, y, src, perm_in, parity_in, f, n, k, lane);
+        const u64 d0 = S.d0;
         // scan the TEP table, one TEP per lane per round; strict '<' keeps the first minimum
         float best = __builtin_inff();
         int bestt = 0x7FFFFFFF;
@@ -190,18 +235,9 @@ __global__ __launch_bounds__(64) void osdx_search_kernel(const float *__restrict
             if ((trip & 7) == 0) bound = wave_min_f32(best);
         }
         wave_argmin(best, bestt, bestD, bestE, lane);
-        // candidate -> codeword in ORIGINAL bit order
-        const u64 mrb_bits = hm ^ bestE, par_bits = bestD ^ hp;
-        if (live1 && ((mrb_bits >> lane) & 1)) atomicOr(&L.cw[o1 >> 6], 1ull << (o1 & 63));
-        if (live2 && ((par_bits >> lane) & 1)) atomicOr(&L.cw[o2 >> 6], 1ull << (o2 & 63));
-        wave_fence();
-        if (lane < words) cw_out[f * words + lane] = L.cw[lane];
+        osdx_finish(L, S, bestE, bestD, f, words, lane, cw_out);
         store_results(f, lane, best, bestt, ntep, metric_out, best_out, ntep_out);
-        if (label) {
-            bool bad = false;
-            for (int w = 0; w < words; ++w) bad |= L.cw[w] != label[src * words + w];
-            seen += 1; wrong += bad; nteps += ntep_out ? (unsigned long long)ntep : 0ull;
-        }
+        if (label) { seen += 1; wrong += osdx_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
         wave_fence();
     }
     if (label && lane == 0 && seen) {

@@ -313,7 +313,7 @@ class Decoder:
     # ------------------------------------------------------------------ OSD for short codes of any shape
     @property
     def osdx_supported(self):
-        """Whether ``osdx_front`` / ``osdx_search`` / ``osdx_decode`` serve this code (1 <= k <= 64 and 1 <= n-k <= 64)."""
+        """Whether the ``osdx_*`` methods serve this code (1 <= k <= 64 and 1 <= n-k <= 64)."""
         return bool(self.L.ldpc_osdx_supported(self._ctx))
 
     def _osdx_outputs(self, out, F):
@@ -364,6 +364,49 @@ class Decoder:
                                            _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
                                            _ptr(label_bits), _ptr(counts), self._stream()), "ldpc_osdx_decode")
         out["perm"], out["parity"] = perm, parity
+        return out
+
+    def osdx_fs_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
+        """FS-OSD on front-end results of any supported shape.  ``params``: ``osd_params(order, _lib.OSD_FS, fs_beta=...,
+        fs_tau_e=..., fs_tau_psc=..., fs_reference_quirk=...)``, order 0..min(3, k).  Returns the dict of ``osdx_search``
+        (best: rank in visit order, 0 = the all-zero TEP; ntep: num_teps)."""
+        self._chk(y, torch.float32, (self.n,), "y")
+        self._chk(perm, torch.uint8, (128,), "perm")
+        self._chk(parity, torch.int64, (64,), "parity")
+        F = perm.shape[0] if F is None else F
+        out = self._osdx_outputs(out, F)
+        _lib.check(self.L.ldpc_osdx_fs_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
+                                              C.byref(params), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
+                                              _ptr(out["ntep"]), self._stream()), "ldpc_osdx_fs_search")
+        return out
+
+    def osdx_fs_decode(self, y, params, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
+                       out=None):
+        """Front end + FS-OSD of the frames y[index[f]] (or y[f]) for any supported shape: ``osdx_decode`` with the search
+        of ``osdx_fs_search``; ``perm`` / ``parity`` / ``label_bits`` / ``counts`` as there."""
+        self._chk(y, torch.float32, (self.n,), "y")
+        F = (index.shape[0] if index is not None else y.shape[0]) if F is None else F
+        perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
+        parity = self.empty((F, 64), torch.int64) if parity is None else self._chk(parity, torch.int64, (64,), "parity")
+        out = self._osdx_outputs(out, F)
+        _lib.check(self.L.ldpc_osdx_fs_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, C.byref(params), _ptr(perm),
+                                              _ptr(parity), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
+                                              _ptr(out["ntep"]), _ptr(label_bits), _ptr(counts), self._stream()),
+                   "ldpc_osdx_fs_decode")
+        out["perm"], out["parity"] = perm, parity
+        return out
+
+    def osdx_tep_eval(self, y, perm, parity, mask, index=None, count=None):
+        """``osd_tep_eval`` for any supported shape (mask [F] int64: bit p < k flips primed MRB position p).
+        Returns dict(cw[F,words] int64 original bit order, metric[F] f32, hd[F] i32)."""
+        self._chk(y, torch.float32, (self.n,), "y")
+        self._chk(perm, torch.uint8, (128,), "perm")
+        self._chk(parity, torch.int64, (64,), "parity")
+        self._chk(mask, torch.int64, (), "mask")
+        F = perm.shape[0]
+        out = dict(cw=self.empty((F, self.words), torch.int64), metric=self.empty((F,), torch.float32), hd=self.empty((F,), torch.int32))
+        _lib.check(self.L.ldpc_osdx_tep_eval(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(mask),
+                                             _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["hd"]), self._stream()), "ldpc_osdx_tep_eval")
         return out
 
     # ------------------------------------------------------------------ H-form OSD (DL-OSD stage)
