@@ -10,8 +10,6 @@ int osd_ctx_init(ldpc_ctx *ctx);      // ldpc_osd.hip
 void osd_ctx_release(ldpc_ctx *ctx);  // ldpc_osd.hip
 int hosd_ctx_init(ldpc_ctx *ctx);     // ldpc_hosd.hip
 void hosd_ctx_release(ldpc_ctx *ctx); // ldpc_hosd.hip
-int osdx_ctx_init(ldpc_ctx *ctx);     // ldpc_osdx.hip
-void osdx_ctx_release(ldpc_ctx *ctx); // ldpc_osdx.hip
 }  // namespace ldpc
 
 template <typename T>
@@ -49,6 +47,13 @@ int ldpc_ctx_create(const ldpc_code *code, int32_t device, ldpc_ctx **out)
         if ((rc = upload(code->chk_var, &ctx->d_chk_var))) break;
         if ((rc = upload(code->var_ptr, &ctx->d_var_ptr))) break;
         if ((rc = upload(code->var_edge, &ctx->d_var_edge))) break;
+        {   // the OSD tables of every shape they exist for (ldpc_osd_tables.h); osd_ctx_init finds them in place
+            OsdTables &t = ctx->osd_tables;
+            OsdTablesHost host;
+            if ((rc = pack_osd_tables(ctx->code, t, host))) break;
+            if (t.k && ((rc = upload(host.Gcols, &t.d_Gcols)) || (rc = upload(host.tep, &t.d_tep)) ||
+                        (rc = upload(host.tep_fs, &t.d_tep_fs)))) break;
+        }
         if ((rc = probe_dpp(&ctx->dpp_ror_up, &ctx->dpp_wave_rol_dir))) break;
         // event pool of ldpc_pipeline_run's timing slots: created (and recorded once: the first record of an
         // event sets up its signal and is slow) here, so that decode calls never create anything.  The warm-up
@@ -67,7 +72,6 @@ int ldpc_ctx_create(const ldpc_code *code, int32_t device, ldpc_ctx **out)
         if (rc) break;
         if ((rc = osd_ctx_init(ctx))) break;
         if ((rc = hosd_ctx_init(ctx))) break;
-        if ((rc = osdx_ctx_init(ctx))) break;
     } while (0);
     (void)hipSetDevice(prev);
     if (rc) { ldpc_ctx_destroy(ctx); return rc; }
@@ -80,7 +84,7 @@ void ldpc_ctx_destroy(ldpc_ctx *ctx)
     if (!ctx) return;
     osd_ctx_release(ctx);
     hosd_ctx_release(ctx);
-    osdx_ctx_release(ctx);
+    (void)hipFree(ctx->osd_tables.d_Gcols); (void)hipFree(ctx->osd_tables.d_tep); (void)hipFree(ctx->osd_tables.d_tep_fs);
     (void)hipFree(ctx->d_chk_ptr); (void)hipFree(ctx->d_chk_var);
     (void)hipFree(ctx->d_var_ptr); (void)hipFree(ctx->d_var_edge);
     if (ctx->timing) {

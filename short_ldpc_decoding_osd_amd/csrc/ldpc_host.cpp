@@ -233,6 +233,46 @@ int64_t tep_table_fs(int k, int w, uint8_t *supports)
     return total;
 }
 
+// [count][3] supports, 0xFF padded -> (i, j, l, weight) entries appended to `out`
+static void pack_supports(const std::vector<uint8_t> &sup, std::vector<uchar4> &out)
+{
+    for (size_t t = 0; t < sup.size() / 3; ++t) {
+        uint8_t e[3];
+        int w = 0;
+        for (int q = 0; q < 3; ++q) { e[q] = sup[3 * t + q] == 0xFF ? 0 : sup[3 * t + q]; w += sup[3 * t + q] != 0xFF; }
+        uchar4 v;
+        v.x = e[0]; v.y = e[1]; v.z = e[2]; v.w = (uint8_t)w;
+        out.push_back(v);
+    }
+}
+
+int pack_osd_tables(const ldpc_code &c, OsdTables &t, OsdTablesHost &host)
+{
+    t = OsdTables();
+    host = OsdTablesHost();
+    if (c.k < 1 || c.k > 64 || c.n - c.k < 1 || c.n - c.k > 64 || c.G.size() != (size_t)c.k * c.n) return LDPC_OK;
+    host.Gcols.assign(c.n, 0);
+    for (int r = 0; r < c.k; ++r)
+        for (int v = 0; v < c.n; ++v)
+            if (c.G[(size_t)r * c.n + v]) host.Gcols[v] |= 1ull << r;
+    // one table for order 3; orders 0..2 are its prefixes (weight classes are concatenated)
+    int64_t total = tep_table(c.k, 3, nullptr, t.ntep);
+    if (total < 0) return (int)total;
+    std::vector<uint8_t> sup((size_t)total * 3);
+    if ((total = tep_table(c.k, 3, sup.data(), nullptr)) < 0) return (int)total;
+    pack_supports(sup, host.tep);
+    // FS-OSD visit order (generate_sequential_teps, fs_testing.py:32-49), supports stored ascending
+    for (int w = 1; w <= 3 && w <= c.k; ++w) {
+        int64_t cnt = tep_table_fs(c.k, w, nullptr);
+        if (cnt < 0) return (int)cnt;
+        sup.assign((size_t)cnt * 3, 0);
+        if ((cnt = tep_table_fs(c.k, w, sup.data())) < 0) return (int)cnt;
+        t.fs_off[w] = (int)host.tep_fs.size(); t.fs_cnt[w] = (int)cnt;
+        pack_supports(sup, host.tep_fs);
+    }
+    t.n = c.n; t.k = c.k;
+    return LDPC_OK;
+}
 
 // osd.error_pattern_gen (DL_OSD_Testing_serial/ordered_statistics_decoding.py:81-98): product over
 // the segments (leftmost slowest) of the lexicographic combinations inside each segment

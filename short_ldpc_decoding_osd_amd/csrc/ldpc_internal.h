@@ -1,21 +1,36 @@
-// Internal declarations shared by the translation units of libldpcosd.so (not installed).
+// Internal declarations shared by the translation units of libldpcosd.so (not installed): error reporting (fail, LDPC_HIP,
+// first_null), the code and the context (which owns the OSD tables of ldpc_osd_tables.h), the host helpers and the launchers.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/ldpc_osd.h"
+#include "ldpc_osd_tables.h"
 
 namespace ldpc {
 
 // thread-local error text behind ldpc_last_error()
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int hip_fail(hipError_t e, const char *what);
+
+// "<who>: <name> is NULL" (LDPC_E_ARG) for the first NULL among the required pointers, in the order given; LDPC_OK if none is
+struct NamedPtr {
+    const char *name;
+    const void *ptr;
+};
+inline int first_null(const char *who, std::initializer_list<NamedPtr> required)
+{
+    for (const NamedPtr &r : required)
+        if (!r.ptr) return fail(LDPC_E_ARG, "%s: %s is NULL", who, r.name);
+    return LDPC_OK;
+}
 
 #define LDPC_HIP(call)                                      \
     do {                                                    \
@@ -53,16 +68,13 @@ struct ldpc_ctx {
     ldpc_code code;
     // generic NMS tables
     int32_t *d_chk_ptr = nullptr, *d_chk_var = nullptr, *d_var_ptr = nullptr, *d_var_edge = nullptr;
-    // OSD constants (n = 128, k = 64 only)
-    uint64_t *d_Gcols = nullptr;   // [128] column v of G as a 64-bit word (bit r = G[r][v])
-    uint8_t *d_tep = nullptr;      // TEP supports, order <= 3: [43745][4] (i, j, l, weight)
+    ldpc::OsdTables osd_tables;    // G columns and TEP tables of any shape with k, n-k <= 64: read by every OSD family
     uint64_t *d_Hcols = nullptr;   // [128] column v of H as a 64-bit word (bit r = H[r][v]); n = 128, m = 64 only
     bool dpp_ror_up = true;        // probed: row_ror:n moves data towards higher lanes
     int dpp_wave_rol_dir = 0;      // probed: wave_rol:1 -- +1 lane j receives lane j-1, -1 lane j+1, 0 unusable
     bool osd_ok = false;
     bool hosd_ok = false;
-    void *osd_state = nullptr;     // ldpc::OsdState (TEP tables; per-stream workspaces behind its mutex)
-    void *osdx_state = nullptr;    // ldpc::OsdxState (ldpc_osdx.hip): G columns and TEP table of any shape with k, n-k <= 64
+    void *osd_state = nullptr;     // ldpc::OsdState ((128,64) constants; per-stream workspaces behind its mutex)
     hipEvent_t *timing = nullptr;  // [LDPC_TIMING_SLOTS][6] events of ldpc_pipeline_run, created with the context
     unsigned timing_recorded[LDPC_TIMING_SLOTS] = {};   // bit i: event i of the slot was recorded by the last run that used it
 };
@@ -74,6 +86,7 @@ int gf2elim(int32_t *M, int m, int n, std::vector<int32_t> *swaps);  // returns 
 int build_code(ldpc_code &c);  // fills G, graph tables, qc flag from c.H/m/n
 int64_t tep_table(int k, int order, uint8_t *supports, int64_t *boundaries);
 int64_t tep_table_fs(int k, int w, uint8_t *supports);
+// (pack_osd_tables, which packs both into the context's tables: ldpc_osd_tables.h)
 int64_t hosd_pattern_teps(int nseg, const int32_t *bounds, const int32_t *pattern, uint8_t *teps);
 
 // launchers (one per .hip file)

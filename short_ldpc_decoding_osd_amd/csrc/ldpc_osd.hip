@@ -1,5 +1,6 @@
 // Ordered-statistics decoding for (128,64) codes on gfx950 (MI355X): the translation unit of the conventional and FS side.
-// Here: the host side (context, per-stream workspace, validation, route selection, osd_launch, the entry points).
+// Here: the host side (the (128,64) constants of a context, per-stream workspace, validation, route selection, osd_launch, fs_params,
+// the entry points).  G columns and TEP tables: the context's OsdTables (ldpc_osd_tables.h), shared with ldpc_osdx.hip.
 // Reference (paths relative to LDPC_128/ of the reference):
 //   swapped_info / identify_mrb / full_gf2elim   PB_OSD/pb_testing.py:231-320 (== FS_OSD/fs_testing.py:233-322)
 //   generate_teps / convention_osd_main           FS_OSD/convention_osd.py:13-76
@@ -25,50 +26,15 @@
 namespace ldpc {
 
 // ---------------------------------------------------------------------------------------
-// context pieces: G columns, TEP table (order <= 3), front-end workspace
+// context pieces: the constants of the (128,64) kernels beside the context's OsdTables, front-end workspace
 // ---------------------------------------------------------------------------------------
 int osd_ctx_init(ldpc_ctx *ctx)
 {
-    const ldpc_code &c = ctx->code;
+    const OsdTables &t = ctx->osd_tables;
     ctx->osd_ok = false;
-    if (c.n != kOsdN || c.k != kOsdK) return LDPC_OK;  // OSD entry points will report UNSUPPORTED
-    std::vector<u64> cols(kOsdN, 0);
-    for (int r = 0; r < kOsdK; ++r)
-        for (int v = 0; v < kOsdN; ++v)
-            if (c.G[(size_t)r * kOsdN + v]) cols[v] |= 1ull << r;
-    LDPC_HIP(hipMalloc((void **)&ctx->d_Gcols, sizeof(u64) * kOsdN));
-    LDPC_HIP(hipMemcpy(ctx->d_Gcols, cols.data(), sizeof(u64) * kOsdN, hipMemcpyHostToDevice));
-    // one table for order 3; orders 0..2 are its prefixes (weight classes are concatenated)
+    if (t.n != kOsdN || t.k != kOsdK) return LDPC_OK;  // OSD entry points will report UNSUPPORTED
     OsdState *st = new OsdState();
     ctx->osd_state = st;
-    int64_t bounds[4];
-    const int64_t total = tep_table(kOsdK, 3, nullptr, bounds);
-    std::vector<uint8_t> sup((size_t)total * 3), packed((size_t)total * 4);
-    tep_table(kOsdK, 3, sup.data(), nullptr);
-    for (int64_t t = 0; t < total; ++t) {
-        int w = 0;
-        for (int q = 0; q < 3; ++q) { packed[4 * t + q] = sup[3 * t + q] == 0xFF ? 0 : sup[3 * t + q]; w += sup[3 * t + q] != 0xFF; }
-        packed[4 * t + 3] = (uint8_t)w;
-    }
-    for (int o = 0; o < 4; ++o) st->ntep[o] = bounds[o];
-    LDPC_HIP(hipMalloc((void **)&ctx->d_tep, packed.size()));
-    LDPC_HIP(hipMemcpy(ctx->d_tep, packed.data(), packed.size(), hipMemcpyHostToDevice));
-    // FS-OSD visit order (generate_sequential_teps, fs_testing.py:32-49), supports stored ascending
-    std::vector<uint8_t> fs;
-    int off = 0;
-    for (int w = 1; w <= 3; ++w) {
-        const int64_t cnt = tep_table_fs(kOsdK, w, nullptr);
-        std::vector<uint8_t> sup3((size_t)cnt * 3);
-        tep_table_fs(kOsdK, w, sup3.data());
-        st->fs_off[w] = off; st->fs_cnt[w] = (int)cnt;
-        for (int64_t t = 0; t < cnt; ++t) {
-            for (int q = 0; q < 3; ++q) fs.push_back(sup3[3 * t + q] == 0xFF ? 0 : sup3[3 * t + q]);
-            fs.push_back((uint8_t)w);
-        }
-        off += (int)cnt;
-    }
-    LDPC_HIP(hipMalloc((void **)&st->d_tep_fs, fs.size()));
-    LDPC_HIP(hipMemcpy(st->d_tep_fs, fs.data(), fs.size(), hipMemcpyHostToDevice));
     {
         int base2[127];
         auto npairs = [](int t) { return (t - 1) / 2 - (t > 63 ? t - 63 : 0) + 1; };
@@ -108,11 +74,8 @@ static void free_stream_ws(StreamWs &w)
 
 void osd_ctx_release(ldpc_ctx *ctx)
 {
-    (void)hipFree(ctx->d_Gcols);
-    (void)hipFree(ctx->d_tep);
     if (OsdState *st = state(ctx)) {
         for (auto &kv : st->ws) free_stream_ws(kv.second);
-        (void)hipFree(st->d_tep_fs);
         (void)hipFree(st->d_base2);
         (void)hipFree(st->d_cdf_half);
         (void)hipFree(st->d_index_errors);
@@ -206,7 +169,7 @@ static void launch_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index
                          u64 *d_parity, int32_t *d_nswaps, hipStream_t s)
 {
     hipLaunchKernelGGL(osd_front_kernel, dim3(frame_grid(F)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
-                       reinterpret_cast<const u64 *>(ctx->d_Gcols), d_perm, d_parity, d_nswaps);
+                       ctx->osd_tables.d_Gcols, d_perm, d_parity, d_nswaps);
 }
 
 static int need_osd(const ldpc_ctx *ctx)
@@ -268,6 +231,7 @@ int osd_launch(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const in
     *counted = false;
     const OsdPlan r = select_route(ctx, p, d_perm != nullptr);
     OsdState *st = state(ctx);
+    const OsdTables &t = ctx->osd_tables;
     int rc;
     if ((rc = guarded_index(ctx, p, d_index, d_count, F, s, &d_index))) return rc;
     if (!d_perm && r.route != OsdRoute::Fused2r && r.route != OsdRoute::PbFrontInside) {   // the front end into the stream's workspace
@@ -284,8 +248,7 @@ int osd_launch(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const in
     switch (r.route) {
     case OsdRoute::Fused2r:
         hipLaunchKernelGGL(osd_fused2r_kernel, dim3(g2r), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
-                           reinterpret_cast<const u64 *>(ctx->d_Gcols), ctx->dpp_wave_rol_dir, st->d_base2, cw, d_metric, d_best, d_ntep,
-                           label, counts);
+                           t.d_Gcols, ctx->dpp_wave_rol_dir, st->d_base2, cw, d_metric, d_best, d_ntep, label, counts);
         *counted = label != nullptr;
         break;
     case OsdRoute::Search2r:
@@ -300,21 +263,15 @@ int osd_launch(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const in
     case OsdRoute::Table:
         if (p->order >= 2)
             hipLaunchKernelGGL(osd_search_kernel<1>, dim3(g64), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity,
-                               reinterpret_cast<const uchar4 *>(ctx->d_tep), (int)st->ntep[p->order], cw, d_metric, d_best, d_ntep);
+                               t.d_tep, (int)t.ntep[p->order], cw, d_metric, d_best, d_ntep);
         else
             hipLaunchKernelGGL(osd_search_kernel<4>, dim3(osd_grid(F)), dim3(256), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity,
-                               reinterpret_cast<const uchar4 *>(ctx->d_tep), (int)st->ntep[p->order], cw, d_metric, d_best, d_ntep);
+                               t.d_tep, (int)t.ntep[p->order], cw, d_metric, d_best, d_ntep);
         break;
-    case OsdRoute::Fs: {
-        FsParams fp;
-        fp.order = p->order; fp.quirk = p->fs_reference_quirk != 0;
-        fp.beta_term = (float)((double)p->fs_beta * (double)(kOsdN - kOsdK));   // fs_testing.py:138
-        fp.tau_e = p->fs_tau_e; fp.tau_psc = p->fs_tau_psc;
-        for (int w = 0; w < 4; ++w) { fp.cls_off[w] = st->fs_off[w]; fp.cls_cnt[w] = st->fs_cnt[w]; }
-        hipLaunchKernelGGL(osd_fs_kernel, dim3(g64), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity, st->d_tep_fs, fp,
-                           cw, d_metric, d_best, d_ntep);
+    case OsdRoute::Fs:
+        hipLaunchKernelGGL(osd_fs_kernel, dim3(g64), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity, t.d_tep_fs,
+                           fs_params(p, t), cw, d_metric, d_best, d_ntep);
         break;
-    }
     case OsdRoute::PbStaged:
         return launch_pb(ctx, d_y, d_index, d_count, F, d_perm, parity, p, r.pb_mode, false, d_cw, d_metric, d_best, d_ntep, s);
     // The front end INSIDE the first PB kernel, nothing through a workspace (not the list replay, which needs records to set a
@@ -328,6 +285,15 @@ int osd_launch(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const in
     return LDPC_OK;
 }
 
+FsParams fs_params(const ldpc_osd_params *p, const OsdTables &t)
+{
+    FsParams fp;
+    fp.order = p->order; fp.quirk = p->fs_reference_quirk != 0;
+    fp.beta_term = (float)((double)p->fs_beta * (double)(t.n - t.k));   // fs_testing.py:138
+    fp.tau_e = p->fs_tau_e; fp.tau_psc = p->fs_tau_psc;
+    for (int w = 0; w < 4; ++w) { fp.cls_off[w] = t.fs_off[w]; fp.cls_cnt[w] = t.fs_cnt[w]; }
+    return fp;
+}
 
 }  // namespace ldpc
 

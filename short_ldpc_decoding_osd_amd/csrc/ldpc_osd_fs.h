@@ -14,12 +14,6 @@
 
 namespace ldpc {
 
-struct FsParams {
-    int order, quirk;
-    float beta_term, tau_e, tau_psc;
-    int cls_off[4], cls_cnt[4];   // weight class w: offset / count inside the FS-ordered table
-};
-
 // (one wavefront per workgroup, as the order-2 scan: compile-time LDS base for the LUT reads, and the
 //  dispatcher balances the very uneven per-frame TEP counts)
 __global__ __launch_bounds__(64) void osd_fs_kernel(const float *__restrict__ y, const int *__restrict__ index, const int *__restrict__ count,

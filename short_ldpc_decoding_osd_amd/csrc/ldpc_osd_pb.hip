@@ -54,7 +54,7 @@ int pb_ctx_init(ldpc_ctx *ctx)
 // list replay: the list is append-only, at most 1 + 2 (N_max - 1) slots; spilled slots first, spilled chunk minima after
 static int pb_spill_layout(ldpc_ctx *ctx, int order, int64_t *spill_slots, int64_t *stride)
 {
-    const int64_t nmax = state(ctx)->ntep[order];
+    const int64_t nmax = ctx->osd_tables.ntep[order];
     const int64_t slots = 2 * nmax + 2;
     if (slots > (int64_t)kPbSuper * 4096) return fail(LDPC_E_UNSUPPORTED, "ldpc_osd_decode: PB-OSD list of %lld slots exceeds the kernel's limit", (long long)slots);
     *spill_slots = slots > kPbLdsSlots ? slots - kPbLdsSlots : 0;
@@ -118,7 +118,7 @@ int launch_pb(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int
               uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_ntep, hipStream_t s)
 {
     OsdState *st = state(ctx);
-    const int64_t nmax = st->ntep[p->order];
+    const int64_t nmax = ctx->osd_tables.ntep[p->order];
     int64_t spill_slots, stride;
     if (int rc = pb_spill_layout(ctx, p->order, &spill_slots, &stride)) return rc;
     StreamWs *w;
@@ -159,7 +159,7 @@ int launch_pb(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int
     const unsigned g1 = (unsigned)(F < 1 ? 1 : (F < 32768 ? F : 32768));
     // front_inside (ldpc_osd_decode's option): the front end runs inside the singles kernel, nothing goes through a workspace --
     // the frames of list B are then set up from the singles records (mode 2, every frame to the list replay, writes none)
-    const u64 *const Gcols = reinterpret_cast<const u64 *>(ctx->d_Gcols);
+    const u64 *const Gcols = ctx->osd_tables.d_Gcols;
     if (front_inside)
         hipLaunchKernelGGL((pb_singles_kernel<true>), dim3(g1), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, d_parity, Gcols, pp,
                            pb_mode, st->d_cdf_half, w->d_pb_ctl, listA, listB, sub_cap, recs, O);

@@ -1,4 +1,6 @@
-// Host-side OSD state of a context: TEP tables and the per-stream workspaces (ldpc_osd.hip, ldpc_osd_pb.hip; the PB kernels, ldpc_pb_*.h, read the control-word layout).
+// Host-side state of the (128,64) OSD kernels in a context: their own constants and the per-stream workspaces (ldpc_osd.hip,
+// ldpc_osd_pb.hip; the PB kernels, ldpc_pb_*.h, read the control-word layout).  The G columns and the TEP tables are not here:
+// they are the context's OsdTables (ldpc_osd_tables.h), shared with the any-shape kernels.
 #pragma once
 
 #include "ldpc_wave.h"
@@ -39,12 +41,9 @@ constexpr int kPbHeavyCap = 2 * kPbCoopHalf;      // to the end of the table (se
 constexpr int kPbSeqBlocks = 64;      // grid of the sequential PB kernel (each of its 4 x 64 waves owns a spill area)
 
 struct OsdState {
-    int64_t ntep[4] = {0, 0, 0, 0};
-    uchar4 *d_tep_fs = nullptr;       // FS visit order, weight classes 1..3 back to back
     int *d_base2 = nullptr;           // order-2 ranks: number of index pairs with a larger sum
     double *d_cdf_half = nullptr;     // PB-OSD: P[Bin(64, 1/2) <= b], b = 0..64
     unsigned long long *d_index_errors = nullptr;   // ldpc_osd_params.y_frames: out-of-range entries met so far
-    int fs_off[4] = {0, 0, 0, 0}, fs_cnt[4] = {0, 0, 0, 0};
     ldpc_pb_tuning pb_tuning;         // PB-OSD hand-over schedule and chunk targets (ldpc_ctx_set_pb_tuning); read under `mu`
     std::mutex mu;                    // guards `ws`, `reserve_frames` and `pb_tuning`
     std::unordered_map<hipStream_t, StreamWs> ws;

@@ -1,0 +1,43 @@
+// The OSD tables of a context (host side): G columns, the conventional TEP table and the FS visit-order table of the code's k.
+// ONE set per context, for every code with 1 <= k <= 64 and 1 <= n - k <= 64: the (128,64) kernels (ldpc_osd.hip,
+// ldpc_osd_pb.hip) and the any-shape kernels (ldpc_osdx.hip) read the same device copies.  Packed by pack_osd_tables
+// (ldpc_host.cpp), uploaded by ldpc_ctx_create and freed by ldpc_ctx_destroy (ldpc_api.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/ldpc_osd.h"
+
+namespace ldpc {
+
+typedef unsigned long long u64;   // (as ldpc_wave.h; this header is also part of the host-only build, which has no ldpc_wave.h)
+
+struct OsdTables {
+    int n = 0, k = 0;            // the shape the tables were built for; k = 0: no tables (the OSD entry points report UNSUPPORTED)
+    u64 *d_Gcols = nullptr;      // [n] column v of G as a k-bit word (bit r = G[r][v])
+    uchar4 *d_tep = nullptr;     // conventional order-3 TEP table of this k: (i, j, l, weight); order o is the prefix of ntep[o] entries
+    int64_t ntep[4] = {0, 0, 0, 0};
+    uchar4 *d_tep_fs = nullptr;  // FS-OSD visit order (generate_sequential_teps) of this k: weight classes 1..min(3, k) back to back
+    int fs_off[4] = {0, 0, 0, 0}, fs_cnt[4] = {0, 0, 0, 0};   // weight class w: offset / count inside d_tep_fs
+};
+
+// the host images of the three device tables
+struct OsdTablesHost {
+    std::vector<u64> Gcols;
+    std::vector<uchar4> tep, tep_fs;
+};
+
+// For a code with 1 <= k <= 64, 1 <= n - k <= 64 and G = [k][n]: fills `host` and the shape, boundaries, offsets and counts
+// of `t` (never a device pointer).  Any other code leaves t.k = 0.  LDPC_OK, or the error of tep_table / tep_table_fs.
+// Pure host code (ldpc_host.cpp).
+int pack_osd_tables(const ldpc_code &c, OsdTables &t, OsdTablesHost &host);
+
+// The kernel argument of osd_fs_kernel / osdx_fs_kernel (FsParams: ldpc_search.h) from the caller's parameters and the
+// context's tables; beta_term = (float)((double)fs_beta * (double)(n - k)) (fs_testing.py:138).  Defined in ldpc_osd.hip.
+struct FsParams;
+FsParams fs_params(const ldpc_osd_params *p, const OsdTables &t);
+
+}  // namespace ldpc

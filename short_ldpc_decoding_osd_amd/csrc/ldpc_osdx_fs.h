@@ -12,17 +12,11 @@
 
 namespace ldpc {
 
-struct OsdxFsParams {
-    int order, quirk;
-    float beta_term, tau_e, tau_psc;
-    int cls_off[4], cls_cnt[4];   // weight class w: offset / count inside the FS-ordered table of this k
-};
-
 //   counts[3] += {frames, frames_wrong, teps_total} (with label; teps_total sums the frame's own ntep, only with ntep_out): one
 //   atomic per counter and wavefront, after its last frame.
 __global__ __launch_bounds__(64) void osdx_fs_kernel(const float *__restrict__ y, const int *__restrict__ index, const int *__restrict__ count,
         long long F, int n, int k, const unsigned char *__restrict__ perm_in, const u64 *__restrict__ parity_in,
-        const uchar4 *__restrict__ teps_fs, OsdxFsParams P, u64 *__restrict__ cw_out, float *__restrict__ metric_out,
+        const uchar4 *__restrict__ teps_fs, FsParams P, u64 *__restrict__ cw_out, float *__restrict__ metric_out,
         int *__restrict__ best_out, int *__restrict__ ntep_out, const u64 *__restrict__ label, u64 *__restrict__ counts)
 {
     __shared__ SearchLds L;   // one wavefront per workgroup: compile-time LDS base for the LUT reads

@@ -21,6 +21,13 @@ struct __attribute__((aligned(16))) SearchLdsLean {   // the same without the by
     unsigned char perm[128];
 };
 
+// kernel argument of the FS-OSD scans (osd_fs_kernel, osdx_fs_kernel); the host fills it with fs_params (ldpc_osd_tables.h)
+struct FsParams {
+    int order, quirk;
+    float beta_term, tau_e, tau_psc;
+    int cls_off[4], cls_cnt[4];   // weight class w: offset / count inside the FS-ordered table of the code's k
+};
+
 // The metric of tep_cost() without the LUTs: the canonical order written out (each parity byte's set positions ascending from
 // 0.0f, the byte sums added in order) -- bit-identical, ~130 instructions instead of 8 LUT reads: for kernels that evaluate
 // one or two candidates per frame.

@@ -73,8 +73,49 @@ class Decoder:
         return out
 
     def _osd_outputs(self, out, F):
-        return self._outputs(out, {"cw": ((F, 2), torch.int64, True), "metric": ((F,), torch.float32, True),
+        return self._outputs(out, {"cw": ((F, self.words), torch.int64, True), "metric": ((F,), torch.float32, True),
                                    "best": ((F,), torch.int32, True), "ntep": ((F,), torch.int32, True)})
+
+    def _osd_frames(self, y, index, F):
+        """The F rule of the calls that start from channel values: the frame list's length, else y's."""
+        self._chk(y, torch.float32, (self.n,), "y")
+        return (index.shape[0] if index is not None else y.shape[0]) if F is None else F
+
+    def _osd_front_results(self, y, perm, parity, F=None):
+        """The checks of the calls that take front-end results (perm [*,128] u8, parity [*,64] int64).  Returns F."""
+        self._chk(y, torch.float32, (self.n,), "y")
+        self._chk(perm, torch.uint8, (128,), "perm")
+        self._chk(parity, torch.int64, (64,), "parity")
+        return perm.shape[0] if F is None else F
+
+    def _osd_front(self, fn, name, y, index, count, F, out):
+        """``osd_front`` / ``osdx_front``: ``fn`` is the library function, ``name`` its name."""
+        F = self._osd_frames(y, index, F)
+        if out is not None:
+            perm, parity, ns = out
+        else:
+            perm = self.empty((F, 128), torch.uint8)
+            parity = self.empty((F, 64), torch.int64)
+            ns = self.empty((F,), torch.int32)
+        _lib.check(fn(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(ns), self._stream()), name)
+        return perm, parity, ns
+
+    def _osd_tep_eval(self, fn, name, y, perm, parity, mask, index, count):
+        """``osd_tep_eval`` / ``osdx_tep_eval``: ``fn`` is the library function, ``name`` its name."""
+        F = self._osd_front_results(y, perm, parity)
+        self._chk(mask, torch.int64, (), "mask")
+        out = dict(cw=self.empty((F, self.words), torch.int64), metric=self.empty((F,), torch.float32), hd=self.empty((F,), torch.int32))
+        _lib.check(fn(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(mask), _ptr(out["cw"]),
+                      _ptr(out["metric"]), _ptr(out["hd"]), self._stream()), name)
+        return out
+
+    def _osdx_decode_args(self, y, index, F, perm, parity):
+        """The checks of ``osdx_decode`` / ``osdx_fs_decode``: F by the rule of ``_osd_frames``, ``perm`` / ``parity``
+        checked when given and allocated when not.  Returns (F, perm, parity)."""
+        F = self._osd_frames(y, index, F)
+        perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
+        parity = self.empty((F, 64), torch.int64) if parity is None else self._chk(parity, torch.int64, (64,), "parity")
+        return F, perm, parity
 
     def _hosd_args(self, order_llr, metric_llr, front, teps, block_off):
         """The checks hosd_search and hosd_sliding share.  Returns (lri, uidx, M, F, nblk)."""
@@ -240,17 +281,7 @@ class Decoder:
     def osd_front(self, y, index=None, count=None, F=None, out=None):
         """Reliability sort + elimination + MRB bookkeeping.  Returns (perm[F,128] u8,
         parity[F,64] int64 rows of P', nswaps[F] int32); ``out`` may carry those three preallocated."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        F = (index.shape[0] if index is not None else y.shape[0]) if F is None else F
-        if out is not None:
-            perm, parity, ns = out
-        else:
-            perm = self.empty((F, 128), torch.uint8)
-            parity = self.empty((F, 64), torch.int64)
-            ns = self.empty((F,), torch.int32)
-        _lib.check(self.L.ldpc_osd_front(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
-                                         _ptr(ns), self._stream()), "ldpc_osd_front")
-        return perm, parity, ns
+        return self._osd_front(self.L.ldpc_osd_front, "ldpc_osd_front", y, index, count, F, out)
 
     def osd_params(self, order, algo=_lib.OSD_CONVENTIONAL, snr_db=0.0, fs_beta=0.1, fs_tau_e=6.5, fs_tau_psc=30.0,
                    fs_reference_quirk=1, aux=None, table_scan=False, pb_path=None, readlane_scan=False, y_frames=0,
@@ -276,8 +307,7 @@ class Decoder:
     def osd_decode(self, y, order, algo=_lib.OSD_CONVENTIONAL, index=None, count=None, F=None, params=None, out=None):
         """OSD of the frames y[index[f]] (or y[f]).  Returns dict(cw[F,2] int64 original bit
         order, metric[F] f32, best[F] i32, ntep[F] i32)."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        F = (index.shape[0] if index is not None else y.shape[0]) if F is None else F
+        F = self._osd_frames(y, index, F)
         p = params if params is not None else self.osd_params(order, algo)
         out = self._osd_outputs(out, F)
         _lib.check(self.L.ldpc_osd_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, C.byref(p), _ptr(out["cw"]),
@@ -287,10 +317,7 @@ class Decoder:
 
     def osd_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
         """Search only, on caller-supplied front-end results (perm [F,128] u8, parity [F,64] int64)."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        self._chk(perm, torch.uint8, (128,), "perm")
-        self._chk(parity, torch.int64, (64,), "parity")
-        F = perm.shape[0] if F is None else F
+        F = self._osd_front_results(y, perm, parity, F)
         out = self._osd_outputs(out, F)
         _lib.check(self.L.ldpc_osd_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
                                           C.byref(params), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
@@ -300,15 +327,7 @@ class Decoder:
     def osd_tep_eval(self, y, perm, parity, mask, index=None, count=None):
         """One given TEP per frame (mask [F] int64: bit p flips primed MRB position p) on front-end results.
         Returns dict(cw[F,2] int64 original bit order, metric[F] f32, hd[F] i32)."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        self._chk(perm, torch.uint8, (128,), "perm")
-        self._chk(parity, torch.int64, (64,), "parity")
-        self._chk(mask, torch.int64, (), "mask")
-        F = perm.shape[0]
-        out = dict(cw=self.empty((F, 2), torch.int64), metric=self.empty((F,), torch.float32), hd=self.empty((F,), torch.int32))
-        _lib.check(self.L.ldpc_osd_tep_eval(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(mask),
-                                            _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["hd"]), self._stream()), "ldpc_osd_tep_eval")
-        return out
+        return self._osd_tep_eval(self.L.ldpc_osd_tep_eval, "ldpc_osd_tep_eval", y, perm, parity, mask, index, count)
 
     # ------------------------------------------------------------------ OSD for short codes of any shape
     @property
@@ -316,34 +335,17 @@ class Decoder:
         """Whether the ``osdx_*`` methods serve this code (1 <= k <= 64 and 1 <= n-k <= 64)."""
         return bool(self.L.ldpc_osdx_supported(self._ctx))
 
-    def _osdx_outputs(self, out, F):
-        return self._outputs(out, {"cw": ((F, self.words), torch.int64, True), "metric": ((F,), torch.float32, True),
-                                   "best": ((F,), torch.int32, True), "ntep": ((F,), torch.int32, True)})
-
     def osdx_front(self, y, index=None, count=None, F=None, out=None):
         """``osd_front`` for any supported shape.  Returns (perm[F,128] u8: original bit at primed position p < n, MRB
         first, 0 beyond n; parity[F,64] int64: rows r < k of P', bits c < n-k, 0 elsewhere; nswaps[F] int32); ``out`` may
         carry those three preallocated (nswaps may be None)."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        F = (index.shape[0] if index is not None else y.shape[0]) if F is None else F
-        if out is not None:
-            perm, parity, ns = out
-        else:
-            perm = self.empty((F, 128), torch.uint8)
-            parity = self.empty((F, 64), torch.int64)
-            ns = self.empty((F,), torch.int32)
-        _lib.check(self.L.ldpc_osdx_front(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
-                                          _ptr(ns), self._stream()), "ldpc_osdx_front")
-        return perm, parity, ns
+        return self._osd_front(self.L.ldpc_osdx_front, "ldpc_osdx_front", y, index, count, F, out)
 
     def osdx_search(self, y, perm, parity, order, index=None, count=None, F=None, out=None):
         """Conventional order-``order`` search on front-end results (perm [F,128] u8, parity [F,64] int64) of any supported
         shape.  Returns dict(cw[F,words] int64 original bit order, metric[F] f32, best[F] i32, ntep[F] i32)."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        self._chk(perm, torch.uint8, (128,), "perm")
-        self._chk(parity, torch.int64, (64,), "parity")
-        F = perm.shape[0] if F is None else F
-        out = self._osdx_outputs(out, F)
+        F = self._osd_front_results(y, perm, parity, F)
+        out = self._osd_outputs(out, F)
         _lib.check(self.L.ldpc_osdx_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), int(order),
                                            _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
                                            self._stream()), "ldpc_osdx_search")
@@ -355,11 +357,8 @@ class Decoder:
         launches through ``perm`` / ``parity`` (allocated when not given; returned in the dict).  With ``label_bits``
         ([*, words] int64, addressed through ``index``) and ``counts`` ([3] int64) the search accumulates
         counts += {frames, frames_wrong, teps_total}."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        F = (index.shape[0] if index is not None else y.shape[0]) if F is None else F
-        perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
-        parity = self.empty((F, 64), torch.int64) if parity is None else self._chk(parity, torch.int64, (64,), "parity")
-        out = self._osdx_outputs(out, F)
+        F, perm, parity = self._osdx_decode_args(y, index, F, perm, parity)
+        out = self._osd_outputs(out, F)
         _lib.check(self.L.ldpc_osdx_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, int(order), _ptr(perm), _ptr(parity),
                                            _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
                                            _ptr(label_bits), _ptr(counts), self._stream()), "ldpc_osdx_decode")
@@ -370,11 +369,8 @@ class Decoder:
         """FS-OSD on front-end results of any supported shape.  ``params``: ``osd_params(order, _lib.OSD_FS, fs_beta=...,
         fs_tau_e=..., fs_tau_psc=..., fs_reference_quirk=...)``, order 0..min(3, k).  Returns the dict of ``osdx_search``
         (best: rank in visit order, 0 = the all-zero TEP; ntep: num_teps)."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        self._chk(perm, torch.uint8, (128,), "perm")
-        self._chk(parity, torch.int64, (64,), "parity")
-        F = perm.shape[0] if F is None else F
-        out = self._osdx_outputs(out, F)
+        F = self._osd_front_results(y, perm, parity, F)
+        out = self._osd_outputs(out, F)
         _lib.check(self.L.ldpc_osdx_fs_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
                                               C.byref(params), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
                                               _ptr(out["ntep"]), self._stream()), "ldpc_osdx_fs_search")
@@ -384,11 +380,8 @@ class Decoder:
                        out=None):
         """Front end + FS-OSD of the frames y[index[f]] (or y[f]) for any supported shape: ``osdx_decode`` with the search
         of ``osdx_fs_search``; ``perm`` / ``parity`` / ``label_bits`` / ``counts`` as there."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        F = (index.shape[0] if index is not None else y.shape[0]) if F is None else F
-        perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
-        parity = self.empty((F, 64), torch.int64) if parity is None else self._chk(parity, torch.int64, (64,), "parity")
-        out = self._osdx_outputs(out, F)
+        F, perm, parity = self._osdx_decode_args(y, index, F, perm, parity)
+        out = self._osd_outputs(out, F)
         _lib.check(self.L.ldpc_osdx_fs_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, C.byref(params), _ptr(perm),
                                               _ptr(parity), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
                                               _ptr(out["ntep"]), _ptr(label_bits), _ptr(counts), self._stream()),
@@ -399,15 +392,7 @@ class Decoder:
     def osdx_tep_eval(self, y, perm, parity, mask, index=None, count=None):
         """``osd_tep_eval`` for any supported shape (mask [F] int64: bit p < k flips primed MRB position p).
         Returns dict(cw[F,words] int64 original bit order, metric[F] f32, hd[F] i32)."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        self._chk(perm, torch.uint8, (128,), "perm")
-        self._chk(parity, torch.int64, (64,), "parity")
-        self._chk(mask, torch.int64, (), "mask")
-        F = perm.shape[0]
-        out = dict(cw=self.empty((F, self.words), torch.int64), metric=self.empty((F,), torch.float32), hd=self.empty((F,), torch.int32))
-        _lib.check(self.L.ldpc_osdx_tep_eval(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(mask),
-                                             _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["hd"]), self._stream()), "ldpc_osdx_tep_eval")
-        return out
+        return self._osd_tep_eval(self.L.ldpc_osdx_tep_eval, "ldpc_osdx_tep_eval", y, perm, parity, mask, index, count)
 
     # ------------------------------------------------------------------ H-form OSD (DL-OSD stage)
     def hosd_front(self, order_llr):
