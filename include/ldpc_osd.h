@@ -359,9 +359,11 @@ int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label
  *   the conventional search     convention_osd_main, FS_OSD/convention_osd.py:49-76, orders 0..3
  *   FS-OSD                      fs_osd, FS_OSD/fs_testing.py:129-161, orders 0..min(3, k)
  *   one given TEP per frame     one_tep_compare, FS_OSD/fs_testing.py:51-64
- * Everything else of this header that says OSD -- PB-OSD, the elimination primitive, the H-form primitives, the
- * one-call pipeline, the LDPC_OSD_F_* flags, d_aux and y_frames of ldpc_osd_params, and the entry points above
- * themselves -- stays with (n = 128, k = 64) and keeps answering LDPC_E_UNSUPPORTED on other shapes.
+ *   PB-OSD                      pb_osd, PB_OSD/pb_testing.py:100-149, orders 0..min(3, k)
+ * Everything else of this header that says OSD -- the PB tuning (ldpc_pb_tuning), the elimination primitive, the H-form
+ * primitives, the one-call pipeline, the LDPC_OSD_F_* flags (the LDPC_OSD_F_PB_* routes among them) and y_frames of
+ * ldpc_osd_params, d_aux outside the PB pair, and the entry points above themselves -- stays with (n = 128, k = 64) and
+ * keeps answering LDPC_E_UNSUPPORTED on other shapes.
  * Same rules as above for d_index / d_count (min(*d_count, F) frames, read on the device; nothing at or beyond that
  * frame is written), for ties of the sort (lower index first), the TEP table (the one of this code's k, orders 0..3,
  * first minimum) and the float order of the metric: flipped MRB weights ascending from 0.0f, then bytes of eight
@@ -377,8 +379,8 @@ int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label
  * The decode entry points are two launches through the caller's d_perm / d_parity, which are scratch AND outputs and
  * required: there is no library workspace and no per-stream state.  Before any launch: an unsupported shape is
  * LDPC_E_UNSUPPORTED (the message names the limits and the code's (n,k)), an order outside its range and a NULL in a
- * required pointer are LDPC_E_ARG, F == 0 is LDPC_OK.  The tables (G columns, the order-3 TEP table and the FS visit
- * order of k) are uploaded by ldpc_ctx_create; nothing is allocated and nothing synchronises in a call
+ * required pointer are LDPC_E_ARG, F == 0 is LDPC_OK.  The tables (G columns, the order-3 TEP table, the FS visit
+ * order of k and the PB constants of k and n-k) are uploaded by ldpc_ctx_create; nothing is allocated and nothing synchronises in a call
  * (graph-capturable).
  * The FS entry points read `params` for order, algo, fs_beta, fs_tau_e, fs_tau_psc and fs_reference_quirk, with the
  * meaning they have in ldpc_osd_decode: the lower bound of weight w is the sum of the w least reliable MRB |y'|
@@ -388,6 +390,17 @@ int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label
  * order outside 0..min(3, k) (the bound has no meaning for w > k), flags != 0, d_aux != NULL and y_frames != 0.
  * The one-TEP entry point is ldpc_osd_tep_eval with the split at k: d_mask [F] u64, bit p < k flips MRB position p
  * (bits at or beyond k are ignored); d_cw [F][ceil(n/64)] u64; d_metric [F] f32 and d_hd [F] i32 are nullable.
+ * The PB entry points read `params` for order, algo, snr_db and d_aux (nullable DEVICE [F][4] i32: {frontier comparisons,
+ * suc1, suc2, stop reason}), with the meaning they have in ldpc_osd_decode and its float conventions with 64 replaced by
+ * k and m = n-k: c4 = (float)(-4 / 10^(snr_db/10)); q_p = 1 / (1 + det_expf(-(c4 |y'_p|))) in float32; p1 and the mean
+ * |y'| over the parity part divided by (float)m, pt over the MRB by (float)k, the product of 1 - q_p over the MRB, each
+ * ascending; the binomial CDFs of (m, p1), (m, 1/2) and (k, pt) by the float64 pmf recurrence with q^N by left-to-right
+ * square-and-multiply; beta clamped to 0..m; N_max = sum of C(k, w) over w <= order.  The frontier starts as {k-1}; a
+ * step pops the first minimum by (reliability sum, insertion order) and appends the extended child e + {k-1}, then the
+ * adjacent child.  d_best is the rank in visit order (0 = the all-zero TEP), d_ntep is cost_tep_num, or N_max when no
+ * rule fired.  The frontier lives in LDS (one slot per run of adjacent children, at most 1 + (k-1) + C(k-1, 2) of them):
+ * no workspace here either.  LDPC_E_ARG, naming the offender, for algo != LDPC_OSD_PB, an order outside
+ * 0..min(3, k), flags != 0 and y_frames != 0.
  * ------------------------------------------------------------------------------------- */
 int ldpc_osdx_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
 int ldpc_osdx_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
@@ -409,6 +422,13 @@ int ldpc_osdx_fs_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
 int ldpc_osdx_tep_eval(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
                        const uint8_t *d_perm, const uint64_t *d_parity, const uint64_t *d_mask, uint64_t *d_cw,
                        float *d_metric, int32_t *d_hd, void *stream);
+int ldpc_osdx_pb_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *params, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, void *stream);
+int ldpc_osdx_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const ldpc_osd_params *params, uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits,
+                        int64_t *d_counts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H):

@@ -1,8 +1,11 @@
-"""NMS + order-p OSD of any short code (1 <= k <= 64, 1 <= n-k <= 64): FER before and after the OSD, and the two OSD kernels timed.
+"""NMS + order-p OSD (conventional, FS-OSD or PB-OSD) of any short code (1 <= k <= 64, 1 <= n-k <= 64): FER before and after the
+OSD, and the two OSD kernels timed.
 
     python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2
     python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2 \
         --osd fs --tau-e 4.5
+    python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 3 \
+        --osd pb
 
 Frame generator -> ldpc_nms_decode -> ldpc_compact -> ldpc_osdx_decode on the failures (the reference's loop: NMS, then
 convention_osd_main on the frames with a non-zero syndrome).  Times are HIP events around --calls back-to-back launches on the
@@ -12,6 +15,10 @@ failures of the whole batch, after a warm-up, --repeats times (every repeat is p
 as the reference evaluates it: required for an alist, whose d_min the script cannot know; 6.5 for the packaged CCSDS code) and
 --tau-psc.  Printed then: mean and maximum TEPs per frame next to the size of the order-p table, osdx_fs_kernel timed like the other
 legs and, on a (128,64) code, osd_fs_kernel through ldpc_osd_search on the same frames.
+--osd pb: the search is PB-OSD (ldpc_osdx_pb_decode; pb_osd, PB_OSD/pb_testing.py:100-149), --snr doubling as the decoder's snr_db.
+Printed then: mean and maximum TEPs per frame next to N_max, the shares of the three stop reasons (0 = no rule fired, 1 = the
+promising rule, 2 = the success rule), osdx_pb_kernel timed like the other legs and, on a (128,64) code, ldpc_osd_search on the
+same frames through the literal replay route (LDPC_OSD_F_PB_REPLAY: the same algorithm) and through the default staged route.
 One JSON line at the end."""
 import argparse
 import json
@@ -74,12 +81,13 @@ def main(argv=None):
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--osd", choices=("conv", "fs"), default="conv", help="the search: the conventional table scan, or FS-OSD")
+    ap.add_argument("--osd", choices=("conv", "fs", "pb"), default="conv",
+                    help="the search: the conventional table scan, FS-OSD, or PB-OSD")
     ap.add_argument("--beta", type=float, default=0.1, help="FS-OSD: beta of the lower bound (Main_FS_OSD.py:20)")
     ap.add_argument("--tau-e", type=float, default=None, help="FS-OSD: the stop threshold on the Hamming distance")
     ap.add_argument("--tau-psc", type=float, default=30.0, help="FS-OSD: tau_psc (FS_OSD/globalmap.py:50)")
     args = ap.parse_args(argv)
-    fs = args.osd == "fs"
+    fs, pb = args.osd == "fs", args.osd == "pb"
     if fs and args.tau_e is None:
         if args.alist:
             ap.error("--osd fs needs --tau-e for an alist code (there is no default d_min)")
@@ -100,6 +108,10 @@ def main(argv=None):
     if fs:
         fsp = dec.osd_params(args.order, _lib.OSD_FS, fs_beta=args.beta, fs_tau_e=args.tau_e, fs_tau_psc=args.tau_psc)
         out = dec.osdx_fs_decode(y, fsp, index=idx, count=count, label_bits=labels, counts=counts)
+    elif pb:
+        aux = torch.zeros((idx.shape[0], 4), dtype=torch.int32, device=dec.device)
+        pbp = dec.osd_params(args.order, _lib.OSD_PB, snr_db=args.snr, aux=aux)
+        out = dec.osdx_pb_decode(y, pbp, index=idx, count=count, label_bits=labels, counts=counts)
     else:
         out = dec.osdx_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
     torch.cuda.synchronize()
@@ -119,6 +131,15 @@ def main(argv=None):
         print(f"  order-{args.order} FS-OSD (beta {args.beta}, tau_e {args.tau_e}, tau_psc {args.tau_psc}) on the {nf} failures: FER {fer_osd:.3e} "
               f"({oc[1]} still wrong); TEPs per frame: mean {mean:.1f}, max {most}, table {table}", flush=True)
         result.update(osd="fs", beta=args.beta, tau_e=args.tau_e, tau_psc=args.tau_psc, teps_mean=mean, teps_max=most, teps_table=table)
+    elif pb:
+        table = sum(math.comb(dec.k, w) for w in range(args.order + 1))
+        ntep = out["ntep"][:nf].to(torch.float64)
+        mean, most = (float(ntep.mean()), int(ntep.max())) if nf else (0.0, 0)
+        stops = [int((aux[:nf, 3] == r).sum()) / max(nf, 1) for r in range(3)]
+        print(f"  order-{args.order} PB-OSD (snr_db {args.snr}) on the {nf} failures: FER {fer_osd:.3e} ({oc[1]} still wrong); TEPs per frame: "
+              f"mean {mean:.1f}, max {most}, N_max {table}; stops: none {stops[0]:.3f}, promising {stops[1]:.3f}, success {stops[2]:.3f}",
+              flush=True)
+        result.update(osd="pb", teps_mean=mean, teps_max=most, teps_table=table, stop_shares=stops)
     else:
         print(f"  order-{args.order} OSD on the {nf} failures: FER {fer_osd:.3e} ({oc[1]} still wrong, {oc[2] // max(oc[0], 1)} TEPs per frame)",
               flush=True)
@@ -133,6 +154,13 @@ def main(argv=None):
         if (dec.n, dec.k) == (128, 64):                  # the specialised kernel on the same front-end results, in the same run
             out2 = dec.osd_search(y, out["perm"], out["parity"], fsp, index=idx, count=count)
             legs.append(("osd_fs_kernel", lambda: dec.osd_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out2)))
+    elif pb:
+        legs[1] = ("osdx_pb_kernel", lambda: dec.osdx_pb_search(y, out["perm"], out["parity"], pbp, index=idx, count=count, out=out))
+        if (dec.n, dec.k) == (128, 64):                  # the specialised routes on the same front-end results, in the same run
+            for name, path in (("osd_search(PB replay)", "replay"), ("osd_search(PB staged)", None)):
+                pr = dec.osd_params(args.order, _lib.OSD_PB, snr_db=args.snr, pb_path=path)
+                o2 = dec.osd_search(y, out["perm"], out["parity"], pr, index=idx, count=count)
+                legs.append((name, lambda pr=pr, o2=o2: dec.osd_search(y, out["perm"], out["parity"], pr, index=idx, count=count, out=o2)))
     elif (dec.n, dec.k) == (128, 64):                      # the specialised kernels on the same frames, in the same run
         p = dec.osd_params(args.order, table_scan=True)
         perm2, par2, ns2 = dec.osd_front(y, index=idx, count=count)

@@ -52,7 +52,7 @@ int ldpc_ctx_create(const ldpc_code *code, int32_t device, ldpc_ctx **out)
             OsdTablesHost host;
             if ((rc = pack_osd_tables(ctx->code, t, host))) break;
             if (t.k && ((rc = upload(host.Gcols, &t.d_Gcols)) || (rc = upload(host.tep, &t.d_tep)) ||
-                        (rc = upload(host.tep_fs, &t.d_tep_fs)))) break;
+                        (rc = upload(host.tep_fs, &t.d_tep_fs)) || (rc = upload(host.pb, &t.d_pb)))) break;
         }
         if ((rc = probe_dpp(&ctx->dpp_ror_up, &ctx->dpp_wave_rol_dir))) break;
         // event pool of ldpc_pipeline_run's timing slots: created (and recorded once: the first record of an
@@ -85,6 +85,7 @@ void ldpc_ctx_destroy(ldpc_ctx *ctx)
     osd_ctx_release(ctx);
     hosd_ctx_release(ctx);
     (void)hipFree(ctx->osd_tables.d_Gcols); (void)hipFree(ctx->osd_tables.d_tep); (void)hipFree(ctx->osd_tables.d_tep_fs);
+    (void)hipFree(ctx->osd_tables.d_pb);
     (void)hipFree(ctx->d_chk_ptr); (void)hipFree(ctx->d_chk_var);
     (void)hipFree(ctx->d_var_ptr); (void)hipFree(ctx->d_var_edge);
     if (ctx->timing) {

@@ -270,6 +270,25 @@ int pack_osd_tables(const ldpc_code &c, OsdTables &t, OsdTablesHost &host)
         t.fs_off[w] = (int)host.tep_fs.size(); t.fs_cnt[w] = (int)cnt;
         pack_supports(sup, host.tep_fs);
     }
+    // any-shape PB-OSD: P[Bin(m, 1/2) <= b] by the float64 pmf recurrence of the oracle (q^m by left-to-right square-and-multiply,
+    // ratio p / q = 1), and the ratios of consecutive binomial coefficients of m and k
+    {
+        const int m = c.n - c.k;
+        host.pb.assign(65 + 64 + 64, 0.0);
+        double *cdf = host.pb.data(), *coef_m = cdf + 65, *coef_k = coef_m + 64;
+        for (int i = 0; i < m; ++i) coef_m[i] = (double)(m - i) / (double)(i + 1);
+        for (int i = 0; i < c.k; ++i) coef_k[i] = (double)(c.k - i) / (double)(i + 1);
+        int top = 0;
+        while ((m >> (top + 1)) != 0) ++top;
+        double tt = 0.5;
+        for (int b = top - 1; b >= 0; --b) {
+            tt = tt * tt;
+            if ((m >> b) & 1) tt = tt * 0.5;
+        }
+        double acc = tt;
+        cdf[0] = acc;
+        for (int i = 0; i < m; ++i) { tt = tt * coef_m[i] * (0.5 / 0.5); acc = acc + tt; cdf[i + 1] = acc; }
+    }
     t.n = c.n; t.k = c.k;
     return LDPC_OK;
 }

@@ -1,4 +1,5 @@
-// The OSD tables of a context (host side): G columns, the conventional TEP table and the FS visit-order table of the code's k.
+// The OSD tables of a context (host side): G columns, the conventional TEP table, the FS visit-order table of the code's k and
+// the code-only constants of the any-shape PB-OSD kernel.
 // ONE set per context, for every code with 1 <= k <= 64 and 1 <= n - k <= 64: the (128,64) kernels (ldpc_osd.hip,
 // ldpc_osd_pb.hip) and the any-shape kernels (ldpc_osdx.hip) read the same device copies.  Packed by pack_osd_tables
 // (ldpc_host.cpp), uploaded by ldpc_ctx_create and freed by ldpc_ctx_destroy (ldpc_api.hip).
@@ -22,12 +23,14 @@ struct OsdTables {
     int64_t ntep[4] = {0, 0, 0, 0};
     uchar4 *d_tep_fs = nullptr;  // FS-OSD visit order (generate_sequential_teps) of this k: weight classes 1..min(3, k) back to back
     int fs_off[4] = {0, 0, 0, 0}, fs_cnt[4] = {0, 0, 0, 0};   // weight class w: offset / count inside d_tep_fs
+    double *d_pb = nullptr;      // any-shape PB-OSD (ldpc_osdx_pb.h): [65] P[Bin(n-k, 1/2) <= b], then [64] (n-k-i)/(i+1) and [64] (k-i)/(i+1)
 };
 
-// the host images of the three device tables
+// the host images of the device tables
 struct OsdTablesHost {
     std::vector<u64> Gcols;
     std::vector<uchar4> tep, tep_fs;
+    std::vector<double> pb;
 };
 
 // For a code with 1 <= k <= 64, 1 <= n - k <= 64 and G = [k][n]: fills `host` and the shape, boundaries, offsets and counts

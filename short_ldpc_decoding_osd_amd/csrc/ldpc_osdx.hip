@@ -1,11 +1,14 @@
 // OSD for short codes of any shape: the host side of ldpc_osdx_* (context tables, validation, launches).
 // For every code with 1 <= k <= 64 and 1 <= n - k <= 64: the front end, the conventional order-p scan (device code:
-// ldpc_osdx.h), FS-OSD and the one-TEP primitive (ldpc_osdx_fs.h).  PB-OSD and the one-call pipeline stay with the (128,64)
-// kernels of ldpc_osd.hip / ldpc_osd_pb.hip.
+// ldpc_osdx.h), FS-OSD and the one-TEP primitive (ldpc_osdx_fs.h) and PB-OSD (ldpc_osdx_pb.h).  The PB tuning and routes and the
+// one-call pipeline stay with the (128,64) kernels of ldpc_osd.hip / ldpc_osd_pb.hip.
 // The G columns and the TEP tables are the context's OsdTables (ldpc_osd_tables.h), the set the (128,64) kernels read as well.
 // There is no library workspace: the decode entry points run their two launches through the caller's d_perm / d_parity, so the
 // calls hold no per-stream state, allocate nothing and are graph-capturable as they are.
+#include <cmath>
+
 #include "ldpc_osdx_fs.h"
+#include "ldpc_osdx_pb.h"
 
 namespace ldpc {
 
@@ -79,6 +82,38 @@ static int osdx_launch_fs(ldpc_ctx *ctx, const float *d_y, const int32_t *d_inde
     return LDPC_OK;
 }
 
+// every check of the PB entry points before a launch; `required`: the pointers a call with F > 0 needs
+static int osdx_pb_check(const ldpc_ctx *ctx, const ldpc_osd_params *p, int64_t F, std::initializer_list<NamedPtr> required, const char *who)
+{
+    if (!ctx || F < 0) return fail(LDPC_E_ARG, "%s: bad arguments", who);
+    if (int rc = need_osdx(ctx)) return rc;
+    if (!p) return fail(LDPC_E_ARG, "%s: params is NULL", who);
+    if (p->algo != LDPC_OSD_PB) return fail(LDPC_E_ARG, "%s: algo %d is not LDPC_OSD_PB", who, p->algo);
+    const int omax = ctx->osd_tables.k < 3 ? ctx->osd_tables.k : 3;
+    if (p->order < 0 || p->order > omax) return fail(LDPC_E_ARG, "%s: order %d outside 0..%d", who, p->order, omax);
+    if (p->flags != 0) return fail(LDPC_E_ARG, "%s: flags 0x%x are not served here (flags must be 0)", who, (unsigned)p->flags);
+    if (p->y_frames != 0) return fail(LDPC_E_ARG, "%s: y_frames %lld is not served here (it must be 0)", who, (long long)p->y_frames);
+    return F > 0 ? first_null(who, required) : LDPC_OK;
+}
+
+static int osdx_launch_pb(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                          const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *p, uint64_t *d_cw, float *d_metric,
+                          int32_t *d_best, int32_t *d_ntep, OsdxCounting c, hipStream_t s)
+{
+    const OsdTables &t = ctx->osd_tables;
+    PbxParams pp;
+    pp.order = p->order;
+    pp.nmax = (int)t.ntep[p->order];
+    pp.c4 = (float)(-4.0 * (1.0 / pow(10.0, (double)p->snr_db / 10.0)));    // -4 * noise_variance, pb_testing.py:50-52
+    // the frontier's LDS is sized by the order: 64 slots up to order 2, 2048 for order 3
+    const auto kern = p->order == 3 ? osdx_pb_kernel<true> : osdx_pb_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(osdx_grid(F)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, t.n, t.k, d_perm,
+                       reinterpret_cast<const u64 *>(d_parity), t.d_pb, pp, reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_ntep,
+                       static_cast<int *>(p->d_aux), c.label, c.counts);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
 }  // namespace ldpc
 
 using namespace ldpc;
@@ -142,6 +177,28 @@ int ldpc_osdx_fs_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
     if (F == 0) return LDPC_OK;
     if (int rc = osdx_launch_front(ctx, d_y, d_index, d_count, F, d_perm, d_parity, nullptr, (hipStream_t)stream)) return rc;
     return osdx_launch_fs(ctx, d_y, d_index, d_count, F, d_perm, d_parity, params, d_cw, d_metric, d_best, d_ntep,
+                          osdx_counting(d_label_bits, d_counts), (hipStream_t)stream);
+}
+
+int ldpc_osdx_pb_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F, const uint8_t *d_perm,
+                        const uint64_t *d_parity, const ldpc_osd_params *params, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                        int32_t *d_ntep, void *stream)
+{
+    if (int rc = osdx_pb_check(ctx, params, F, {{"d_y", d_y}, {"d_perm", d_perm}, {"d_parity", d_parity}, {"d_cw", d_cw}},
+                               "ldpc_osdx_pb_search")) return rc;
+    if (F == 0) return LDPC_OK;
+    return osdx_launch_pb(ctx, d_y, d_index, d_count, F, d_perm, d_parity, params, d_cw, d_metric, d_best, d_ntep, {}, (hipStream_t)stream);
+}
+
+int ldpc_osdx_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const ldpc_osd_params *params, uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw, float *d_metric,
+                        int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits, int64_t *d_counts, void *stream)
+{
+    if (int rc = osdx_pb_check(ctx, params, F, {{"d_y", d_y}, {"d_perm", d_perm}, {"d_parity", d_parity}, {"d_cw", d_cw}},
+                               "ldpc_osdx_pb_decode")) return rc;
+    if (F == 0) return LDPC_OK;
+    if (int rc = osdx_launch_front(ctx, d_y, d_index, d_count, F, d_perm, d_parity, nullptr, (hipStream_t)stream)) return rc;
+    return osdx_launch_pb(ctx, d_y, d_index, d_count, F, d_perm, d_parity, params, d_cw, d_metric, d_best, d_ntep,
                           osdx_counting(d_label_bits, d_counts), (hipStream_t)stream);
 }
 

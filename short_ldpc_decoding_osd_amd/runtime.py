@@ -389,6 +389,31 @@ class Decoder:
         out["perm"], out["parity"] = perm, parity
         return out
 
+    def osdx_pb_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
+        """PB-OSD on front-end results of any supported shape.  ``params``: ``osd_params(order, _lib.OSD_PB, snr_db=...,
+        aux=...)``, order 0..min(3, k); ``aux`` ([F, 4] int32, optional) receives {frontier comparisons, suc1, suc2, stop
+        reason} per frame.  Returns the dict of ``osdx_search`` (best: rank in visit order, 0 = the all-zero TEP; ntep:
+        cost_tep_num, or N_max when no rule fired)."""
+        F = self._osd_front_results(y, perm, parity, F)
+        out = self._osd_outputs(out, F)
+        _lib.check(self.L.ldpc_osdx_pb_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
+                                              C.byref(params), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
+                                              _ptr(out["ntep"]), self._stream()), "ldpc_osdx_pb_search")
+        return out
+
+    def osdx_pb_decode(self, y, params, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
+                       out=None):
+        """Front end + PB-OSD of the frames y[index[f]] (or y[f]) for any supported shape: ``osdx_decode`` with the search
+        of ``osdx_pb_search``; ``perm`` / ``parity`` / ``label_bits`` / ``counts`` as there."""
+        F, perm, parity = self._osdx_decode_args(y, index, F, perm, parity)
+        out = self._osd_outputs(out, F)
+        _lib.check(self.L.ldpc_osdx_pb_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, C.byref(params), _ptr(perm),
+                                              _ptr(parity), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
+                                              _ptr(out["ntep"]), _ptr(label_bits), _ptr(counts), self._stream()),
+                   "ldpc_osdx_pb_decode")
+        out["perm"], out["parity"] = perm, parity
+        return out
+
     def osdx_tep_eval(self, y, perm, parity, mask, index=None, count=None):
         """``osd_tep_eval`` for any supported shape (mask [F] int64: bit p < k flips primed MRB position p).
         Returns dict(cw[F,words] int64 original bit order, metric[F] f32, hd[F] i32)."""
