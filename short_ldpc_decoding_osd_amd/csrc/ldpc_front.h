@@ -25,6 +25,7 @@ struct FrontResult {
 
 // sort + column gather + elimination + bookkeeping of one frame (one wavefront); results in registers
 // (a1 / a2: the magnitude bits of y[lane] / y[64 + lane])
+template <bool GE_LANE_OPAQUE = false>
 __device__ __forceinline__ FrontResult front_device_vals(FrontLds &L, unsigned a1, unsigned a2, const u64 *__restrict__ Gcols, int lane)
 {
     // ---- reliability sort: rank of each |y| in descending order, ties -> lower index ------
@@ -41,7 +42,15 @@ __device__ __forceinline__ FrontResult front_device_vals(FrontLds &L, unsigned a
     u64 C1 = Gcols[L.pi1[lane]];
     u64 C2 = Gcols[L.pi1[lane + 64]];
     int rho = lane, idx1 = lane, idx2 = lane + 64;
-    const int ns = ge_columns(C1, C2, rho, idx1, idx2, lane, nullptr);
+    // The elimination compares the lane number with each of its 64 step numbers, in the exchange path only (a step in thirty).
+    // Given the kernel's own `lane`, the compiler computes all 64 compares ahead of osd_front_kernel's frame loop and parks 37
+    // of the 64 SGPR pairs in lanes of two VGPRs: 64 v_cmp + 74 v_writelane per workgroup -- which is per frame when the grid
+    // covers the frames -- and a v_readlane pair wherever one is used.  GE_LANE_OPAQUE hands the elimination a copy of the
+    // lane number that the compiler cannot see through (an empty asm, no instruction), so each compare stays in the block
+    // that uses it.  For osd_front_kernel only: in osd_fused2r_kernel, at 128 VGPRs, the same copy moves eight VGPRs to scratch.
+    int ge_lane = lane;
+    if constexpr (GE_LANE_OPAQUE) asm volatile("" : "+v"(ge_lane));
+    const int ns = ge_columns(C1, C2, rho, idx1, idx2, ge_lane, nullptr);
     // ---- identify_mrb bookkeeping (pb_testing.py:276-304) --------------------------------
     // (no column exchange -- the 64 most reliable columns were independent: a quarter of the frames -- leaves every index
     //  where the sort put it: the ranks are the lane numbers and the membership mask is not needed)
@@ -68,10 +77,11 @@ __device__ __forceinline__ FrontResult front_device_vals(FrontLds &L, unsigned a
     return res;
 }
 
+template <bool GE_LANE_OPAQUE = false>
 __device__ __forceinline__ FrontResult front_device(FrontLds &L, const float *__restrict__ y, long long src,
                                                     const u64 *__restrict__ Gcols, int lane)
 {
-    return front_device_vals(L, __float_as_uint(y[src * 128 + lane]) & 0x7FFFFFFFu, __float_as_uint(y[src * 128 + 64 + lane]) & 0x7FFFFFFFu, Gcols, lane);
+    return front_device_vals<GE_LANE_OPAQUE>(L, __float_as_uint(y[src * 128 + lane]) & 0x7FFFFFFFu, __float_as_uint(y[src * 128 + 64 + lane]) & 0x7FFFFFFFu, Gcols, lane);
 }
 
 

@@ -246,16 +246,21 @@ int osd_launch(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const in
     u64 *const counts = label ? reinterpret_cast<u64 *>(d_counts) : nullptr;
     const unsigned g2r = grid2r(ctx, F), g64 = frame_grid(F);
     switch (r.route) {
-    case OsdRoute::Fused2r:
-        hipLaunchKernelGGL(osd_fused2r_kernel, dim3(g2r), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
-                           t.d_Gcols, ctx->dpp_wave_rol_dir, st->d_base2, cw, d_metric, d_best, d_ntep, label, counts);
+    case OsdRoute::Fused2r: {
+        // (the probed wave_rol:1 direction picks the instantiation; select_route leaves 0 to the read-lane scan)
+        const auto kernel = ctx->dpp_wave_rol_dir > 0 ? osd_fused2r_kernel<1> : osd_fused2r_kernel<-1>;
+        hipLaunchKernelGGL(kernel, dim3(g2r), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, t.d_Gcols, st->d_base2, cw, d_metric,
+                           d_best, d_ntep, label, counts);
         *counted = label != nullptr;
         break;
-    case OsdRoute::Search2r:
-        hipLaunchKernelGGL(osd_search2r_kernel, dim3(g2r), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity,
-                           ctx->dpp_wave_rol_dir, st->d_base2, cw, d_metric, d_best, d_ntep, label, counts);
+    }
+    case OsdRoute::Search2r: {
+        const auto kernel = ctx->dpp_wave_rol_dir > 0 ? osd_search2r_kernel<1> : osd_search2r_kernel<-1>;
+        hipLaunchKernelGGL(kernel, dim3(g2r), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity, st->d_base2, cw, d_metric,
+                           d_best, d_ntep, label, counts);
         *counted = label != nullptr;
         break;
+    }
     case OsdRoute::Search2:
         hipLaunchKernelGGL(osd_search2_kernel, dim3(g64), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity, st->d_base2,
                            cw, d_metric, d_best, d_ntep);

@@ -38,11 +38,15 @@ __device__ __forceinline__ float cost2r(const Search2rLds &L, float mrb, u64 D)
 
 __device__ __forceinline__ int wave_rot1(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x134, 0xF, 0xF, true); }
 
-__device__ __forceinline__ void search2r_finish_batch(const Search2rLds &L, uint2 e, bool valid, int dir, u64 d0, const int *__restrict__ base2,
+// (DIR: the probed direction of wave_rol:1, +1 or -1 -- a template parameter of the rotation kernels, so the partner of a
+//  survivor is an add or a subtract; as a kernel argument it was a v_mul_lo_u32 per batch and lane)
+template <int DIR>
+__device__ __forceinline__ void search2r_finish_batch(const Search2rLds &L, uint2 e, bool valid, u64 d0, const int *__restrict__ base2,
                                                       float &best, int &bi, int &bj, u64 &bestD)
 {
+    static_assert(DIR == 1 || DIR == -1, "wave_rol:1 direction");
     if (!valid) return;
-    const int r = (int)(e.y >> 6), l = (int)(e.y & 63), m = (l - dir * r) & 63;
+    const int r = (int)(e.y >> 6), l = (int)(e.y & 63), m = (DIR > 0 ? l - r : l + r) & 63;
     const u64 D = d0 ^ L.P[l] ^ L.P[m];
     float acc = __uint_as_float(e.x);
     acc = acc + lut_byte<2>(L.lut, D); acc = acc + lut_byte<3>(L.lut, D); acc = acc + lut_byte<4>(L.lut, D);
@@ -89,7 +93,8 @@ __device__ __forceinline__ bool search2r_round(Search2rLds &LL, Scan2r &s, int R
 // the whole candidate from the P' rows in LDS.  The 32 rounds are unrolled (round number, id and the half-lane rule of round
 // 32 are constants, no loop counter, no pipeline copies).  The ring is not circular: a batch takes slots 0..63 and moves the < 64 entries behind them
 // down to slot 0, so an append is "slot = qn + mbcnt" with no wrap-around.
-__device__ __forceinline__ void search2r_device(Search2rLds &LL, const SearchFrame &S, u64 Pl, float wl, int dir,
+template <int DIR>
+__device__ __forceinline__ void search2r_device(Search2rLds &LL, const SearchFrame &S, u64 Pl, float wl,
                                                 const int *__restrict__ base2, int lane, float &best_out, int &rank_out,
                                                 u64 &D_out, u64 &E_out)
 {
@@ -113,13 +118,13 @@ __device__ __forceinline__ void search2r_device(Search2rLds &LL, const SearchFra
             const uint2 e = LL.q[lane], rest = LL.q[64 + lane];
             s.qn -= 64;
             if (lane < s.qn) LL.q[lane] = rest;
-            search2r_finish_batch(L, e, true, dir, S.d0, base2, best, bi, bj, bestD);
+            search2r_finish_batch<DIR>(L, e, true, S.d0, base2, best, bi, bj, bestD);
             s.bound = wave_min_f32(best);
             wave_fence();
         }
     }
     wave_fence();
-    search2r_finish_batch(L, LL.q[lane], lane < s.qn, dir, S.d0, base2, best, bi, bj, bestD);
+    search2r_finish_batch<DIR>(L, LL.q[lane], lane < s.qn, S.d0, base2, best, bi, bj, bestD);
     wave_fence();
     int bestt = tep2_rank(bi, bj, base2);
     u64 bestE = (bi >= 0 ? 1ull << bi : 0ull) | (bj >= 0 ? 1ull << bj : 0ull);
@@ -130,7 +135,8 @@ __device__ __forceinline__ void search2r_device(Search2rLds &LL, const SearchFra
 // The frame body of both rotation-paired order-2 kernels (osd_search2r_kernel, osd_fused2r_kernel): the scan of frame f on
 // (o1, o2, P'[lane], y1 = y'[lane], y2 = y'[64 + lane]), its outputs, and -- with counts -- the wrong-codeword counter
 // against lab (the label word of lane 0 / 1).
-__device__ __forceinline__ void search2r_frame(Search2rLds &LL, int o1, int o2, u64 Pl, float y1, float y2, int dir, const int *base2,
+template <int DIR>
+__device__ __forceinline__ void search2r_frame(Search2rLds &LL, int o1, int o2, u64 Pl, float y1, float y2, const int *base2,
                                                long long f, u64 lab, int lane, u64 *cw_out, float *metric_out, int *best_out,
                                                int *ntep_out, u64 *counts)
 {
@@ -145,7 +151,7 @@ __device__ __forceinline__ void search2r_frame(Search2rLds &LL, int o1, int o2, 
     S.d0 = wave_xor64(((S.hm >> lane) & 1) ? Pl : 0ull) ^ S.hp;
     wave_fence();
     float best; int bestt; u64 bestD, bestE;
-    search2r_device(LL, S, Pl, w1, dir, base2, lane, best, bestt, bestD, bestE);
+    search2r_device<DIR>(LL, S, Pl, w1, base2, lane, best, bestt, bestD, bestE);
     {   // search_finish, with the codeword words still in hand for the success test (convention_osd.py:65-66)
         const u64 mrb_bits = S.hm ^ bestE, par_bits = bestD ^ S.hp;
         u64 *const cw = LL.cw();
@@ -180,9 +186,10 @@ __device__ __forceinline__ void count_up_front(u64 *__restrict__ counts, long lo
 // they are looked at: 129 us; static: 102 us (the wavefronts are then alive for ~63 % of the launch: the scan time
 // varies with the number of survivors) -- so the balance comes from the hardware dispatcher instead: the grid is 6x
 // the resident wavefronts (see the launcher).
+template <int DIR>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void osd_search2r_kernel(const float *__restrict__ y,
         const int *__restrict__ index, const int *__restrict__ count, long long F, const unsigned char *__restrict__ perm_in,
-        const u64 *__restrict__ parity_in, int dir, const int *__restrict__ base2, u64 *__restrict__ cw_out, float *__restrict__ metric_out,
+        const u64 *__restrict__ parity_in, const int *__restrict__ base2, u64 *__restrict__ cw_out, float *__restrict__ metric_out,
         int *__restrict__ best_out, int *__restrict__ ntep_out, const u64 *__restrict__ label, u64 *__restrict__ counts)
 {
     __shared__ Search2rLds LL;
@@ -219,7 +226,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void os
             srcc = index ? index[f2] : f2;
         }
         // ---- frame f0
-        search2r_frame(LL, o1a, o2a, Pa, y1a, y2a, dir, base2, f0, laba, lane, cw_out, metric_out, best_out, ntep_out, counts);
+        search2r_frame<DIR>(LL, o1a, o2a, Pa, y1a, y2a, base2, f0, laba, lane, cw_out, metric_out, best_out, ntep_out, counts);
         // ---- rotate the pipeline
         f0 = f1; f1 = f2; f2 += G;
         o1a = o1b; o2a = o2b; Pa = Pb; srca = srcb; y1a = y1b; y2a = y2b; laba = labb;
@@ -235,8 +242,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void os
 // algorithmic: 5.1x); this form reads 512 B and writes 24 B per frame.  The front end's 3.6 KiB of LDS lie inside the
 // scan's LUT area (built afterwards), the frame's y row in its P' rows (filled afterwards): 9.5 KiB, 16 wavefronts per CU.
 // ---------------------------------------------------------------------------------------
+template <int DIR>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void osd_fused2r_kernel(const float *__restrict__ y,
-        const int *__restrict__ index, const int *__restrict__ count, long long F, const u64 *__restrict__ Gcols, int dir,
+        const int *__restrict__ index, const int *__restrict__ count, long long F, const u64 *__restrict__ Gcols,
         const int *__restrict__ base2, u64 *__restrict__ cw_out, float *__restrict__ metric_out, int *__restrict__ best_out,
         int *__restrict__ ntep_out, const u64 *__restrict__ label, u64 *__restrict__ counts)
 {
@@ -269,7 +277,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void os
         const float y1 = yrow[fr.o1], y2 = yrow[fr.o2];            // y'[p] = y[perm[p]]
         wave_fence();
         // ---- scan
-        search2r_frame(LL, fr.o1, fr.o2, fr.Prow, y1, y2, dir, base2, f0, laba, lane, cw_out, metric_out, best_out, ntep_out, counts);
+        search2r_frame<DIR>(LL, fr.o1, fr.o2, fr.Prow, y1, y2, base2, f0, laba, lane, cw_out, metric_out, best_out, ntep_out, counts);
         f0 = f1; f1 = f2; f2 += G;
         srca = srcb; srcb = srcc; ya1 = yb1; ya2 = yb2; laba = labb;
     }

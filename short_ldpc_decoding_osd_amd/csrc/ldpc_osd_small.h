@@ -44,7 +44,7 @@ __global__ __launch_bounds__(64) void osd_front_kernel(const float *__restrict__
 
     for (long long f = blockIdx.x; f < nframes; f += gridDim.x) {
         const long long src = index ? index[f] : f;
-        const FrontResult res = front_device(L, y, src, Gcols, lane);
+        const FrontResult res = front_device<true>(L, y, src, Gcols, lane);     // (true: see GE_LANE_OPAQUE, ldpc_front.h)
         perm_out[f * 128 + lane] = (unsigned char)res.o1;
         perm_out[f * 128 + 64 + lane] = (unsigned char)res.o2;
         parity_out[f * 64 + lane] = res.Prow;

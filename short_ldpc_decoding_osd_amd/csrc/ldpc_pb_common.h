@@ -75,9 +75,10 @@ struct PbList {
 };
 
 // wave arg-min on (sum, index): lower index wins ties; result in every lane
+// (the minimum is handed on as a value, hence the float form of the reduction: see wave_min_f32, ldpc_wave.h)
 __device__ __forceinline__ void argmin_si(float &s, int &idx, int lane)
 {
-    const float m = wave_min_f32(s);
+    const float m = wave_min_f32_value(s);
     idx = wave_min_i32(s == m ? idx : 0x7FFFFFFF);
     s = m;
 }

@@ -45,21 +45,31 @@ __device__ __forceinline__ int wave_lane_rank(u64 mask, unsigned base = 0u)
 // ds_bpermute shuffles (~30 cycles per wave-instruction on gfx950, profiles/r01/ubench_valu_issue.txt).
 // Pattern: xor-1, xor-2 quad permutes, row_half_mirror, row_mirror -> every lane holds its row's result;
 // row_bcast:15 into rows 1,3 and row_bcast:31 into rows 2,3 -> lane 63 holds the wave's result.
+// Every step is ONE instruction (v_<op>_dpp): in the four full permutes every lane has a source, so `old` is never used and
+// bound_ctrl may be set, which lets the compiler fold the move into the operation (with old = v and bound_ctrl off it kept
+// v_mov + v_mov_dpp + op, profiles/osd_trim/README.md); the two row_bcast steps write rows 1,3 / 2,3 only and pass the
+// operation's identity ID as `old` for the rows they skip.
 template <int CTRL, int ROWMASK>
 __device__ __forceinline__ int dpp_i(int old, int x)
 {
     return __builtin_amdgcn_update_dpp(old, x, CTRL, ROWMASK, 0xF, false);
 }
+template <int CTRL>
+__device__ __forceinline__ int dpp_perm(int x)   // a permute in which every lane has a source
+{
+    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true);
+}
 #define LDPC_WAVE_REDUCE(v, OP)                                   \
-    v = OP(v, dpp_i<0xB1, 0xF>(v, v));  /* quad_perm [1,0,3,2] */ \
-    v = OP(v, dpp_i<0x4E, 0xF>(v, v));  /* quad_perm [2,3,0,1] */ \
-    v = OP(v, dpp_i<0x141, 0xF>(v, v)); /* row_half_mirror */     \
-    v = OP(v, dpp_i<0x140, 0xF>(v, v)); /* row_mirror */          \
+    v = OP(v, dpp_perm<0xB1>(v));  /* quad_perm [1,0,3,2] */      \
+    v = OP(v, dpp_perm<0x4E>(v));  /* quad_perm [2,3,0,1] */      \
+    v = OP(v, dpp_perm<0x141>(v)); /* row_half_mirror */          \
+    v = OP(v, dpp_perm<0x140>(v)); /* row_mirror */               \
     v = OP(v, dpp_i<0x142, 0xA>(ID, v)); /* row_bcast:15 */       \
     v = OP(v, dpp_i<0x143, 0xC>(ID, v)); /* row_bcast:31 */
 
 __device__ __forceinline__ int op_xor(int a, int b) { return a ^ b; }
 __device__ __forceinline__ int op_min_i(int a, int b) { return a < b ? a : b; }
+__device__ __forceinline__ int op_min_u(int a, int b) { return (unsigned)a < (unsigned)b ? a : b; }
 __device__ __forceinline__ int op_min_f(int a, int b) { return __float_as_int(__builtin_fminf(__int_as_float(a), __int_as_float(b))); }
 
 // XOR of a 64-bit value over the wave, result in every lane
@@ -70,8 +80,22 @@ __device__ __forceinline__ u64 wave_xor64(u64 x)
     const unsigned rl = __builtin_amdgcn_readlane(lo, 63), rh = __builtin_amdgcn_readlane(hi, 63);
     return ((u64)rh << 32) | rl;
 }
-// minimum of non-negative-or-inf floats over the wave, result in every lane
+// Minimum over the wave of metrics and bounds, result in every lane -- for a result that is only COMPARED against.  Every caller
+// passes a sum of magnitudes or +inf: a value with the sign bit clear, whose bit pattern orders as the value does, so the
+// reduction is the unsigned integer minimum of the patterns (v_min_u32_dpp; fminf costs a canonicalising v_max per step
+// on top).  Non-finite channel values can make a lane's value a NaN.  Its pattern lies above +inf's, with either sign, so the
+// integer minimum passes it over exactly as fminf does while any lane holds a number; when every lane holds a NaN the result
+// is one of them, as before, possibly with another payload -- and every comparison with it is false whatever the payload.
+// (A minimum that is passed on as a value: wave_min_f32_value.)
 __device__ __forceinline__ float wave_min_f32(float x)
+{
+    int v = __float_as_int(x);
+    { const int ID = -1; LDPC_WAVE_REDUCE(v, op_min_u) }
+    return __int_as_float(__builtin_amdgcn_readlane(v, 63));
+}
+// The same as a float operation (fminf at every step), for the one caller that hands the minimum on as a result (argmin_si,
+// ldpc_pb_common.h): there the NaN that an all-NaN wave yields must stay the one fminf forms.
+__device__ __forceinline__ float wave_min_f32_value(float x)
 {
     int v = __float_as_int(x);
     { const int ID = 0x7F800000; LDPC_WAVE_REDUCE(v, op_min_f) }
@@ -93,6 +117,7 @@ __device__ __forceinline__ int wave_max_i32(int x)
 __device__ __forceinline__ int op_max_f(int a, int b) { return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b))); }
 __device__ __forceinline__ int op_add_i(int a, int b) { return a + b; }
 // maximum of floats >= -1 over the wave / sum of ints over the wave, result in every lane
+// (wave_max_f32 stays a float operation, canonicalisations included: values in [-1, 0) do not order as their bit patterns)
 __device__ __forceinline__ float wave_max_f32(float x)
 {
     int v = __float_as_int(x);
@@ -131,6 +156,8 @@ __device__ __forceinline__ float wave_incl_addf_dpp(float x)
     return v;
 }
 // inclusive prefix minimum over the lanes, same DPP ladder (a lane without a source keeps its own value)
+// (left a float operation with `old = v`: its prefixes go on into the PB rules as values, see wave_min_f32_value, and a lane
+//  without a source must keep its own value, so bound_ctrl cannot be set here)
 __device__ __forceinline__ float wave_incl_min_dpp(float x)
 {
     int v = __float_as_int(x);
@@ -322,12 +349,23 @@ struct __attribute__((aligned(16))) RankLds {
     int base[64];            // number of keys in higher buckets
 };
 
-// bucket of a magnitude (given as its bit pattern) on a linear scale up to the frame's largest magnitude; monotone in
-// the bits for every input (a NaN lands in the top bucket, as its bit pattern demands)
+// bucket of a magnitude (given as its bit pattern) on a linear scale up to the frame's largest magnitude m; monotone in
+// the bits for every input (a NaN lands in the top bucket, as its bit pattern demands).
+// scale = 63.5 * rcp(m): one v_rcp_f32 (1 ulp) and a multiply where 63.5f / m was the 12-instruction IEEE division.  The
+// ranks are exact for ANY bucket function that is monotone in the key and lands in 0..63 (bucket_ranks), and this one is,
+// whatever the scale: a * scale with scale >= 0 rounds monotonically in a, fminf(., 63.0f) and the conversion keep the order
+// and the range, and fminf turns a NaN product into 63.  The scale only decides how evenly the buckets fill:
+//   ordinary m: a * scale <= m * 63.5 * (1 + 3 ulp) < 64 even before the clamp;
+//   m = 0 (all-zero frame): scale = +inf, every product 0 * inf = NaN -> all keys in bucket 63 (the division gave the same);
+//   m denormal or below ~2^-122: rcp flushes its input or 63.5 * rcp overflows, scale = +inf: zeros (NaN) and the rest (+inf)
+//     all in bucket 63;   m near FLT_MAX: rcp may flush its result, scale = 0: every finite key in bucket 0;
+//   m = +inf: scale = 0, finite keys in bucket 0, the infinities (inf * 0 = NaN) in bucket 63 -- monotone;
+//   m = NaN (its pattern is the largest): scale = NaN, every key in bucket 63.
+// One bucket for all 128 keys is the case bucket_ranks pads its array for (nmax = 128).
 __device__ __forceinline__ float bucket_scale(unsigned a1, unsigned a2)
 {
     const int m = wave_max_i32((int)(a1 > a2 ? a1 : a2));
-    return 63.5f / __int_as_float(m);
+    return 63.5f * __builtin_amdgcn_rcpf(__int_as_float(m));
 }
 __device__ __forceinline__ int bucket_of(unsigned a, float scale) { return (int)__builtin_fminf(__uint_as_float(a) * scale, 63.0f); }
 
@@ -355,17 +393,20 @@ __device__ __forceinline__ void rank_gt(int &r, int a, int k)
     asm("v_cmp_gt_i32_e32 vcc, %2, %1\n\tv_addc_co_u32_e32 %0, vcc, 0, %0, vcc" : "+v"(r) : "v"(a), "v"(k) : "vcc");
 }
 
+// number of set bits of the 128-bit mask strictly below position x, x = 0..128.  The mask is the same in every lane, so its
+// words and the popcounts of the whole words below each of them are scalars (s_bcnt1, once per call pair); a lane selects
+// its word (bits 5, 6 of x) and that word's prefix count (one byte select from the packed counts: byte d of {p4 : p3 p2 p1 0}
+// is the number of set bits in words 0..d-1), masks the word to its low x & 31 bits and counts them.
+// (x = 128: word 0 with an empty bit field, prefix = p4, the whole mask.)
 __device__ __forceinline__ int below_mask(const unsigned (&m)[4], int x)
 {
-    // number of set bits of the 128-bit mask strictly below position x
-    int c = 0;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const int t = x - 32 * d;
-        const unsigned bm = t <= 0 ? 0u : (t >= 32 ? 0xFFFFFFFFu : ((1u << t) - 1u));
-        c += __popc(m[d] & bm);
-    }
-    return c;
+    const unsigned s0 = __builtin_amdgcn_readfirstlane(m[0]), s1 = __builtin_amdgcn_readfirstlane(m[1]);
+    const unsigned s2 = __builtin_amdgcn_readfirstlane(m[2]), s3 = __builtin_amdgcn_readfirstlane(m[3]);
+    const unsigned p1 = __popc(s0), p2 = p1 + __popc(s1), p3 = p2 + __popc(s2), p4 = p3 + __popc(s3);   // <= 32, 64, 96, 128
+    const unsigned pre = __builtin_amdgcn_perm(p4, (p1 << 8) | (p2 << 16) | (p3 << 24), (unsigned)x >> 5);
+    const unsigned w01 = (x & 32) ? s1 : s0, w23 = (x & 32) ? s3 : s2;
+    const unsigned word = (x & 64) ? w23 : w01;
+    return (int)(pre + __popc(__builtin_amdgcn_ubfe(word, 0u, (unsigned)x & 31u)));
 }
 
 // Byte LUTs of partial weight sums: lut[b][v] = sum over the set bits t of v (ascending t) of w[8 b + t].
