@@ -268,6 +268,36 @@ __device__ __forceinline__ unsigned ge_xor_masked(unsigned c, int m, unsigned e)
     return c;
 }
 
+// Exchange of logical rows i and r (i < r) in the row map at step i: lane i gets npr = nrho[r], lane r gets nrho[i], and r is
+// entered in `moved`, the logical positions that have received a displaced row.  A position is written only as the `r` of an
+// exchange (position i is never looked at again after step i), and every caller starts from rho = lane, so while bit i of
+// `moved` is clear lane i still holds its initial 63 - i: the constant replaces v_readlane(nrho, i) -- in 56 % of the
+// exchanges of a CCSDS frame (profiles/ge_known/README.md).  One wave-uniform branch on s_bitcmp1 inside the block; i is an
+// immediate lane select (the step loop is fully unrolled, so i is a constant when the "i" constraint is resolved), r goes
+// through M0 (a VALU instruction may read only one SGPR on gfx9).
+// (s_nop: an SGPR written by v_readlane needs two wait states before a VALU instruction reads it on gfx940/950, and the
+//  compiler does not look inside the block; the v_writelane in between is the other one.)
+__device__ __forceinline__ void ge_exchange_rows(int &nrho, u64 &moved, int i, int r, int npr)
+{
+    int t;
+    asm volatile("s_bitcmp1_b64 %[mv], %[i]\n\t"
+                 "s_mov_b32 m0, %[r]\n\t"
+                 "s_bitset1_b64 %[mv], %[r]\n\t"
+                 "s_cbranch_scc1 1f\n\t"
+                 "v_writelane_b32 %[nrho], %[npr], %[i]\n\t"
+                 "v_writelane_b32 %[nrho], %[ci], m0\n\t"
+                 "s_branch 2f\n"
+                 "1:\n\t"
+                 "v_readlane_b32 %[t], %[nrho], %[i]\n\t"
+                 "v_writelane_b32 %[nrho], %[npr], %[i]\n\t"
+                 "s_nop 0\n\t"
+                 "v_writelane_b32 %[nrho], %[t], m0\n"
+                 "2:"
+                 : [nrho] "+v"(nrho), [mv] "+s"(moved), [t] "=&s"(t)
+                 : [npr] "s"(npr), [r] "s"(r), [i] "i"(i), [ci] "i"(63 - i)
+                 : "m0", "scc");
+}
+
 __device__ __forceinline__ int ge_columns(u64 &C1, u64 &C2, int &rho, int &idx1, int &idx2, int lane,
                                           unsigned char *swaps /* LDS or global [64][2], may be null */)
 {
@@ -275,6 +305,7 @@ __device__ __forceinline__ int ge_columns(u64 &C1, u64 &C2, int &rho, int &idx1,
     bool deficient = false;   // (no early exit from the loop: it would make the compiler guard every step)
     int nrho = 63 - rho;   // the loop carries 63 - rho: "bit rho of cj" is then the sign of cj << nrho
     u64 ge_i = ~0ull;      // lanes (logical rows) >= i
+    u64 moved = 0;         // logical positions that have received a displaced row (ge_exchange_rows)
 #pragma unroll
     for (int i = 0; i < kOsdK; ++i, ge_i <<= 1) {
         u64 cj = readlane64(C1, i);
@@ -311,12 +342,7 @@ __device__ __forceinline__ int ge_columns(u64 &C1, u64 &C2, int &rho, int &idx1,
         }
         const int r = __builtin_ctzll(bal);
         const int npr = __builtin_amdgcn_readlane(nrho, r);
-        if (r != i) {   // exchange logical rows i and r: two lanes of the row map, no data moves
-            const int npi = __builtin_amdgcn_readlane(nrho, i);
-            // (lane select through M0: a VALU instruction may read only one SGPR on gfx9)
-            asm volatile("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(nrho) : "s"(npr), "s"(i) : "m0");
-            asm volatile("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(nrho) : "s"(npi), "s"(r) : "m0");
-        }
+        if (r != i) ge_exchange_rows(nrho, moved, i, r, npr);   // two lanes of the row map, no data moves
         const int pr = 63 - npr;
         const u64 e = ge_clear_bit(cj, pr);
         if (e != 0) {   // nothing to clear when the pivot column is already a unit vector (common: G = [P | I])
