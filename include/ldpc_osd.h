@@ -431,6 +431,36 @@ int ldpc_osdx_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
                         int64_t *d_counts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * OSD for high-rate short codes, i.e. every code with n <= 128 and 1 <= n-k <= 64 (hence every k from 1 to 127): the
+ * reference's (121,80) array code, which the ldpc_osdx_* entry points above refuse for its k > 64.  Served: the front end
+ * and the conventional search, orders 0..3.  Codes with k <= 64 are served as well; there d_perm, d_cw, d_metric, d_best,
+ * d_ntep and d_nswaps equal those of ldpc_osdx_front / _search / _decode bit for bit, and the first 64 rows of d_parity
+ * equal the d_parity of those calls.  FS-OSD, PB-OSD and one-TEP evaluation stay with k <= 64 (ldpc_osdx_*), the one-call
+ * pipeline with (128,64); codes with n-k > 64 or n > 128 are refused by every OSD entry point.
+ * The contract is that of ldpc_osdx_front / _search / _decode -- d_index / d_count, ties of the sort, the pivot rule, the
+ * TEP table of this code's k (first minimum), the float order of the metric, the nullable outputs, d_label_bits with
+ * d_counts[3] as a pair or not at all, teps_total only with d_ntep -- with one layout changed:
+ *   d_perm    [F][128] u8  : original bit at primed position p < n (MRB 0..k-1, parity k..n-1); 0 for p >= n
+ *   d_parity  [F][128] u64 : row r < k, bit c < n-k = P'[r][c]; rows >= k and bits >= n-k are written as 0
+ *   d_cw      [F][ceil(n/64)] u64 best codeword, ORIGINAL bit order
+ * ldpc_osdw_decode is two launches through the caller's d_perm / d_parity, which are scratch AND outputs and required:
+ * no library workspace, no per-stream state.  Before any launch: an unsupported shape is LDPC_E_UNSUPPORTED (the message
+ * names the limits 1 <= n-k <= 64 and n <= 128 and the code's (n,k)), an order outside 0..3 and a NULL in a required
+ * pointer are LDPC_E_ARG (naming the entry point and the pointer), F == 0 is LDPC_OK.  The tables (G columns as two
+ * words each, the order-3 TEP table of k: 341 504 entries at k = 127) are uploaded by ldpc_ctx_create; nothing is
+ * allocated and nothing synchronises in a call (graph-capturable).
+ * ------------------------------------------------------------------------------------- */
+int ldpc_osdw_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
+int ldpc_osdw_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                    uint8_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, void *stream);
+int ldpc_osdw_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                     const uint8_t *d_perm, const uint64_t *d_parity, int32_t order, uint64_t *d_cw, float *d_metric,
+                     int32_t *d_best, int32_t *d_ntep, void *stream);
+int ldpc_osdw_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                     int32_t order, uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw, float *d_metric,
+                     int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits, int64_t *d_counts, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H):
  * DL_OSD_Testing_serial/ordered_statistics_decoding.py and nn_net.py: the per-frame sort / elimination /
  * candidate scan, the scan with the sliding-window early stop, and the bit-wise CNN.

@@ -1,5 +1,6 @@
 """NMS + order-p OSD (conventional, FS-OSD or PB-OSD) of any short code (1 <= k <= 64, 1 <= n-k <= 64): FER before and after the
-OSD, and the two OSD kernels timed.
+OSD, and the two OSD kernels timed.  A high-rate code (k > 64, n <= 128, n-k <= 64) runs the conventional search through the
+ldpc_osdw_* family.
 
     python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2
     python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2 \
@@ -19,6 +20,10 @@ legs and, on a (128,64) code, osd_fs_kernel through ldpc_osd_search on the same 
 Printed then: mean and maximum TEPs per frame next to N_max, the shares of the three stop reasons (0 = no rule fired, 1 = the
 promising rule, 2 = the success rule), osdx_pb_kernel timed like the other legs and, on a (128,64) code, ldpc_osd_search on the
 same frames through the literal replay route (LDPC_OSD_F_PB_REPLAY: the same algorithm) and through the default staged route.
+A code that ldpc_osdx_* refuses and ldpc_osdw_* serves (k > 64, e.g. tests/golden/ArrayCode_N121_K80_r0.66.alist) runs the
+conventional search through ldpc_osdw_decode, osdw_front_kernel and osdw_search_kernel timed like the other legs; --osd fs and
+--osd pb exit with a message there (FS-OSD and PB-OSD stay with k <= 64).  On a code both families serve, the conventional run
+also times the osdw kernels on the same frames in the same run, alternating with the osdx kernels.
 One JSON line at the end."""
 import argparse
 import json
@@ -94,8 +99,12 @@ def main(argv=None):
         args.tau_e = 6.5
 
     dec = Decoder(Code(args.alist) if args.alist else Code(), 0)
-    if not dec.osdx_supported:
-        raise SystemExit(f"osdx_fer: the OSD kernels serve 1 <= k <= 64 and 1 <= n-k <= 64; this code is ({dec.n},{dec.k})")
+    wide = dec.osdw_supported and not dec.osdx_supported     # k > 64: the high-rate family, conventional search only
+    if not dec.osdx_supported and not dec.osdw_supported:
+        raise SystemExit(f"osdx_fer: the OSD kernels serve n <= 128 and 1 <= n-k <= 64; this code is ({dec.n},{dec.k})")
+    if wide and (fs or pb):
+        raise SystemExit(f"osdx_fer: --osd {args.osd} needs 1 <= k <= 64; this code is ({dec.n},{dec.k}), which only the conventional "
+                         "search serves (ldpc_osdw_decode: drop --osd)")
     B = args.frames
     y, labels = make_frames(dec, B, args.seed, args.snr)
     res = dec.nms(y, args.T, args.alpha)
@@ -112,6 +121,8 @@ def main(argv=None):
         aux = torch.zeros((idx.shape[0], 4), dtype=torch.int32, device=dec.device)
         pbp = dec.osd_params(args.order, _lib.OSD_PB, snr_db=args.snr, aux=aux)
         out = dec.osdx_pb_decode(y, pbp, index=idx, count=count, label_bits=labels, counts=counts)
+    elif wide:
+        out = dec.osdw_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
     else:
         out = dec.osdx_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
     torch.cuda.synchronize()
@@ -149,6 +160,14 @@ def main(argv=None):
     front = (out["perm"], out["parity"], None)
     legs = [("osdx_front_kernel", lambda: dec.osdx_front(y, index=idx, count=count, out=front)),
             ("osdx_search_kernel", lambda: dec.osdx_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=out))]
+    if wide:
+        legs = [("osdw_front_kernel", lambda: dec.osdw_front(y, index=idx, count=count, out=front)),
+                ("osdw_search_kernel", lambda: dec.osdw_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=out))]
+    elif not fs and not pb and dec.osdw_supported:       # both families serve the code: the osdw kernels on the same frames
+        outw = dec.osdw_decode(y, args.order, index=idx, count=count)
+        frontw = (outw["perm"], outw["parity"], None)
+        legs += [("osdw_front_kernel", lambda: dec.osdw_front(y, index=idx, count=count, out=frontw)),
+                 ("osdw_search_kernel", lambda: dec.osdw_search(y, outw["perm"], outw["parity"], args.order, index=idx, count=count, out=outw))]
     if fs:
         legs[1] = ("osdx_fs_kernel", lambda: dec.osdx_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out))
         if (dec.n, dec.k) == (128, 64):                  # the specialised kernel on the same front-end results, in the same run

@@ -69,6 +69,7 @@ struct ldpc_ctx {
     // generic NMS tables
     int32_t *d_chk_ptr = nullptr, *d_chk_var = nullptr, *d_var_ptr = nullptr, *d_var_edge = nullptr;
     ldpc::OsdTables osd_tables;    // G columns and TEP tables of any shape with k, n-k <= 64: read by every OSD family
+    ldpc::OsdwTables osdw_tables;  // two-word G columns and the TEP table of k <= 127 (n <= 128, n-k <= 64): the ldpc_osdw_* family
     uint64_t *d_Hcols = nullptr;   // [128] column v of H as a 64-bit word (bit r = H[r][v]); n = 128, m = 64 only
     bool dpp_ror_up = true;        // probed: row_ror:n moves data towards higher lanes
     int dpp_wave_rol_dir = 0;      // probed: wave_rol:1 -- +1 lane j receives lane j-1, -1 lane j+1, 0 unusable

@@ -365,6 +365,53 @@ class Decoder:
         out["perm"], out["parity"] = perm, parity
         return out
 
+    # ------------------------------------------------------------------ OSD for high-rate short codes (k up to 127)
+    @property
+    def osdw_supported(self):
+        """Whether the ``osdw_*`` methods serve this code (n <= 128 and 1 <= n-k <= 64)."""
+        return bool(self.L.ldpc_osdw_supported(self._ctx))
+
+    def osdw_front(self, y, index=None, count=None, F=None, out=None):
+        """``osdx_front`` for every code with n <= 128 and 1 <= n-k <= 64.  Returns (perm[F,128] u8, parity[F,128] int64: rows
+        r < k of P', bits c < n-k, 0 elsewhere; nswaps[F] int32); ``out`` may carry those three preallocated (nswaps may be
+        None)."""
+        F = self._osd_frames(y, index, F)
+        if out is not None:
+            perm, parity, ns = out
+        else:
+            perm, parity, ns = self.empty((F, 128), torch.uint8), self.empty((F, 128), torch.int64), self.empty((F,), torch.int32)
+        _lib.check(self.L.ldpc_osdw_front(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(ns),
+                                          self._stream()), "ldpc_osdw_front")
+        return perm, parity, ns
+
+    def osdw_search(self, y, perm, parity, order, index=None, count=None, F=None, out=None):
+        """Conventional order-``order`` search on the results of ``osdw_front`` (perm [F,128] u8, parity [F,128] int64).
+        Returns the dict of ``osdx_search``."""
+        self._chk(y, torch.float32, (self.n,), "y")
+        self._chk(perm, torch.uint8, (128,), "perm")
+        self._chk(parity, torch.int64, (128,), "parity")
+        F = perm.shape[0] if F is None else F
+        out = self._osd_outputs(out, F)
+        _lib.check(self.L.ldpc_osdw_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), int(order),
+                                           _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
+                                           self._stream()), "ldpc_osdw_search")
+        return out
+
+    def osdw_decode(self, y, order, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
+                    out=None):
+        """``osdx_decode`` for every code with n <= 128 and 1 <= n-k <= 64: front end + conventional order-``order`` search,
+        two launches through ``perm`` [F,128] u8 / ``parity`` [F,128] int64 (allocated when not given; returned in the
+        dict); ``label_bits`` / ``counts`` as there."""
+        F = self._osd_frames(y, index, F)
+        perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
+        parity = self.empty((F, 128), torch.int64) if parity is None else self._chk(parity, torch.int64, (128,), "parity")
+        out = self._osd_outputs(out, F)
+        _lib.check(self.L.ldpc_osdw_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, int(order), _ptr(perm), _ptr(parity),
+                                           _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
+                                           _ptr(label_bits), _ptr(counts), self._stream()), "ldpc_osdw_decode")
+        out["perm"], out["parity"] = perm, parity
+        return out
+
     def osdx_fs_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
         """FS-OSD on front-end results of any supported shape.  ``params``: ``osd_params(order, _lib.OSD_FS, fs_beta=...,
         fs_tau_e=..., fs_tau_psc=..., fs_reference_quirk=...)``, order 0..min(3, k).  Returns the dict of ``osdx_search``
