@@ -432,11 +432,11 @@ int ldpc_osdx_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
 
 /* ---------------------------------------------------------------------------------------
  * OSD for high-rate short codes, i.e. every code with n <= 128 and 1 <= n-k <= 64 (hence every k from 1 to 127): the
- * reference's (121,80) array code, which the ldpc_osdx_* entry points above refuse for its k > 64.  Served: the front end
- * and the conventional search, orders 0..3.  Codes with k <= 64 are served as well; there d_perm, d_cw, d_metric, d_best,
- * d_ntep and d_nswaps equal those of ldpc_osdx_front / _search / _decode bit for bit, and the first 64 rows of d_parity
- * equal the d_parity of those calls.  FS-OSD, PB-OSD and one-TEP evaluation stay with k <= 64 (ldpc_osdx_*), the one-call
- * pipeline with (128,64); codes with n-k > 64 or n > 128 are refused by every OSD entry point.
+ * reference's (121,80) array code, which the ldpc_osdx_* entry points above refuse for its k > 64.  Served: the front end,
+ * the conventional search (orders 0..3), FS-OSD (orders 0..min(3, k)) and one-TEP evaluation.  Codes with k <= 64 are served
+ * as well; there d_perm, d_cw, d_metric, d_best, d_ntep, d_hd and d_nswaps equal those of the ldpc_osdx_* call of the same
+ * name bit for bit, and the first 64 rows of d_parity equal the d_parity of those calls.  PB-OSD stays with k <= 64
+ * (ldpc_osdx_pb_*), the one-call pipeline with (128,64); codes with n-k > 64 or n > 128 are refused by every OSD entry point.
  * The contract is that of ldpc_osdx_front / _search / _decode -- d_index / d_count, ties of the sort, the pivot rule, the
  * TEP table of this code's k (first minimum), the float order of the metric, the nullable outputs, d_label_bits with
  * d_counts[3] as a pair or not at all, teps_total only with d_ntep -- with one layout changed:
@@ -447,8 +447,19 @@ int ldpc_osdx_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
  * no library workspace, no per-stream state.  Before any launch: an unsupported shape is LDPC_E_UNSUPPORTED (the message
  * names the limits 1 <= n-k <= 64 and n <= 128 and the code's (n,k)), an order outside 0..3 and a NULL in a required
  * pointer are LDPC_E_ARG (naming the entry point and the pointer), F == 0 is LDPC_OK.  The tables (G columns as two
- * words each, the order-3 TEP table of k: 341 504 entries at k = 127) are uploaded by ldpc_ctx_create; nothing is
- * allocated and nothing synchronises in a call (graph-capturable).
+ * words each, the order-3 TEP table of k: 341 504 entries at k = 127, and the FS visit order of k: 341 503 entries) are
+ * uploaded by ldpc_ctx_create; nothing is allocated and nothing synchronises in a call (graph-capturable).
+ * ldpc_osdw_fs_search / _fs_decode / _tep_eval: the contract of ldpc_osdx_fs_search / _fs_decode / _tep_eval, word for word
+ * -- `params` read for order, algo, fs_beta, fs_tau_e, fs_tau_psc and fs_reference_quirk; the lower bound of weight w the
+ * sum of |y'| at positions k-w .. k-1 (ascending from 0.0f, on either side of position 64) plus
+ * (float)((double)fs_beta * (n-k)); d_best the rank in visit order (0 = the all-zero TEP), d_ntep num_teps; with
+ * fs_reference_quirk = 0 a tau_e stop returns the stopping candidate, its own metric and its rank; LDPC_E_ARG, naming the
+ * offender, for algo != LDPC_OSD_FS, an order outside 0..min(3, k), flags != 0, d_aux != NULL, y_frames != 0 and a NULL in
+ * a required pointer; ldpc_osdw_fs_decode is ldpc_osdw_front plus the scan, two launches -- with d_parity [F][128] u64 as
+ * above and
+ *   d_mask    [F][2] u64 : bit p of word 0 flips MRB position p, bit p of word 1 flips position 64 + p; bits at or
+ *                          beyond k are ignored (for k <= 64 that is all of word 1)
+ *   d_metric  [F] f32 and d_hd [F] i32 of ldpc_osdw_tep_eval: nullable, each on its own
  * ------------------------------------------------------------------------------------- */
 int ldpc_osdw_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
 int ldpc_osdw_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
@@ -459,6 +470,17 @@ int ldpc_osdw_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, co
 int ldpc_osdw_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
                      int32_t order, uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw, float *d_metric,
                      int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits, int64_t *d_counts, void *stream);
+
+int ldpc_osdw_fs_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *params, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, void *stream);
+int ldpc_osdw_fs_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const ldpc_osd_params *params, uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits,
+                        int64_t *d_counts, void *stream);
+int ldpc_osdw_tep_eval(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                       const uint8_t *d_perm, const uint64_t *d_parity, const uint64_t *d_mask, uint64_t *d_cw,
+                       float *d_metric, int32_t *d_hd, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H):

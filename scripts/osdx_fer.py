@@ -1,6 +1,6 @@
 """NMS + order-p OSD (conventional, FS-OSD or PB-OSD) of any short code (1 <= k <= 64, 1 <= n-k <= 64): FER before and after the
-OSD, and the two OSD kernels timed.  A high-rate code (k > 64, n <= 128, n-k <= 64) runs the conventional search through the
-ldpc_osdw_* family.
+OSD, and the two OSD kernels timed.  A high-rate code (k > 64, n <= 128, n-k <= 64) runs the conventional search or FS-OSD
+through the ldpc_osdw_* family.
 
     python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2
     python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2 \
@@ -21,9 +21,11 @@ Printed then: mean and maximum TEPs per frame next to N_max, the shares of the t
 promising rule, 2 = the success rule), osdx_pb_kernel timed like the other legs and, on a (128,64) code, ldpc_osd_search on the
 same frames through the literal replay route (LDPC_OSD_F_PB_REPLAY: the same algorithm) and through the default staged route.
 A code that ldpc_osdx_* refuses and ldpc_osdw_* serves (k > 64, e.g. tests/golden/ArrayCode_N121_K80_r0.66.alist) runs the
-conventional search through ldpc_osdw_decode, osdw_front_kernel and osdw_search_kernel timed like the other legs; --osd fs and
---osd pb exit with a message there (FS-OSD and PB-OSD stay with k <= 64).  On a code both families serve, the conventional run
-also times the osdw kernels on the same frames in the same run, alternating with the osdx kernels.
+conventional search through ldpc_osdw_decode, osdw_front_kernel and osdw_search_kernel timed like the other legs.  --osd fs runs
+ldpc_osdw_fs_decode there: the same line of TEPs per frame, the FER of the conventional scan of the same order on the same frames
+next to it, and osdw_fs_kernel timed next to osdw_search_kernel.  --osd pb exits with a message there (PB-OSD stays with
+k <= 64).  On a code both families serve, the conventional run also times the osdw kernels on the same frames in the same run,
+alternating with the osdx kernels, and the --osd fs run times osdw_fs_kernel alternating with osdx_fs_kernel.
 One JSON line at the end."""
 import argparse
 import json
@@ -99,12 +101,12 @@ def main(argv=None):
         args.tau_e = 6.5
 
     dec = Decoder(Code(args.alist) if args.alist else Code(), 0)
-    wide = dec.osdw_supported and not dec.osdx_supported     # k > 64: the high-rate family, conventional search only
+    wide = dec.osdw_supported and not dec.osdx_supported     # k > 64: the high-rate family, conventional search and FS-OSD
     if not dec.osdx_supported and not dec.osdw_supported:
         raise SystemExit(f"osdx_fer: the OSD kernels serve n <= 128 and 1 <= n-k <= 64; this code is ({dec.n},{dec.k})")
-    if wide and (fs or pb):
+    if wide and pb:
         raise SystemExit(f"osdx_fer: --osd {args.osd} needs 1 <= k <= 64; this code is ({dec.n},{dec.k}), which only the conventional "
-                         "search serves (ldpc_osdw_decode: drop --osd)")
+                         "search and FS-OSD serve (ldpc_osdw_decode, ldpc_osdw_fs_decode: drop --osd or take --osd fs)")
     B = args.frames
     y, labels = make_frames(dec, B, args.seed, args.snr)
     res = dec.nms(y, args.T, args.alpha)
@@ -116,7 +118,8 @@ def main(argv=None):
     counts = torch.zeros(3, dtype=torch.int64, device=dec.device)
     if fs:
         fsp = dec.osd_params(args.order, _lib.OSD_FS, fs_beta=args.beta, fs_tau_e=args.tau_e, fs_tau_psc=args.tau_psc)
-        out = dec.osdx_fs_decode(y, fsp, index=idx, count=count, label_bits=labels, counts=counts)
+        fs_decode = dec.osdw_fs_decode if wide else dec.osdx_fs_decode
+        out = fs_decode(y, fsp, index=idx, count=count, label_bits=labels, counts=counts)
     elif pb:
         aux = torch.zeros((idx.shape[0], 4), dtype=torch.int32, device=dec.device)
         pbp = dec.osd_params(args.order, _lib.OSD_PB, snr_db=args.snr, aux=aux)
@@ -142,6 +145,14 @@ def main(argv=None):
         print(f"  order-{args.order} FS-OSD (beta {args.beta}, tau_e {args.tau_e}, tau_psc {args.tau_psc}) on the {nf} failures: FER {fer_osd:.3e} "
               f"({oc[1]} still wrong); TEPs per frame: mean {mean:.1f}, max {most}, table {table}", flush=True)
         result.update(osd="fs", beta=args.beta, tau_e=args.tau_e, tau_psc=args.tau_psc, teps_mean=mean, teps_max=most, teps_table=table)
+        if wide:                                             # the full scan of the same order on the same frames
+            cc = torch.zeros(3, dtype=torch.int64, device=dec.device)
+            outc = dec.osdw_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=cc)
+            torch.cuda.synchronize()
+            fer_conv = (nc[3] + cc.cpu().tolist()[1]) / B
+            print(f"  order-{args.order} conventional scan on the same failures: FER {fer_conv:.3e} ({cc.cpu().tolist()[1]} still wrong, "
+                  f"{table} TEPs per frame)", flush=True)
+            result.update(fer_conv=fer_conv)
     elif pb:
         table = sum(math.comb(dec.k, w) for w in range(args.order + 1))
         ntep = out["ntep"][:nf].to(torch.float64)
@@ -168,8 +179,14 @@ def main(argv=None):
         frontw = (outw["perm"], outw["parity"], None)
         legs += [("osdw_front_kernel", lambda: dec.osdw_front(y, index=idx, count=count, out=frontw)),
                  ("osdw_search_kernel", lambda: dec.osdw_search(y, outw["perm"], outw["parity"], args.order, index=idx, count=count, out=outw))]
-    if fs:
+    if fs and wide:
+        legs[1] = ("osdw_fs_kernel", lambda: dec.osdw_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out))
+        legs.append(("osdw_search_kernel", lambda: dec.osdw_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=outc)))
+    elif fs:
         legs[1] = ("osdx_fs_kernel", lambda: dec.osdx_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out))
+        if dec.osdw_supported:                           # both families serve the code: osdw_fs_kernel on the same frames
+            outw = dec.osdw_fs_decode(y, fsp, index=idx, count=count)
+            legs.append(("osdw_fs_kernel", lambda: dec.osdw_fs_search(y, outw["perm"], outw["parity"], fsp, index=idx, count=count, out=outw)))
         if (dec.n, dec.k) == (128, 64):                  # the specialised kernel on the same front-end results, in the same run
             out2 = dec.osd_search(y, out["perm"], out["parity"], fsp, index=idx, count=count)
             legs.append(("osd_fs_kernel", lambda: dec.osd_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out2)))

@@ -246,6 +246,22 @@ static void pack_supports(const std::vector<uint8_t> &sup, std::vector<uchar4> &
     }
 }
 
+// FS-OSD visit order of k (generate_sequential_teps, fs_testing.py:32-49): weight classes 1..min(3, k) back to back in `out`,
+// supports stored ascending; class w starts at off[w] and has cnt[w] entries.  LDPC_OK, or the error of tep_table_fs.
+static int pack_fs_table(int k, std::vector<uchar4> &out, int (&off)[4], int (&cnt)[4])
+{
+    std::vector<uint8_t> sup;
+    for (int w = 1; w <= 3 && w <= k; ++w) {
+        int64_t c = tep_table_fs(k, w, nullptr);
+        if (c < 0) return (int)c;
+        sup.assign((size_t)c * 3, 0);
+        if ((c = tep_table_fs(k, w, sup.data())) < 0) return (int)c;
+        off[w] = (int)out.size(); cnt[w] = (int)c;
+        pack_supports(sup, out);
+    }
+    return LDPC_OK;
+}
+
 int pack_osd_tables(const ldpc_code &c, OsdTables &t, OsdTablesHost &host)
 {
     t = OsdTables();
@@ -261,15 +277,7 @@ int pack_osd_tables(const ldpc_code &c, OsdTables &t, OsdTablesHost &host)
     std::vector<uint8_t> sup((size_t)total * 3);
     if ((total = tep_table(c.k, 3, sup.data(), nullptr)) < 0) return (int)total;
     pack_supports(sup, host.tep);
-    // FS-OSD visit order (generate_sequential_teps, fs_testing.py:32-49), supports stored ascending
-    for (int w = 1; w <= 3 && w <= c.k; ++w) {
-        int64_t cnt = tep_table_fs(c.k, w, nullptr);
-        if (cnt < 0) return (int)cnt;
-        sup.assign((size_t)cnt * 3, 0);
-        if ((cnt = tep_table_fs(c.k, w, sup.data())) < 0) return (int)cnt;
-        t.fs_off[w] = (int)host.tep_fs.size(); t.fs_cnt[w] = (int)cnt;
-        pack_supports(sup, host.tep_fs);
-    }
+    if (int rc = pack_fs_table(c.k, host.tep_fs, t.fs_off, t.fs_cnt)) return rc;
     // any-shape PB-OSD: P[Bin(m, 1/2) <= b] by the float64 pmf recurrence of the oracle (q^m by left-to-right square-and-multiply,
     // ratio p / q = 1), and the ratios of consecutive binomial coefficients of m and k
     {
@@ -302,7 +310,7 @@ int pack_osdw_tables(const ldpc_code &c, const OsdTables &base, OsdwTables &t, O
     for (int r = 0; r < c.k; ++r)
         for (int v = 0; v < c.n; ++v)
             if (c.G[(size_t)r * c.n + v]) host.Gcols[2 * (size_t)v + (r >> 6)] |= 1ull << (r & 63);
-    // one table for order 3; orders 0..2 are its prefixes.  The context's OsdTables hold the table of every k <= 64 already.
+    // one table for order 3; orders 0..2 are its prefixes.  The context's OsdTables hold both tables of every k <= 64 already.
     int64_t total = tep_table(c.k, 3, nullptr, t.ntep);
     if (total < 0) return (int)total;
     t.own_tep = base.k != c.k;
@@ -311,6 +319,10 @@ int pack_osdw_tables(const ldpc_code &c, const OsdTables &base, OsdwTables &t, O
         if ((total = tep_table(c.k, 3, sup.data(), nullptr)) < 0) return (int)total;
         host.tep.reserve((size_t)total);
         pack_supports(sup, host.tep);
+        host.tep_fs.reserve((size_t)total);
+        if (int rc = pack_fs_table(c.k, host.tep_fs, t.fs_off, t.fs_cnt)) return rc;
+    } else {
+        for (int w = 0; w < 4; ++w) { t.fs_off[w] = base.fs_off[w]; t.fs_cnt[w] = base.fs_cnt[w]; }
     }
     t.n = c.n; t.k = c.k;
     return LDPC_OK;

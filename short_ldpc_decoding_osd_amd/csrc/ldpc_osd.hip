@@ -275,7 +275,7 @@ int osd_launch(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const in
         break;
     case OsdRoute::Fs:
         hipLaunchKernelGGL(osd_fs_kernel, dim3(g64), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, d_perm, parity, t.d_tep_fs,
-                           fs_params(p, t), cw, d_metric, d_best, d_ntep);
+                           fs_params(p, t.n, t.k, t.fs_off, t.fs_cnt), cw, d_metric, d_best, d_ntep);
         break;
     case OsdRoute::PbStaged:
         return launch_pb(ctx, d_y, d_index, d_count, F, d_perm, parity, p, r.pb_mode, false, d_cw, d_metric, d_best, d_ntep, s);
@@ -290,13 +290,13 @@ int osd_launch(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const in
     return LDPC_OK;
 }
 
-FsParams fs_params(const ldpc_osd_params *p, const OsdTables &t)
+FsParams fs_params(const ldpc_osd_params *p, int n, int k, const int (&fs_off)[4], const int (&fs_cnt)[4])
 {
     FsParams fp;
     fp.order = p->order; fp.quirk = p->fs_reference_quirk != 0;
-    fp.beta_term = (float)((double)p->fs_beta * (double)(t.n - t.k));   // fs_testing.py:138
+    fp.beta_term = (float)((double)p->fs_beta * (double)(n - k));   // fs_testing.py:138
     fp.tau_e = p->fs_tau_e; fp.tau_psc = p->fs_tau_psc;
-    for (int w = 0; w < 4; ++w) { fp.cls_off[w] = t.fs_off[w]; fp.cls_cnt[w] = t.fs_cnt[w]; }
+    for (int w = 0; w < 4; ++w) { fp.cls_off[w] = fs_off[w]; fp.cls_cnt[w] = fs_cnt[w]; }
     return fp;
 }
 

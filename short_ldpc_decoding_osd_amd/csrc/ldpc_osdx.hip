@@ -76,8 +76,8 @@ static int osdx_launch_fs(ldpc_ctx *ctx, const float *d_y, const int32_t *d_inde
 {
     const OsdTables &t = ctx->osd_tables;
     hipLaunchKernelGGL(osdx_fs_kernel, dim3(osdx_grid(F)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F, t.n, t.k, d_perm,
-                       reinterpret_cast<const u64 *>(d_parity), t.d_tep_fs, fs_params(p, t), reinterpret_cast<u64 *>(d_cw), d_metric,
-                       d_best, d_ntep, c.label, c.counts);
+                       reinterpret_cast<const u64 *>(d_parity), t.d_tep_fs, fs_params(p, t.n, t.k, t.fs_off, t.fs_cnt),
+                       reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_ntep, c.label, c.counts);
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
 }

@@ -412,6 +412,52 @@ class Decoder:
         out["perm"], out["parity"] = perm, parity
         return out
 
+    def _osdw_front_results(self, y, perm, parity, F=None):
+        """The checks of the ``osdw_*`` calls that take front-end results (perm [*,128] u8, parity [*,128] int64).  Returns F."""
+        self._chk(y, torch.float32, (self.n,), "y")
+        self._chk(perm, torch.uint8, (128,), "perm")
+        self._chk(parity, torch.int64, (128,), "parity")
+        return perm.shape[0] if F is None else F
+
+    def osdw_fs_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
+        """``osdx_fs_search`` for every code with n <= 128 and 1 <= n-k <= 64, on the results of ``osdw_front`` (perm [F,128]
+        u8, parity [F,128] int64).  ``params`` and the returned dict as there."""
+        F = self._osdw_front_results(y, perm, parity, F)
+        out = self._osd_outputs(out, F)
+        _lib.check(self.L.ldpc_osdw_fs_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
+                                              C.byref(params), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
+                                              _ptr(out["ntep"]), self._stream()), "ldpc_osdw_fs_search")
+        return out
+
+    def osdw_fs_decode(self, y, params, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
+                       out=None):
+        """``osdx_fs_decode`` for every code with n <= 128 and 1 <= n-k <= 64: ``osdw_decode`` with the search of
+        ``osdw_fs_search``; ``perm`` [F,128] u8 / ``parity`` [F,128] int64 / ``label_bits`` / ``counts`` as there."""
+        F = self._osd_frames(y, index, F)
+        perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
+        parity = self.empty((F, 128), torch.int64) if parity is None else self._chk(parity, torch.int64, (128,), "parity")
+        out = self._osd_outputs(out, F)
+        _lib.check(self.L.ldpc_osdw_fs_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, C.byref(params), _ptr(perm),
+                                              _ptr(parity), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
+                                              _ptr(out["ntep"]), _ptr(label_bits), _ptr(counts), self._stream()),
+                   "ldpc_osdw_fs_decode")
+        out["perm"], out["parity"] = perm, parity
+        return out
+
+    def osdw_tep_eval(self, y, perm, parity, mask, index=None, count=None):
+        """``osdx_tep_eval`` for every code with n <= 128 and 1 <= n-k <= 64, on the results of ``osdw_front`` (parity [F,128]
+        int64).  mask [F,2] int64: bit p of word 0 flips primed MRB position p, bit p of word 1 position 64 + p; bits at or
+        beyond k are ignored.  Returns dict(cw[F,words] int64 original bit order, metric[F] f32, hd[F] i32)."""
+        F = self._osdw_front_results(y, perm, parity)
+        self._chk(mask, torch.int64, (2,), "mask")
+        if mask.shape[0] < F:
+            raise ValueError(f"mask: {mask.shape[0]} rows for {F} frames")
+        out = dict(cw=self.empty((F, self.words), torch.int64), metric=self.empty((F,), torch.float32), hd=self.empty((F,), torch.int32))
+        _lib.check(self.L.ldpc_osdw_tep_eval(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(mask),
+                                             _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["hd"]), self._stream()),
+                   "ldpc_osdw_tep_eval")
+        return out
+
     def osdx_fs_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
         """FS-OSD on front-end results of any supported shape.  ``params``: ``osd_params(order, _lib.OSD_FS, fs_beta=...,
         fs_tau_e=..., fs_tau_psc=..., fs_reference_quirk=...)``, order 0..min(3, k).  Returns the dict of ``osdx_search``
