@@ -371,6 +371,7 @@ int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label
  *   d_y       [*][n] f32, stride n: the layout of ldpc_nms_decode's d_soft
  *   d_perm    [F][128] u8 : original bit at primed position p < n (MRB 0..k-1, parity k..n-1); 0 for p >= n
  *   d_parity  [F][64] u64 : row r < k, bit c < n-k = P'[r][c]; rows >= k and bits >= n-k are written as 0
+ *             (as inputs, the search entry points ignore d_perm entries p >= n, d_parity rows >= k and bits >= n-k)
  *   d_nswaps  [F] i32 (nullable): recorded column exchanges
  *   d_cw      [F][ceil(n/64)] u64 best codeword, ORIGINAL bit order (the layout of ldpc_pack_bits)
  *   d_metric  [F] f32, d_best [F] i32 (index into the table), d_ntep [F] i32: nullable, each on its own
@@ -442,6 +443,7 @@ int ldpc_osdx_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
  * d_counts[3] as a pair or not at all, teps_total only with d_ntep -- with one layout changed:
  *   d_perm    [F][128] u8  : original bit at primed position p < n (MRB 0..k-1, parity k..n-1); 0 for p >= n
  *   d_parity  [F][128] u64 : row r < k, bit c < n-k = P'[r][c]; rows >= k and bits >= n-k are written as 0
+ *             (as inputs, the search entry points ignore d_perm entries p >= n, d_parity rows >= k and bits >= n-k)
  *   d_cw      [F][ceil(n/64)] u64 best codeword, ORIGINAL bit order
  * ldpc_osdw_decode is two launches through the caller's d_perm / d_parity, which are scratch AND outputs and required:
  * no library workspace, no per-stream state.  Before any launch: an unsupported shape is LDPC_E_UNSUPPORTED (the message

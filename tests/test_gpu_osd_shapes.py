@@ -1,0 +1,395 @@
+"""-m gpu: the any-shape (ldpc_osdx_*) and the high-rate (ldpc_osdw_*) OSD entry points on structured front-end results and at
+the shape edges no tested code has -- the pairs and codes of tests/osd_shapes.py, bit for bit against the CPU models
+(osdx_model.scan_oracle, osdx_fs_model.Batch, osdx_pb_model.pb, osdw_model.front_oracle), which tests/test_osd_shapes_host.py
+holds to the reference restatements and whose premises it asserts.  Integers compare equal, floats as uint32.
+
+  1  every search on caller-made (perm, P') pairs: zero, equal, all-ones, unit and rank-one rows of P', float and grid
+     magnitudes, perm = identity with sorted y' and a random perm with unsorted y' (conventional search and one TEP only)
+  2  the six magnitude extremes through the same calls
+  3  non-zero padding of perm and P': ignored by every search entry point
+  4  structured codes (zero columns, repeated columns, a rank-one parity part of G) through the device front end and the decodes
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from short_ldpc_decoding_osd_amd import _lib
+from tests import osd_shapes as S
+from tests import osdw_fs_model as W
+from tests import osdx_fs_model as M
+from tests import osdx_model, osdx_pb_model
+from tests.gpu_util import to_dev, words_np
+
+pytestmark = pytest.mark.gpu
+PAIR_CASES = [(k, n, name) for k, n in S.SHAPES for name in S.STRUCTURES]
+CODE_CASES = [(k, n, name) for k, n in S.CODE_SHAPES for name in S.CODE_STRUCTURES]
+_decoders, _REF = {}, {}
+_p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+
+
+def decoder(k, n, name=None):
+    """A context of the shape (a plain H = [A | I] code: the searches never read G), or of the structured code ``name``."""
+    key = (k, n, name)
+    if key not in _decoders:
+        from short_ldpc_decoding_osd_amd import Code
+        from short_ldpc_decoding_osd_amd.runtime import Decoder
+        H, G = S.context_graph(k, n) if name is None else S.code(k, n, name)[:2]
+        code = Code(H=H)
+        assert np.array_equal(code.G, G) and (code.k, code.check_matrix_column) == (k, n)
+        dec = Decoder(code)
+        assert dec.osdw_supported and dec.osdx_supported == (k <= 64)
+        _decoders[key] = dec
+    return _decoders[key]
+
+
+def ref(kind, c, *args):
+    """One model result per (case, search, parameters), shared by the tests and left unchanged."""
+    key = (kind, c["k"], c["n"], c["name"], c["mode"], c["form"]) + args
+    if key not in _REF:
+        if kind == "batch":
+            _REF[key] = M.Batch(c["y"], c["perm"], c["Gps"])
+        elif kind == "conv":
+            order, F = args
+            _REF[key] = osdx_model.scan_oracle(c["G"], c["y"][:F], order, S.front_of(c))
+        elif kind == "fs":
+            _REF[key] = ref("batch", c).fs(S.fs_order(c["k"]), *args)
+        elif kind == "pb":
+            with np.errstate(invalid="ignore"):              # (all-zero parity magnitudes: 0 / 0 in beta, which then is 0)
+                _REF[key] = osdx_pb_model.pb(c["y"], c["perm"], c["Gps"], min(2, c["k"]), args[0])
+        elif kind == "masks":
+            _REF[key] = S.tep_masks(c, np.random.default_rng(77))
+        elif kind == "tep":
+            _REF[key] = ref("batch", c).one_tep(ref("masks", c)[args[0]])
+    return _REF[key]
+
+
+def conv_frames(k, order, F):
+    """Order 2 on a few frames at k >= 100, order 3 where k <= 70 on at most 4 frames (the CPU scan dominates the time)."""
+    if order == 3:
+        return 0 if k > 70 else (2 if k >= 48 else 4)
+    return min(F, 3) if (order == 2 and k >= 100) else F
+
+
+def u32(t):
+    return (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.ascontiguousarray(t)).view(np.uint32)
+
+
+def assert_scan(out, want, tag):
+    F = len(want["best"])
+    assert np.array_equal(words_np(out["cw"])[:F], want["cw"]), tag
+    assert np.array_equal(u32(out["metric"])[:F], u32(want["metric"])), tag
+    assert np.array_equal(out["best"].cpu().numpy()[:F], want["best"]), tag
+    assert np.array_equal(out["ntep"].cpu().numpy()[:F], want["ntep"]), tag
+
+
+def assert_fs(out, want, quirk, tag):
+    key = "ref" if quirk else "hit"
+    assert_scan(out, dict(cw=want["cw_" + key], metric=want["metric_" + key], best=want["best_" + key], ntep=want["ntep"]), tag)
+
+
+def assert_same(a, b, tag, keys=("cw", "metric", "best", "ntep")):
+    for key in keys:
+        x, y = a[key], b[key]
+        if x.dtype == torch.float32:
+            x, y = x.view(torch.int32), y.view(torch.int32)
+        assert torch.equal(x, y), tag + (key,)
+
+
+def fs_params(dec, order, s, quirk):
+    return dec.osd_params(order, _lib.OSD_FS, fs_beta=s[0], fs_tau_e=s[1], fs_tau_psc=s[2], fs_reference_quirk=quirk)
+
+
+def device_inputs(dec, c, padding=False):
+    perm, p64, p128 = S.dirty(c) if padding else (c["perm"], c["parity64"], c["parity128"])
+    return (to_dev(np.array(c["y"]), dec), to_dev(np.array(perm), dec), to_dev(np.array(p128).view(np.int64), dec),
+            to_dev(np.array(p64).view(np.int64), dec) if p64 is not None else None)
+
+
+def run_searches(dec, c, padding=False):
+    """Every search call the case is defined for -> {(call, parameters...): output dict}; PB results carry ``aux``."""
+    k, F = c["k"], len(c["y"])
+    yd, perm, p128, p64 = device_inputs(dec, c, padding)
+    out = {}
+    for order in range(4):
+        Fo = conv_frames(k, order, F)
+        if Fo:
+            out["osdw_search", order] = dec.osdw_search(yd, perm[:Fo], p128[:Fo], order)
+            if k <= 64:
+                out["osdx_search", order] = dec.osdx_search(yd, perm[:Fo], p64[:Fo], order)
+    for i, masks in enumerate(ref("masks", c)):
+        out["osdw_tep_eval", i] = dec.osdw_tep_eval(yd, perm, p128, to_dev(W.split_masks(masks).view(np.int64), dec))
+        if k <= 64:
+            out["osdx_tep_eval", i] = dec.osdx_tep_eval(yd, perm, p64, to_dev(np.array(masks, dtype=np.uint64).view(np.int64), dec))
+    if c["form"] == "sorted":
+        for s in S.fs_sets(k, c["n"]):
+            for quirk in (1, 0):
+                p = fs_params(dec, S.fs_order(k), s, quirk)
+                out["osdw_fs_search", s, quirk] = dec.osdw_fs_search(yd, perm, p128, p)
+                if k <= 64:
+                    out["osdx_fs_search", s, quirk] = dec.osdx_fs_search(yd, perm, p64, p)
+        if k <= 64:
+            for snr in S.PB_SNRS:
+                aux = torch.full((F, 4), -9, dtype=torch.int32, device=dec.device)
+                r = dec.osdx_pb_search(yd, perm, p64, dec.osd_params(min(2, k), _lib.OSD_PB, snr_db=snr, aux=aux))
+                out["osdx_pb_search", snr] = dict(r, aux=aux)
+    torch.cuda.synchronize()
+    return out
+
+
+def _check_conv(c, args, got, tag):
+    assert_scan(got, ref("conv", c, args[0], conv_frames(c["k"], args[0], len(c["y"]))), tag)
+
+
+def _check_tep(c, args, got, tag):
+    want = ref("tep", c, args[0])
+    assert np.array_equal(words_np(got["cw"]), want["cw"]), tag
+    assert np.array_equal(u32(got["metric"]), u32(want["metric"])), tag
+    assert np.array_equal(got["hd"].cpu().numpy(), want["hd"]), tag
+
+
+def _check_fs(c, args, got, tag):
+    assert_fs(got, ref("fs", c, *args[0]), args[1], tag)
+
+
+def _check_pb(c, args, got, tag):
+    want = ref("pb", c, args[0])
+    assert_scan(got, want, tag)
+    assert np.array_equal(got["aux"].cpu().numpy(), want["aux"]), tag
+
+
+# the calls of run_searches by their name without the family: (checker against the model, outputs compared between runs)
+SCAN_KEYS = ("cw", "metric", "best", "ntep")
+CALLS = {"search": (_check_conv, SCAN_KEYS), "tep_eval": (_check_tep, ("cw", "metric", "hd")),
+         "fs_search": (_check_fs, SCAN_KEYS), "pb_search": (_check_pb, SCAN_KEYS + ("aux",))}
+
+
+def split_call(key):
+    """("osdw_fs_search", ...) -> ("osdw", "fs_search")."""
+    return tuple(key[0].split("_", 1))
+
+
+def check_against_models(c, out):
+    tag = (c["k"], c["n"], c["name"], c["mode"], c["form"])
+    for key, got in out.items():
+        CALLS[split_call(key)[1]][0](c, key[1:], got, tag + key)
+    # the two families against each other where both serve the shape (PB has one family)
+    for key, got in out.items():
+        family, call = split_call(key)
+        if family == "osdx" and call != "pb_search":
+            assert_same(got, out[("osdw_" + call,) + key[1:]], tag + key, CALLS[call][1])
+
+
+def pair_cases(k, n, name, modes):
+    return [S.pair(k, n, name, mode, form) for mode in modes for form in S.FORMS]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1: searches on caller-made pairs, per shape and structure
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k,n,name", PAIR_CASES)
+def test_searches_on_pairs(k, n, name):
+    dec = decoder(k, n)
+    for c in pair_cases(k, n, name, S.MODES):
+        masks = ref("masks", c)
+        if name == "zero_rows" and k >= 3:
+            assert all(m != 0 for m in masks[5])             # premise: a TEP over zero rows of P' only
+        if name in ("equal_rows", "rank_one") and k >= 2:
+            assert all(bin(m).count("1") > 1 for m in masks[6])   # premise: a TEP over a group of equal rows
+        check_against_models(c, run_searches(dec, c))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2: magnitude extremes
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["random_dense", "equal_rows"])
+@pytest.mark.parametrize("k,n", S.SHAPES)
+def test_magnitude_extremes(k, n, name):
+    dec = decoder(k, n)
+    for c in pair_cases(k, n, name, ("extreme",)):
+        check_against_models(c, run_searches(dec, c))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3: non-zero padding is ignored
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k,n", S.SHAPES)
+def test_padding_of_the_inputs_is_ignored(k, n):
+    """perm entries at or beyond n set to 0xEE, parity rows at or beyond k all ones, bits at or beyond n-k set: every output of
+    the pairs of part 1 (float and grid, both forms), ldpc_osdx_pb_search's aux among them, equals the clean run's."""
+    dec = decoder(k, n)
+    for name in S.STRUCTURES:
+        for c in pair_cases(k, n, name, S.MODES):
+            clean, dirty = run_searches(dec, c), run_searches(dec, c, padding=True)
+            assert clean.keys() == dirty.keys()
+            for key in clean:
+                assert_same(dirty[key], clean[key], (k, n, name, c["mode"], c["form"]) + key, CALLS[split_call(key)[1]][1])
+
+
+def _sentinels(dec, F):
+    return dict(cw=torch.full((F, dec.words), -1, dtype=torch.int64, device=dec.device),
+                metric=torch.full((F,), -5.0, dtype=torch.float32, device=dec.device),
+                best=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
+                ntep=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
+                hd=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
+                aux=torch.full((F, 4), -9, dtype=torch.int32, device=dec.device))
+
+
+@pytest.mark.parametrize("k,n", [(5, 12), (70, 87)])
+def test_padding_through_raw_calls_with_sentinels(k, n):
+    """The padded pairs through every C search entry point of the shape's families with a device-side count below F: the
+    frames below the count equal the models, nothing at or beyond it is written, and no output the call does not have."""
+    dec = decoder(k, n)
+    c = S.pair(k, n, "equal_rows", "grid")
+    F = len(c["y"])
+    done = F - 3
+    yd, perm, p128, p64 = device_inputs(dec, c, padding=True)
+    count = to_dev(np.array([done], np.int32), dec)
+    s = S.fs_sets(k, n)[0]
+    order = S.fs_order(k)
+    L, ctx, st = dec.L, dec._ctx, dec._stream()
+    scan = SCAN_KEYS
+    conv = ref("conv", c, 2, F)
+    r = ref("fs", c, *s)
+    fs = dict(cw=r["cw_ref"], metric=r["metric_ref"], best=r["best_ref"], ntep=r["ntep"])
+    tep = ref("tep", c, 3)
+    masks = ref("masks", c)[3]
+    fsp, runs = fs_params(dec, order, s, 1), []
+
+    def run(name, want, keys, call):
+        b = _sentinels(dec, F)
+        assert call(b) == 0, (name, dec.L.ldpc_last_error())
+        runs.append((name, b, {key: want[key] for key in keys}))
+
+    run("osdw_search", conv, scan, lambda b: L.ldpc_osdw_search(
+        ctx, _p(yd), None, _p(count), F, _p(perm), _p(p128), 2, _p(b["cw"]), _p(b["metric"]), _p(b["best"]), _p(b["ntep"]), st))
+    run("osdw_fs_search", fs, scan, lambda b: L.ldpc_osdw_fs_search(
+        ctx, _p(yd), None, _p(count), F, _p(perm), _p(p128), C.byref(fsp), _p(b["cw"]), _p(b["metric"]), _p(b["best"]),
+        _p(b["ntep"]), st))
+    m2 = to_dev(W.split_masks(masks).view(np.int64), dec)
+    run("osdw_tep_eval", tep, ("cw", "metric", "hd"), lambda b: L.ldpc_osdw_tep_eval(
+        ctx, _p(yd), None, _p(count), F, _p(perm), _p(p128), _p(m2), _p(b["cw"]), _p(b["metric"]), _p(b["hd"]), st))
+    if k <= 64:
+        run("osdx_search", conv, scan, lambda b: L.ldpc_osdx_search(
+            ctx, _p(yd), None, _p(count), F, _p(perm), _p(p64), 2, _p(b["cw"]), _p(b["metric"]), _p(b["best"]), _p(b["ntep"]), st))
+        run("osdx_fs_search", fs, scan, lambda b: L.ldpc_osdx_fs_search(
+            ctx, _p(yd), None, _p(count), F, _p(perm), _p(p64), C.byref(fsp), _p(b["cw"]), _p(b["metric"]), _p(b["best"]),
+            _p(b["ntep"]), st))
+        m1 = to_dev(np.array(masks, dtype=np.uint64).view(np.int64), dec)
+        run("osdx_tep_eval", tep, ("cw", "metric", "hd"), lambda b: L.ldpc_osdx_tep_eval(
+            ctx, _p(yd), None, _p(count), F, _p(perm), _p(p64), _p(m1), _p(b["cw"]), _p(b["metric"]), _p(b["hd"]), st))
+
+        def pb_call(b):
+            pb = dec.osd_params(order, _lib.OSD_PB, snr_db=1.0, aux=b["aux"])
+            return L.ldpc_osdx_pb_search(ctx, _p(yd), None, _p(count), F, _p(perm), _p(p64), C.byref(pb), _p(b["cw"]),
+                                         _p(b["metric"]), _p(b["best"]), _p(b["ntep"]), st)
+        run("osdx_pb_search", ref("pb", c, 1.0), scan + ("aux",), pb_call)
+    torch.cuda.synchronize()
+    clean = _sentinels(dec, F)
+    assert len(runs) == (7 if k <= 64 else 3)
+    for name, b, want in runs:
+        for key, w in want.items():
+            got = words_np(b[key]) if key == "cw" else b[key].cpu().numpy()
+            if key == "metric":
+                got, w = u32(got), u32(w)
+            assert np.array_equal(got[:done], w[:done]), (name, key)
+        for key in b:
+            lo = done if key in want else 0                  # an output the call does not have stays untouched altogether
+            assert torch.equal(b[key][lo:], clean[key][lo:]), (name, key)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4: structured codes through the device front end
+# ---------------------------------------------------------------------------------------------------------------------
+def assert_front(got, want, n, k, rows):
+    perm, parity, ns = got
+    perm, parity = perm.cpu().numpy(), words_np(parity)
+    assert parity.shape[1] == rows
+    if ns is not None:
+        assert np.array_equal(ns.cpu().numpy(), want[2])
+    assert np.array_equal(perm[:, :n], want[0][:, :n])
+    assert np.array_equal(parity[:, :min(k, rows)], want[1][:, :min(k, rows)])
+    assert not perm[:, n:].any() and not parity[:, k:].any()            # the padding is written as zero
+    assert n - k == 64 or not (parity >> np.uint64(n - k)).any()
+
+
+def decode_frames(k):
+    """The decodes run on the 64 frames of the front-end comparison; at k >= 100, where the CPU scan takes about 0.2 s per
+    frame, on the first 6."""
+    return 6 if k >= 100 else S.CODE_FRAMES
+
+
+def code_ref(kind, k, n, name, mode, *args):
+    """The models of a structured code's decodes on the oracle's front, one result per (code, mode, search), shared."""
+    key = ("code", kind, k, n, name, mode) + args
+    if key not in _REF:
+        cc = S.code_case(k, n, name, mode)
+        Fd = decode_frames(k)
+        y, front = cc["y"][:Fd], tuple(part[:Fd] for part in cc["front"][:4])
+        if kind == "sub":
+            _REF[key] = (y, front)
+        elif kind == "conv":
+            _REF[key] = osdx_model.scan_oracle(cc["G"], y, 2, front)
+        elif kind == "fs":
+            _REF[key] = M.Batch(y, front[0], front[3]).fs(2, *S.fs_sets(k, n)[0])
+        elif kind == "pb":
+            with np.errstate(invalid="ignore"):
+                _REF[key] = osdx_pb_model.pb(y, front[0], front[3], 2, args[0])
+    return _REF[key]
+
+
+@pytest.mark.parametrize("mode", S.MODES)
+@pytest.mark.parametrize("k,n,name", CODE_CASES)
+def test_structured_codes_through_the_front_end(k, n, name, mode):
+    """A code whose G has zero columns, repeated columns or a rank-one parity part: the front end on 64 frames against the
+    oracle (grid mode: sort ties meet zero and repeated columns), and the conventional and FS decodes at order 2 on the same
+    frames (``decode_frames``) against the models on the oracle's front."""
+    dec = decoder(k, n, name)
+    cc = S.code_case(k, n, name, mode)
+    y, front = cc["y"], cc["front"]
+    F = len(y)
+    assert F == S.CODE_FRAMES
+    yd = to_dev(y, dec)
+    perm = torch.full((F, 128), 0xEE, dtype=torch.uint8, device=dec.device)
+    parity = torch.full((F, 128), -1, dtype=torch.int64, device=dec.device)
+    ns = torch.full((F,), -7, dtype=torch.int32, device=dec.device)
+    got = dec.osdw_front(yd, out=(perm, parity, ns))
+    torch.cuda.synchronize()
+    assert_front(got, front, n, k, 128)
+    if k <= 64:
+        gx = dec.osdx_front(yd)
+        torch.cuda.synchronize()
+        assert_front(gx, front, n, k, 64)
+    ys, sub = code_ref("sub", k, n, name, mode)
+    assert len(ys) == (F if k < 100 else 6)
+    yds = to_dev(ys, dec)
+    conv, fs = code_ref("conv", k, n, name, mode), code_ref("fs", k, n, name, mode)
+    s = S.fs_sets(k, n)[0]
+    for family, rows in (("osdw", 128),) + ((("osdx", 64),) if k <= 64 else ()):
+        out = getattr(dec, family + "_decode")(yds, 2)
+        torch.cuda.synchronize()
+        assert_scan(out, conv, (k, n, name, mode, family + "_decode"))
+        assert_front((out["perm"], out["parity"], None), sub, n, k, rows)
+        for quirk in (1, 0):
+            out = getattr(dec, family + "_fs_decode")(yds, fs_params(dec, 2, s, quirk))
+            torch.cuda.synchronize()
+            assert_fs(out, fs, quirk, (k, n, name, mode, family + "_fs_decode", quirk))
+            assert_front((out["perm"], out["parity"], None), sub, n, k, rows)
+
+
+@pytest.mark.parametrize("snr", S.PB_SNRS)
+@pytest.mark.parametrize("mode", S.MODES)
+@pytest.mark.parametrize("k,n,name", [c for c in CODE_CASES if c[0] <= 64])
+def test_structured_codes_through_the_pb_decode(k, n, name, mode, snr):
+    """ldpc_osdx_pb_decode at order 2 on the 64 frames of the structured codes with k <= 64, aux included."""
+    dec = decoder(k, n, name)
+    ys, sub = code_ref("sub", k, n, name, mode)
+    assert len(ys) == S.CODE_FRAMES
+    want = code_ref("pb", k, n, name, mode, snr)
+    aux = torch.full((len(ys), 4), -9, dtype=torch.int32, device=dec.device)
+    out = dec.osdx_pb_decode(to_dev(ys, dec), dec.osd_params(2, _lib.OSD_PB, snr_db=snr, aux=aux))
+    torch.cuda.synchronize()
+    assert_scan(out, want, (k, n, name, mode, "osdx_pb_decode", snr))
+    assert np.array_equal(aux.cpu().numpy(), want["aux"]), (k, n, name, mode, snr)
+    assert_front((out["perm"], out["parity"], None), sub, n, k, 64)
