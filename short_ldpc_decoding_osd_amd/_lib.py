@@ -117,22 +117,8 @@ def load():
         "ldpc_osd_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
         "ldpc_osd_tep_eval": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "ldpc_osd_counts": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, vp]),
-        "ldpc_osdx_supported": (C.c_int, [vp]),
-        "ldpc_osdx_front": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp]),
-        "ldpc_osdx_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp]),
-        "ldpc_osdx_decode": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "ldpc_osdx_fs_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
-        "ldpc_osdx_fs_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ldpc_osdx_pb_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
         "ldpc_osdx_pb_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "ldpc_osdx_tep_eval": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
-        "ldpc_osdw_supported": (C.c_int, [vp]),
-        "ldpc_osdw_front": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp]),
-        "ldpc_osdw_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp]),
-        "ldpc_osdw_decode": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "ldpc_osdw_fs_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
-        "ldpc_osdw_fs_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "ldpc_osdw_tep_eval": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "ldpc_hosd_pattern_teps": (i64, [i32, pi32, pi32, C.POINTER(C.c_uint8)]),
         "ldpc_hosd_front": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, vp]),
         "ldpc_hosd_search": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -142,6 +128,17 @@ def load():
         "ldpc_pipeline_run": (C.c_int, [vp, C.POINTER(Pipeline), vp]),
         "ldpc_pipeline_timing": (C.c_int, [vp, i32, C.POINTER(f32)]),
     }
+    # the entry points that the any-shape and the high-rate family both have, under the same signatures
+    for fam in ("osdx", "osdw"):
+        sig.update({
+            f"ldpc_{fam}_supported": (C.c_int, [vp]),
+            f"ldpc_{fam}_front": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp]),
+            f"ldpc_{fam}_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp]),
+            f"ldpc_{fam}_decode": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            f"ldpc_{fam}_fs_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
+            f"ldpc_{fam}_fs_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            f"ldpc_{fam}_tep_eval": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        })
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError here = ABI/header drift, which must be loud
         fn.restype, fn.argtypes = sig[name]

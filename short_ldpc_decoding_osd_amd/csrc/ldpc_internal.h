@@ -38,6 +38,10 @@ inline int first_null(const char *who, std::initializer_list<NamedPtr> required)
         if (e__ != hipSuccess) return ::ldpc::hip_fail(e__, #call); \
     } while (0)
 
+// The grid of every kernel that runs one wavefront per workgroup: a workgroup per frame up to 65536, then strided (a wavefront
+// decodes several frames in turn).
+inline unsigned frame_grid(int64_t F) { return (unsigned)(F < 65536 ? F : 65536); }
+
 constexpr int kMaxIters = 64;  // alpha[] travels by value in the kernel arguments
 
 struct AlphaArg {

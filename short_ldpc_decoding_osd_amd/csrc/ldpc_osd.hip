@@ -157,8 +157,7 @@ static unsigned osd_grid(int64_t F)
     return (unsigned)(want < 1 ? 1 : (want < 4096 ? want : 4096));
 }
 
-// one wavefront per workgroup, a workgroup per frame up to 65536 (then strided)
-static unsigned frame_grid(int64_t F) { return (unsigned)(F < 65536 ? F : 65536); }
+// (frame_grid, one wavefront per workgroup: ldpc_internal.h)
 
 // the rotation-paired kernels: 4 wavefronts per SIMD are resident (10 KiB of LDS each); the grid is 6x that, ~1.5 frames per
 // workgroup at the headline size: the dispatcher then evens out the different scan times, and the prefetch still covers the

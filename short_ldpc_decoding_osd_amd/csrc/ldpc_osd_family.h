@@ -1,0 +1,188 @@
+// The host side that the any-shape family (ldpc_osdx_*, ldpc_osdx.hip) and the high-rate family (ldpc_osdw_*, ldpc_osdw.hip)
+// share: validation, launches and the bodies of their entry points, written once.  Host code only; included after the
+// family's kernel headers.  A family is a traits struct FAM with
+//   tables(ctx)                     its tables in the context (OsdTables / OsdwTables: n, k, d_Gcols, d_tep, ntep, d_tep_fs,
+//                                   fs_off, fs_cnt under the same names); k = 0: the code is not served
+//   needs                           the sentence of its UNSUPPORTED message
+//   front, search, fs, tep_eval     its kernels (the same argument lists in both families)
+// `who` is the name of the extern "C" entry point, for the error texts.
+// There is no library workspace: the decode entry points run their two launches through the caller's d_perm / d_parity, so the
+// calls hold no per-stream state, allocate nothing and are graph-capturable as they are.
+#pragma once
+
+#include "ldpc_internal.h"
+
+namespace ldpc {
+
+// the frames of a call and the per-frame results of a scan, as the entry points receive them
+struct OsdFrames {
+    const float *y;
+    const int32_t *index, *count;
+    int64_t F;
+};
+struct OsdScanOut {
+    uint64_t *cw;
+    float *metric;
+    int32_t *best, *ntep;
+};
+
+// the fused counters of a scan: only with the labels AND the counters, otherwise neither
+struct OsdCounting {
+    const u64 *label = nullptr;
+    u64 *counts = nullptr;
+};
+inline OsdCounting osd_counting(const uint64_t *d_label, int64_t *d_counts)
+{
+    if (!d_label || !d_counts) return {};
+    return {reinterpret_cast<const u64 *>(d_label), reinterpret_cast<u64 *>(d_counts)};
+}
+
+// the first checks of every entry point: the context, the frame count, whether the family serves the code
+template <class FAM>
+int family_open(const ldpc_ctx *ctx, int64_t F, const char *who)
+{
+    if (!ctx || F < 0) return fail(LDPC_E_ARG, "%s: bad arguments", who);
+    return FAM::tables(ctx).k ? LDPC_OK : fail(LDPC_E_UNSUPPORTED, "%s; this code is (%d,%d)", FAM::needs, ctx->code.n, ctx->code.k);
+}
+
+inline int check_order(int order, const char *who)
+{
+    return order < 0 || order > 3 ? fail(LDPC_E_ARG, "%s: order %d outside 0..3", who, order) : LDPC_OK;
+}
+
+// the pointers every scan with F > 0 needs
+inline int scan_required(const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const OsdScanOut &o, const char *who)
+{
+    return first_null(who, {{"d_y", fr.y}, {"d_perm", d_perm}, {"d_parity", d_parity}, {"d_cw", o.cw}});
+}
+
+template <class FAM>
+int family_launch_front(const ldpc_ctx *ctx, const OsdFrames &fr, uint8_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, hipStream_t s)
+{
+    const auto &t = FAM::tables(ctx);
+    hipLaunchKernelGGL(FAM::front, dim3(frame_grid(fr.F)), dim3(64), 0, s, fr.y, fr.index, fr.count, (long long)fr.F, t.n, t.k, t.d_Gcols,
+                       d_perm, reinterpret_cast<u64 *>(d_parity), d_nswaps);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+template <class FAM>
+int family_launch_search(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, int order,
+                         const OsdScanOut &o, OsdCounting c, hipStream_t s)
+{
+    const auto &t = FAM::tables(ctx);
+    hipLaunchKernelGGL(FAM::search, dim3(frame_grid(fr.F)), dim3(64), 0, s, fr.y, fr.index, fr.count, (long long)fr.F, t.n, t.k, d_perm,
+                       reinterpret_cast<const u64 *>(d_parity), t.d_tep, (int)t.ntep[order], reinterpret_cast<u64 *>(o.cw), o.metric,
+                       o.best, o.ntep, c.label, c.counts);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+template <class FAM>
+int family_launch_fs(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *p,
+                     const OsdScanOut &o, OsdCounting c, hipStream_t s)
+{
+    const auto &t = FAM::tables(ctx);
+    hipLaunchKernelGGL(FAM::fs, dim3(frame_grid(fr.F)), dim3(64), 0, s, fr.y, fr.index, fr.count, (long long)fr.F, t.n, t.k, d_perm,
+                       reinterpret_cast<const u64 *>(d_parity), t.d_tep_fs, fs_params(p, t.n, t.k, t.fs_off, t.fs_cnt),
+                       reinterpret_cast<u64 *>(o.cw), o.metric, o.best, o.ntep, c.label, c.counts);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+template <class FAM>
+int family_front(ldpc_ctx *ctx, const OsdFrames &fr, uint8_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, void *stream, const char *who)
+{
+    if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
+    if (fr.F == 0) return LDPC_OK;
+    if (int rc = first_null(who, {{"d_y", fr.y}, {"d_perm", d_perm}, {"d_parity", d_parity}})) return rc;
+    return family_launch_front<FAM>(ctx, fr, d_perm, d_parity, d_nswaps, (hipStream_t)stream);
+}
+
+template <class FAM>
+int family_search(ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, int32_t order, const OsdScanOut &o,
+                  void *stream, const char *who)
+{
+    if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
+    if (int rc = check_order(order, who)) return rc;
+    if (fr.F == 0) return LDPC_OK;
+    if (int rc = scan_required(fr, d_perm, d_parity, o, who)) return rc;
+    return family_launch_search<FAM>(ctx, fr, d_perm, d_parity, order, o, {}, (hipStream_t)stream);
+}
+
+template <class FAM>
+int family_decode(ldpc_ctx *ctx, const OsdFrames &fr, int32_t order, uint8_t *d_perm, uint64_t *d_parity, const OsdScanOut &o,
+                  OsdCounting c, void *stream, const char *who)
+{
+    if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
+    if (int rc = check_order(order, who)) return rc;
+    if (fr.F == 0) return LDPC_OK;
+    if (int rc = scan_required(fr, d_perm, d_parity, o, who)) return rc;
+    if (int rc = family_launch_front<FAM>(ctx, fr, d_perm, d_parity, nullptr, (hipStream_t)stream)) return rc;
+    return family_launch_search<FAM>(ctx, fr, d_perm, d_parity, order, o, c, (hipStream_t)stream);
+}
+
+// A scan that takes ldpc_osd_params (FS-OSD in both families, PB-OSD in ldpc_osdx.hip): what its entry points check and launch
+struct OsdScan {
+    int algo;
+    const char *algo_name;
+    bool aux_allowed;   // the scan writes params->d_aux
+    int (*launch)(const ldpc_ctx *, const OsdFrames &, const uint8_t *, const uint64_t *, const ldpc_osd_params *, const OsdScanOut &,
+                  OsdCounting, hipStream_t);
+};
+template <class FAM>
+constexpr OsdScan fs_scan{LDPC_OSD_FS, "LDPC_OSD_FS", false, family_launch_fs<FAM>};
+
+// the params of the entry points of `scan` for a code with k information bits: its algorithm, an order up to min(3, k), and
+// nothing that only ldpc_osd_search / ldpc_osd_decode serve
+inline int check_scan_params(int k, const ldpc_osd_params *p, const OsdScan &scan, const char *who)
+{
+    if (!p) return fail(LDPC_E_ARG, "%s: params is NULL", who);
+    if (p->algo != scan.algo) return fail(LDPC_E_ARG, "%s: algo %d is not %s", who, p->algo, scan.algo_name);
+    const int omax = k < 3 ? k : 3;
+    if (p->order < 0 || p->order > omax) return fail(LDPC_E_ARG, "%s: order %d outside 0..%d", who, p->order, omax);
+    if (p->flags != 0) return fail(LDPC_E_ARG, "%s: flags 0x%x are not served here (flags must be 0)", who, (unsigned)p->flags);
+    if (p->d_aux && !scan.aux_allowed) return fail(LDPC_E_ARG, "%s: d_aux is not served here (it must be NULL)", who);
+    if (p->y_frames != 0) return fail(LDPC_E_ARG, "%s: y_frames %lld is not served here (it must be 0)", who, (long long)p->y_frames);
+    return LDPC_OK;
+}
+
+template <class FAM>
+int family_scan_search(ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *params,
+                       const OsdScan &scan, const OsdScanOut &o, void *stream, const char *who)
+{
+    if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
+    if (int rc = check_scan_params(FAM::tables(ctx).k, params, scan, who)) return rc;
+    if (fr.F == 0) return LDPC_OK;
+    if (int rc = scan_required(fr, d_perm, d_parity, o, who)) return rc;
+    return scan.launch(ctx, fr, d_perm, d_parity, params, o, {}, (hipStream_t)stream);
+}
+
+template <class FAM>
+int family_scan_decode(ldpc_ctx *ctx, const OsdFrames &fr, const ldpc_osd_params *params, const OsdScan &scan, uint8_t *d_perm,
+                       uint64_t *d_parity, const OsdScanOut &o, OsdCounting c, void *stream, const char *who)
+{
+    if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
+    if (int rc = check_scan_params(FAM::tables(ctx).k, params, scan, who)) return rc;
+    if (fr.F == 0) return LDPC_OK;
+    if (int rc = scan_required(fr, d_perm, d_parity, o, who)) return rc;
+    if (int rc = family_launch_front<FAM>(ctx, fr, d_perm, d_parity, nullptr, (hipStream_t)stream)) return rc;
+    return scan.launch(ctx, fr, d_perm, d_parity, params, o, c, (hipStream_t)stream);
+}
+
+template <class FAM>
+int family_tep_eval(ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const uint64_t *d_mask,
+                    uint64_t *d_cw, float *d_metric, int32_t *d_hd, void *stream, const char *who)
+{
+    if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
+    if (fr.F == 0) return LDPC_OK;
+    if (int rc = first_null(who, {{"d_y", fr.y}, {"d_perm", d_perm}, {"d_parity", d_parity}, {"d_mask", d_mask}, {"d_cw", d_cw}})) return rc;
+    const auto &t = FAM::tables(ctx);
+    hipLaunchKernelGGL(FAM::tep_eval, dim3(frame_grid(fr.F)), dim3(64), 0, (hipStream_t)stream, fr.y, fr.index, fr.count, (long long)fr.F,
+                       t.n, t.k, d_perm, reinterpret_cast<const u64 *>(d_parity), reinterpret_cast<const u64 *>(d_mask),
+                       reinterpret_cast<u64 *>(d_cw), d_metric, d_hd);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+}  // namespace ldpc

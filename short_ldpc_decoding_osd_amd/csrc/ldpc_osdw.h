@@ -6,8 +6,9 @@
 // per lane.  Layout of a frame on the wavefront: lane l owns sorted columns l and 64 + l (the slots of the reliability sort), a
 // slot at or beyond n carries a zero column.  The n - k <= 64 parity columns keep a row of P' and the discrepancy D in one word,
 // so the scan is the one of ldpc_osdx.h with 128 rows of P' and two words of MRB hard decisions.
-// The helpers of ldpc_wave.h are used unchanged; those of ldpc_search.h that are typed on SearchLds (tep_apply,
-// tep_cost_bounded, wave_argmin) have their counterparts for SearchWLds here (tepw_*), ldpc_search.h is not touched.
+// The helpers of ldpc_wave.h and the metric of ldpc_search.h (tep_cost, tep_cost_bounded: templates on the LDS type, they read
+// only its byte LUTs) are used unchanged.  tep_apply and wave_argmin carry a one-word flip mask, which 127 MRB positions do not
+// fit: their counterparts without the mask are here (tepw_apply, tepw_flips, five lines of arg-min in the scan).
 #pragma once
 
 #include "ldpc_search.h"
@@ -207,18 +208,6 @@ __device__ __forceinline__ void tepw_apply(const SearchWLds &L, uchar4 s, u64 d0
     if (s.w > 2) { D ^= L.P[s.z]; mrb = mrb + L.w[s.z]; }
 }
 
-// tep_cost_bounded (ldpc_search.h) on SearchWLds: the same sum in the same order with the same exact early exit
-__device__ __forceinline__ bool tepw_cost_bounded(const SearchWLds &L, float mrb, u64 D, float bound, float &cost)
-{
-    float acc = mrb + lut_byte<0>(L.lut, D);
-    acc = acc + lut_byte<1>(L.lut, D);
-    if (acc > bound) return false;
-    acc = acc + lut_byte<2>(L.lut, D); acc = acc + lut_byte<3>(L.lut, D); acc = acc + lut_byte<4>(L.lut, D);
-    acc = acc + lut_byte<5>(L.lut, D); acc = acc + lut_byte<6>(L.lut, D); acc = acc + lut_byte<7>(L.lut, D);
-    cost = acc;
-    return true;
-}
-
 // whether the TEP flips primed MRB position p
 __device__ __forceinline__ bool tepw_flips(uchar4 s, int p)
 {
@@ -272,7 +261,7 @@ __global__ __launch_bounds__(64) void osdw_search_kernel(const float *__restrict
                 u64 D;
                 float mrb, c;
                 tepw_apply(L, teps[t], d0, D, mrb);
-                if (tepw_cost_bounded(L, mrb, D, bound, c) && c < best) { best = c; bestt = t; bestD = D; }
+                if (tep_cost_bounded(L, mrb, D, bound, c) && c < best) { best = c; bestt = t; bestD = D; }
             }
             if ((trip & 7) == 0) bound = wave_min_f32(best);
         }

@@ -5,8 +5,8 @@
 // range lies, HD = w + popcount(D), the visit-order table of this k <= 127 (classes 1..min(3, k)).
 // No flip mask is carried through the scan (it would be two words per lane): the winner and the stopping candidate are
 // remembered as table positions and their flipped positions read from their entries after the scan, as osdw_search_kernel does
-// with teps[best].  The per-frame prologue and epilogue are osdw_prepare / osdw_finish below; the metric is tepw_apply /
-// tepw_cost / tepw_cost_bounded (the float order of np_oracle._weighted_distance_k).
+// with teps[best].  The per-frame prologue and epilogue are osdw_prepare / osdw_finish below; the metric is tepw_apply
+// (ldpc_osdw.h) and tep_cost / tep_cost_bounded of ldpc_search.h (the float order of np_oracle._weighted_distance_k).
 #pragma once
 
 #include "ldpc_osdw.h"
@@ -18,15 +18,6 @@ struct __attribute__((aligned(16))) SearchWLdsLean {   // the same without the b
     float w[192];
     u64 cw[2];
 };
-
-// tep_cost (ldpc_search.h) on SearchWLds: the canonical sum, every byte
-__device__ __forceinline__ float tepw_cost(const SearchWLds &L, float mrb, u64 D)
-{
-    float acc = mrb;
-    acc = acc + lut_byte<0>(L.lut, D); acc = acc + lut_byte<1>(L.lut, D); acc = acc + lut_byte<2>(L.lut, D); acc = acc + lut_byte<3>(L.lut, D);
-    acc = acc + lut_byte<4>(L.lut, D); acc = acc + lut_byte<5>(L.lut, D); acc = acc + lut_byte<6>(L.lut, D); acc = acc + lut_byte<7>(L.lut, D);
-    return acc;
-}
 
 // ---------------------------------------------------------------------------------------
 // per-frame prologue and epilogue of the FS scan and the one-TEP kernel (osdx_prepare / osdx_finish of ldpc_osdx.h with two MRB
@@ -87,14 +78,6 @@ __device__ __forceinline__ void osdw_finish(LDS &L, const OsdwFrame &S, bool fli
     if (lane < words) cw_out[f * words + lane] = L.cw[lane];
 }
 
-template <class LDS>
-__device__ __forceinline__ bool osdw_wrong(const LDS &L, const u64 *__restrict__ label, long long src, int words)
-{
-    bool bad = false;
-    for (int w = 0; w < words; ++w) bad |= L.cw[w] != label[src * words + w];
-    return bad;
-}
-
 //   counts[3] += {frames, frames_wrong, teps_total} (with label; teps_total sums the frame's own ntep, only with ntep_out): one
 //   atomic per counter and wavefront, after its last frame.
 __global__ __launch_bounds__(64) void osdw_fs_kernel(const float *__restrict__ y, const int *__restrict__ index, const int *__restrict__ count,
@@ -111,7 +94,7 @@ __global__ __launch_bounds__(64) void osdw_fs_kernel(const float *__restrict__ y
     for (long long f = blockIdx.x; f < nframes; f += gridDim.x) {
         const long long src = index ? index[f] : f;
         const OsdwFrame S = osdw_prepare(L, y, src, perm_in, parity_in, f, n, k, lane);
-        float best = tepw_cost(L, 0.0f, S.d0);     // all-zero TEP (:131)
+        float best = tep_cost(L, 0.0f, S.d0);      // all-zero TEP (:131)
         u64 bestD = S.d0, hitD = 0;
         float hitc = 0.0f;
         int bestidx = 0, ntep = 1, visited = 1, hitidx = 0;
@@ -136,11 +119,11 @@ __global__ __launch_bounds__(64) void osdw_fs_kernel(const float *__restrict__ y
                     const int nvalid = (cnt - t0) < 64 ? (cnt - t0) : 64;
                     ntep += stop ? lim + 1 : nvalid;
                     // best among the TEPs visited before the stop that pass the tau_psc rule: the metric is only
-                    // needed for those, and only if it can beat `best` (exact prefix early exit, tepw_cost_bounded)
+                    // needed for those, and only if it can beat `best` (exact prefix early exit, tep_cost_bounded)
                     float cc = __builtin_inff();
                     if (valid && lane < lim && hd < P.tau_psc) {
                         float c;
-                        if (tepw_cost_bounded(L, mrb, D, best, c)) cc = c;
+                        if (tep_cost_bounded(L, mrb, D, best, c)) cc = c;
                     }
                     if (__ballot(cc < best)) {
                         const int wl = wave_argmin_lane(cc, lane);
@@ -151,7 +134,7 @@ __global__ __launch_bounds__(64) void osdw_fs_kernel(const float *__restrict__ y
                     if (stop) {
                         hit = true;
                         hitD = readlane64(D, lim);
-                        hitc = tepw_cost(L, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mrb), lim)), hitD);   // the stopping candidate's own metric
+                        hitc = tep_cost(L, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mrb), lim)), hitD);   // the stopping candidate's own metric
                         hitidx = visited + t0 + lim; hitpos = off + t0 + lim;
                     }
                 }
@@ -165,7 +148,7 @@ __global__ __launch_bounds__(64) void osdw_fs_kernel(const float *__restrict__ y
         if (pos >= 0) win = teps_fs[pos];
         osdw_finish(L, S, tepw_flips(win, lane), tepw_flips(win, 64 + lane), use_hit ? hitD : bestD, f, words, lane, cw_out);
         store_results(f, lane, use_hit ? hitc : best, use_hit ? hitidx : bestidx, ntep, metric_out, best_out, ntep_out);
-        if (label) { seen += 1; wrong += osdw_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
+        if (label) { seen += 1; wrong += cw_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
         wave_fence();
     }
     if (label && lane == 0 && seen) {

@@ -186,14 +186,6 @@ __device__ __forceinline__ void osdx_finish(LDS &L, const OsdxFrame &S, u64 E, u
     if (lane < words) cw_out[f * words + lane] = L.cw[lane];
 }
 
-template <class LDS>
-__device__ __forceinline__ bool osdx_wrong(const LDS &L, const u64 *__restrict__ label, long long src, int words)
-{
-    bool bad = false;
-    for (int w = 0; w < words; ++w) bad |= L.cw[w] != label[src * words + w];
-    return bad;
-}
-
 // ---------------------------------------------------------------------------------------
 // conventional order-p search over the reference's TEP table for THIS k (the scan of osd_search_kernel, split at k)
 //   SearchLds: w[0..k-1] = |y'| of the MRB, w[64..64+n-k-1] = |y'| of the parity part, zero elsewhere; the eight byte LUTs
@@ -237,7 +229,7 @@ __global__ __launch_bounds__(64) void osdx_search_kernel(const float *__restrict
         wave_argmin(best, bestt, bestD, bestE, lane);
         osdx_finish(L, S, bestE, bestD, f, words, lane, cw_out);
         store_results(f, lane, best, bestt, ntep, metric_out, best_out, ntep_out);
-        if (label) { seen += 1; wrong += osdx_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
+        if (label) { seen += 1; wrong += cw_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
         wave_fence();
     }
     if (label && lane == 0 && seen) {

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(64) void osdx_fs_kernel(const float *__restrict__ y
         const bool use_hit = hit && !P.quirk;
         osdx_finish(L, S, use_hit ? hitE : bestE, use_hit ? hitD : bestD, f, words, lane, cw_out);
         store_results(f, lane, use_hit ? hitc : best, use_hit ? hitidx : bestidx, ntep, metric_out, best_out, ntep_out);
-        if (label) { seen += 1; wrong += osdx_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
+        if (label) { seen += 1; wrong += cw_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
         wave_fence();
     }
     if (label && lane == 0 && seen) {

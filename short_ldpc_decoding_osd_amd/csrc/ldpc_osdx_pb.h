@@ -249,7 +249,7 @@ __global__ __launch_bounds__(64) void osdx_pb_kernel(const float *__restrict__ y
         osdx_finish(L, S, bestE, bestD, f, words, lane, cw_out);
         store_results(f, lane, best, bestidx, ntep, metric_out, best_out, ntep_out);
         if (aux_out && lane == 0) { aux_out[f * 4] = cmp; aux_out[f * 4 + 1] = suc1; aux_out[f * 4 + 2] = suc2; aux_out[f * 4 + 3] = stop; }
-        if (label) { seen += 1; wrong += osdx_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
+        if (label) { seen += 1; wrong += cw_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
         wave_fence();
     }
     if (label && lane == 0 && seen) {

@@ -45,10 +45,12 @@ __device__ __forceinline__ float tep_cost_direct(const float *w, float mrb, u64 
     return acc;
 }
 
-template <int B>
-__device__ __forceinline__ float lut_term(const SearchLds &L, u64 D) { return lut_byte<B>(L.lut, D); }
+// lut_term and the tep_cost* below read only L.lut: LDS is SearchLds, or any struct with that member (SearchWLds, ldpc_osdw.h)
+template <int B, class LDS>
+__device__ __forceinline__ float lut_term(const LDS &L, u64 D) { return lut_byte<B>(L.lut, D); }
 
-__device__ __forceinline__ float tep_cost(const SearchLds &L, float mrb, u64 D)
+template <class LDS>
+__device__ __forceinline__ float tep_cost(const LDS &L, float mrb, u64 D)
 {
     float acc = mrb;
     acc = acc + lut_term<0>(L, D); acc = acc + lut_term<1>(L, D); acc = acc + lut_term<2>(L, D); acc = acc + lut_term<3>(L, D);
@@ -58,7 +60,8 @@ __device__ __forceinline__ float tep_cost(const SearchLds &L, float mrb, u64 D)
 
 // The same sum with the eight LUT reads issued together (their LDS round trips overlap; the compiler, left to the form
 // above under register pressure, issues read - wait - add eight times over).  The empty asm pins the reads before the adds.
-__device__ __forceinline__ float tep_cost_wide(const SearchLds &L, float mrb, u64 D)
+template <class LDS>
+__device__ __forceinline__ float tep_cost_wide(const LDS &L, float mrb, u64 D)
 {
     float t0 = lut_term<0>(L, D), t1 = lut_term<1>(L, D), t2 = lut_term<2>(L, D), t3 = lut_term<3>(L, D);
     float t4 = lut_term<4>(L, D), t5 = lut_term<5>(L, D), t6 = lut_term<6>(L, D), t7 = lut_term<7>(L, D);
@@ -73,7 +76,8 @@ __device__ __forceinline__ float tep_cost_wide(const SearchLds &L, float mrb, u6
 // nor tie, and its six remaining LUT reads are skipped (the scan is LDS-bound: random LUT reads, 63 % of
 // the LDS cycles were bank conflicts).  At 2.5 dB ~93 % of the order-2 TEPs leave after two bytes.
 // Returns false for a pruned candidate; otherwise `cost` is bit-identical to tep_cost().
-__device__ __forceinline__ bool tep_cost_bounded(const SearchLds &L, float mrb, u64 D, float bound, float &cost)
+template <class LDS>
+__device__ __forceinline__ bool tep_cost_bounded(const LDS &L, float mrb, u64 D, float bound, float &cost)
 {
     float acc = mrb + lut_term<0>(L, D);
     acc = acc + lut_term<1>(L, D);
@@ -158,6 +162,15 @@ __device__ __forceinline__ void search_finish(LDS &L, const SearchFrame &S, u64 
     wave_fence();
     if (lane < 2) cw_out[f * 2 + lane] = L.cw[lane];
     wave_fence();
+}
+
+// whether the codeword assembled in L.cw (search_finish and its any-shape counterparts leave it there) differs from the label
+template <class LDS>
+__device__ __forceinline__ bool cw_wrong(const LDS &L, const u64 *__restrict__ label, long long src, int words)
+{
+    bool bad = false;
+    for (int w = 0; w < words; ++w) bad |= L.cw[w] != label[src * words + w];
+    return bad;
 }
 
 // the per-frame results beside the codeword: lane 0 stores those the caller asked for

@@ -81,41 +81,67 @@ class Decoder:
         self._chk(y, torch.float32, (self.n,), "y")
         return (index.shape[0] if index is not None else y.shape[0]) if F is None else F
 
-    def _osd_front_results(self, y, perm, parity, F=None):
-        """The checks of the calls that take front-end results (perm [*,128] u8, parity [*,64] int64).  Returns F."""
+    # An OSD family is the prefix of its methods and library functions (``osd``: the (128,64) kernels, ``osdx``: any shape,
+    # ``osdw``: high rate) with the int64 words of a ``parity`` row and the shape tail of a ``tep_eval`` mask.
+    _OSD_PARITY_WORDS = {"osd": 64, "osdx": 64, "osdw": 128}
+    _OSD_MASK_TAIL = {"osd": (), "osdx": (), "osdw": (2,)}
+
+    def _osd_call(self, fam, op, *args):
+        """``ldpc_<fam>_<op>(ctx, *args, stream)``, checked."""
+        name = f"ldpc_{fam}_{op}"
+        _lib.check(getattr(self.L, name)(self._ctx, *args, self._stream()), name)
+
+    def _osd_front_results(self, fam, y, perm, parity, F=None):
+        """The checks of the calls that take front-end results (perm [*,128] u8, parity [*,64 or 128] int64).  Returns F."""
         self._chk(y, torch.float32, (self.n,), "y")
         self._chk(perm, torch.uint8, (128,), "perm")
-        self._chk(parity, torch.int64, (64,), "parity")
+        self._chk(parity, torch.int64, (self._OSD_PARITY_WORDS[fam],), "parity")
         return perm.shape[0] if F is None else F
 
-    def _osd_front(self, fn, name, y, index, count, F, out):
-        """``osd_front`` / ``osdx_front``: ``fn`` is the library function, ``name`` its name."""
+    def _osd_front(self, fam, y, index, count, F, out):
+        """``<fam>_front``."""
         F = self._osd_frames(y, index, F)
         if out is not None:
             perm, parity, ns = out
         else:
             perm = self.empty((F, 128), torch.uint8)
-            parity = self.empty((F, 64), torch.int64)
+            parity = self.empty((F, self._OSD_PARITY_WORDS[fam]), torch.int64)
             ns = self.empty((F,), torch.int32)
-        _lib.check(fn(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(ns), self._stream()), name)
+        self._osd_call(fam, "front", _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(ns))
         return perm, parity, ns
 
-    def _osd_tep_eval(self, fn, name, y, perm, parity, mask, index, count):
-        """``osd_tep_eval`` / ``osdx_tep_eval``: ``fn`` is the library function, ``name`` its name."""
-        F = self._osd_front_results(y, perm, parity)
-        self._chk(mask, torch.int64, (), "mask")
+    def _osd_tep_eval(self, fam, y, perm, parity, mask, index, count):
+        """``<fam>_tep_eval``.  The kernel reads a mask row for every frame, so a shorter mask is refused here."""
+        F = self._osd_front_results(fam, y, perm, parity)
+        self._chk(mask, torch.int64, self._OSD_MASK_TAIL[fam], "mask")
+        if mask.shape[0] < F:
+            raise ValueError(f"mask: {mask.shape[0]} rows for {F} frames")
         out = dict(cw=self.empty((F, self.words), torch.int64), metric=self.empty((F,), torch.float32), hd=self.empty((F,), torch.int32))
-        _lib.check(fn(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(mask), _ptr(out["cw"]),
-                      _ptr(out["metric"]), _ptr(out["hd"]), self._stream()), name)
+        self._osd_call(fam, "tep_eval", _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(mask), _ptr(out["cw"]),
+                       _ptr(out["metric"]), _ptr(out["hd"]))
         return out
 
-    def _osdx_decode_args(self, y, index, F, perm, parity):
-        """The checks of ``osdx_decode`` / ``osdx_fs_decode``: F by the rule of ``_osd_frames``, ``perm`` / ``parity``
-        checked when given and allocated when not.  Returns (F, perm, parity)."""
+    def _osd_search(self, fam, op, y, perm, parity, arg, index, count, F, out):
+        """``<fam>_<op>`` for the ``*search`` calls: a scan on front-end results.  ``arg``: the order, or the params by
+        reference, as the library function takes it."""
+        F = self._osd_front_results(fam, y, perm, parity, F)
+        out = self._osd_outputs(out, F)
+        self._osd_call(fam, op, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), arg, _ptr(out["cw"]),
+                       _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]))
+        return out
+
+    def _osd_decode(self, fam, op, y, arg, index, count, F, perm, parity, label_bits, counts, out):
+        """``<fam>_<op>`` for the ``*decode`` calls: front end + scan through ``perm`` / ``parity``, which are checked when
+        given, allocated when not, and returned in the dict.  F by the rule of ``_osd_frames``; ``arg`` as in ``_osd_search``."""
         F = self._osd_frames(y, index, F)
+        width = self._OSD_PARITY_WORDS[fam]
         perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
-        parity = self.empty((F, 64), torch.int64) if parity is None else self._chk(parity, torch.int64, (64,), "parity")
-        return F, perm, parity
+        parity = self.empty((F, width), torch.int64) if parity is None else self._chk(parity, torch.int64, (width,), "parity")
+        out = self._osd_outputs(out, F)
+        self._osd_call(fam, op, _ptr(y), _ptr(index), _ptr(count), F, arg, _ptr(perm), _ptr(parity), _ptr(out["cw"]),
+                       _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]), _ptr(label_bits), _ptr(counts))
+        out["perm"], out["parity"] = perm, parity
+        return out
 
     def _hosd_args(self, order_llr, metric_llr, front, teps, block_off):
         """The checks hosd_search and hosd_sliding share.  Returns (lri, uidx, M, F, nblk)."""
@@ -281,7 +307,7 @@ class Decoder:
     def osd_front(self, y, index=None, count=None, F=None, out=None):
         """Reliability sort + elimination + MRB bookkeeping.  Returns (perm[F,128] u8,
         parity[F,64] int64 rows of P', nswaps[F] int32); ``out`` may carry those three preallocated."""
-        return self._osd_front(self.L.ldpc_osd_front, "ldpc_osd_front", y, index, count, F, out)
+        return self._osd_front("osd", y, index, count, F, out)
 
     def osd_params(self, order, algo=_lib.OSD_CONVENTIONAL, snr_db=0.0, fs_beta=0.1, fs_tau_e=6.5, fs_tau_psc=30.0,
                    fs_reference_quirk=1, aux=None, table_scan=False, pb_path=None, readlane_scan=False, y_frames=0,
@@ -317,17 +343,12 @@ class Decoder:
 
     def osd_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
         """Search only, on caller-supplied front-end results (perm [F,128] u8, parity [F,64] int64)."""
-        F = self._osd_front_results(y, perm, parity, F)
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osd_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
-                                          C.byref(params), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
-                                          _ptr(out["ntep"]), self._stream()), "ldpc_osd_search")
-        return out
+        return self._osd_search("osd", "search", y, perm, parity, C.byref(params), index, count, F, out)
 
     def osd_tep_eval(self, y, perm, parity, mask, index=None, count=None):
         """One given TEP per frame (mask [F] int64: bit p flips primed MRB position p) on front-end results.
         Returns dict(cw[F,2] int64 original bit order, metric[F] f32, hd[F] i32)."""
-        return self._osd_tep_eval(self.L.ldpc_osd_tep_eval, "ldpc_osd_tep_eval", y, perm, parity, mask, index, count)
+        return self._osd_tep_eval("osd", y, perm, parity, mask, index, count)
 
     # ------------------------------------------------------------------ OSD for short codes of any shape
     @property
@@ -339,17 +360,12 @@ class Decoder:
         """``osd_front`` for any supported shape.  Returns (perm[F,128] u8: original bit at primed position p < n, MRB
         first, 0 beyond n; parity[F,64] int64: rows r < k of P', bits c < n-k, 0 elsewhere; nswaps[F] int32); ``out`` may
         carry those three preallocated (nswaps may be None)."""
-        return self._osd_front(self.L.ldpc_osdx_front, "ldpc_osdx_front", y, index, count, F, out)
+        return self._osd_front("osdx", y, index, count, F, out)
 
     def osdx_search(self, y, perm, parity, order, index=None, count=None, F=None, out=None):
         """Conventional order-``order`` search on front-end results (perm [F,128] u8, parity [F,64] int64) of any supported
         shape.  Returns dict(cw[F,words] int64 original bit order, metric[F] f32, best[F] i32, ntep[F] i32)."""
-        F = self._osd_front_results(y, perm, parity, F)
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osdx_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), int(order),
-                                           _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
-                                           self._stream()), "ldpc_osdx_search")
-        return out
+        return self._osd_search("osdx", "search", y, perm, parity, int(order), index, count, F, out)
 
     def osdx_decode(self, y, order, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
                     out=None):
@@ -357,13 +373,7 @@ class Decoder:
         launches through ``perm`` / ``parity`` (allocated when not given; returned in the dict).  With ``label_bits``
         ([*, words] int64, addressed through ``index``) and ``counts`` ([3] int64) the search accumulates
         counts += {frames, frames_wrong, teps_total}."""
-        F, perm, parity = self._osdx_decode_args(y, index, F, perm, parity)
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osdx_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, int(order), _ptr(perm), _ptr(parity),
-                                           _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
-                                           _ptr(label_bits), _ptr(counts), self._stream()), "ldpc_osdx_decode")
-        out["perm"], out["parity"] = perm, parity
-        return out
+        return self._osd_decode("osdx", "decode", y, int(order), index, count, F, perm, parity, label_bits, counts, out)
 
     # ------------------------------------------------------------------ OSD for high-rate short codes (k up to 127)
     @property
@@ -375,142 +385,66 @@ class Decoder:
         """``osdx_front`` for every code with n <= 128 and 1 <= n-k <= 64.  Returns (perm[F,128] u8, parity[F,128] int64: rows
         r < k of P', bits c < n-k, 0 elsewhere; nswaps[F] int32); ``out`` may carry those three preallocated (nswaps may be
         None)."""
-        F = self._osd_frames(y, index, F)
-        if out is not None:
-            perm, parity, ns = out
-        else:
-            perm, parity, ns = self.empty((F, 128), torch.uint8), self.empty((F, 128), torch.int64), self.empty((F,), torch.int32)
-        _lib.check(self.L.ldpc_osdw_front(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(ns),
-                                          self._stream()), "ldpc_osdw_front")
-        return perm, parity, ns
+        return self._osd_front("osdw", y, index, count, F, out)
 
     def osdw_search(self, y, perm, parity, order, index=None, count=None, F=None, out=None):
         """Conventional order-``order`` search on the results of ``osdw_front`` (perm [F,128] u8, parity [F,128] int64).
         Returns the dict of ``osdx_search``."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        self._chk(perm, torch.uint8, (128,), "perm")
-        self._chk(parity, torch.int64, (128,), "parity")
-        F = perm.shape[0] if F is None else F
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osdw_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), int(order),
-                                           _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
-                                           self._stream()), "ldpc_osdw_search")
-        return out
+        return self._osd_search("osdw", "search", y, perm, parity, int(order), index, count, F, out)
 
     def osdw_decode(self, y, order, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
                     out=None):
         """``osdx_decode`` for every code with n <= 128 and 1 <= n-k <= 64: front end + conventional order-``order`` search,
         two launches through ``perm`` [F,128] u8 / ``parity`` [F,128] int64 (allocated when not given; returned in the
         dict); ``label_bits`` / ``counts`` as there."""
-        F = self._osd_frames(y, index, F)
-        perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
-        parity = self.empty((F, 128), torch.int64) if parity is None else self._chk(parity, torch.int64, (128,), "parity")
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osdw_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, int(order), _ptr(perm), _ptr(parity),
-                                           _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]),
-                                           _ptr(label_bits), _ptr(counts), self._stream()), "ldpc_osdw_decode")
-        out["perm"], out["parity"] = perm, parity
-        return out
-
-    def _osdw_front_results(self, y, perm, parity, F=None):
-        """The checks of the ``osdw_*`` calls that take front-end results (perm [*,128] u8, parity [*,128] int64).  Returns F."""
-        self._chk(y, torch.float32, (self.n,), "y")
-        self._chk(perm, torch.uint8, (128,), "perm")
-        self._chk(parity, torch.int64, (128,), "parity")
-        return perm.shape[0] if F is None else F
+        return self._osd_decode("osdw", "decode", y, int(order), index, count, F, perm, parity, label_bits, counts, out)
 
     def osdw_fs_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
         """``osdx_fs_search`` for every code with n <= 128 and 1 <= n-k <= 64, on the results of ``osdw_front`` (perm [F,128]
         u8, parity [F,128] int64).  ``params`` and the returned dict as there."""
-        F = self._osdw_front_results(y, perm, parity, F)
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osdw_fs_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
-                                              C.byref(params), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
-                                              _ptr(out["ntep"]), self._stream()), "ldpc_osdw_fs_search")
-        return out
+        return self._osd_search("osdw", "fs_search", y, perm, parity, C.byref(params), index, count, F, out)
 
     def osdw_fs_decode(self, y, params, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
                        out=None):
         """``osdx_fs_decode`` for every code with n <= 128 and 1 <= n-k <= 64: ``osdw_decode`` with the search of
         ``osdw_fs_search``; ``perm`` [F,128] u8 / ``parity`` [F,128] int64 / ``label_bits`` / ``counts`` as there."""
-        F = self._osd_frames(y, index, F)
-        perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
-        parity = self.empty((F, 128), torch.int64) if parity is None else self._chk(parity, torch.int64, (128,), "parity")
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osdw_fs_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, C.byref(params), _ptr(perm),
-                                              _ptr(parity), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
-                                              _ptr(out["ntep"]), _ptr(label_bits), _ptr(counts), self._stream()),
-                   "ldpc_osdw_fs_decode")
-        out["perm"], out["parity"] = perm, parity
-        return out
+        return self._osd_decode("osdw", "fs_decode", y, C.byref(params), index, count, F, perm, parity, label_bits, counts, out)
 
     def osdw_tep_eval(self, y, perm, parity, mask, index=None, count=None):
         """``osdx_tep_eval`` for every code with n <= 128 and 1 <= n-k <= 64, on the results of ``osdw_front`` (parity [F,128]
         int64).  mask [F,2] int64: bit p of word 0 flips primed MRB position p, bit p of word 1 position 64 + p; bits at or
         beyond k are ignored.  Returns dict(cw[F,words] int64 original bit order, metric[F] f32, hd[F] i32)."""
-        F = self._osdw_front_results(y, perm, parity)
-        self._chk(mask, torch.int64, (2,), "mask")
-        if mask.shape[0] < F:
-            raise ValueError(f"mask: {mask.shape[0]} rows for {F} frames")
-        out = dict(cw=self.empty((F, self.words), torch.int64), metric=self.empty((F,), torch.float32), hd=self.empty((F,), torch.int32))
-        _lib.check(self.L.ldpc_osdw_tep_eval(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(mask),
-                                             _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["hd"]), self._stream()),
-                   "ldpc_osdw_tep_eval")
-        return out
+        return self._osd_tep_eval("osdw", y, perm, parity, mask, index, count)
 
     def osdx_fs_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
         """FS-OSD on front-end results of any supported shape.  ``params``: ``osd_params(order, _lib.OSD_FS, fs_beta=...,
         fs_tau_e=..., fs_tau_psc=..., fs_reference_quirk=...)``, order 0..min(3, k).  Returns the dict of ``osdx_search``
         (best: rank in visit order, 0 = the all-zero TEP; ntep: num_teps)."""
-        F = self._osd_front_results(y, perm, parity, F)
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osdx_fs_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
-                                              C.byref(params), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
-                                              _ptr(out["ntep"]), self._stream()), "ldpc_osdx_fs_search")
-        return out
+        return self._osd_search("osdx", "fs_search", y, perm, parity, C.byref(params), index, count, F, out)
 
     def osdx_fs_decode(self, y, params, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
                        out=None):
         """Front end + FS-OSD of the frames y[index[f]] (or y[f]) for any supported shape: ``osdx_decode`` with the search
         of ``osdx_fs_search``; ``perm`` / ``parity`` / ``label_bits`` / ``counts`` as there."""
-        F, perm, parity = self._osdx_decode_args(y, index, F, perm, parity)
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osdx_fs_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, C.byref(params), _ptr(perm),
-                                              _ptr(parity), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
-                                              _ptr(out["ntep"]), _ptr(label_bits), _ptr(counts), self._stream()),
-                   "ldpc_osdx_fs_decode")
-        out["perm"], out["parity"] = perm, parity
-        return out
+        return self._osd_decode("osdx", "fs_decode", y, C.byref(params), index, count, F, perm, parity, label_bits, counts, out)
 
     def osdx_pb_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
         """PB-OSD on front-end results of any supported shape.  ``params``: ``osd_params(order, _lib.OSD_PB, snr_db=...,
         aux=...)``, order 0..min(3, k); ``aux`` ([F, 4] int32, optional) receives {frontier comparisons, suc1, suc2, stop
         reason} per frame.  Returns the dict of ``osdx_search`` (best: rank in visit order, 0 = the all-zero TEP; ntep:
         cost_tep_num, or N_max when no rule fired)."""
-        F = self._osd_front_results(y, perm, parity, F)
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osdx_pb_search(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity),
-                                              C.byref(params), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
-                                              _ptr(out["ntep"]), self._stream()), "ldpc_osdx_pb_search")
-        return out
+        return self._osd_search("osdx", "pb_search", y, perm, parity, C.byref(params), index, count, F, out)
 
     def osdx_pb_decode(self, y, params, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
                        out=None):
         """Front end + PB-OSD of the frames y[index[f]] (or y[f]) for any supported shape: ``osdx_decode`` with the search
         of ``osdx_pb_search``; ``perm`` / ``parity`` / ``label_bits`` / ``counts`` as there."""
-        F, perm, parity = self._osdx_decode_args(y, index, F, perm, parity)
-        out = self._osd_outputs(out, F)
-        _lib.check(self.L.ldpc_osdx_pb_decode(self._ctx, _ptr(y), _ptr(index), _ptr(count), F, C.byref(params), _ptr(perm),
-                                              _ptr(parity), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
-                                              _ptr(out["ntep"]), _ptr(label_bits), _ptr(counts), self._stream()),
-                   "ldpc_osdx_pb_decode")
-        out["perm"], out["parity"] = perm, parity
-        return out
+        return self._osd_decode("osdx", "pb_decode", y, C.byref(params), index, count, F, perm, parity, label_bits, counts, out)
 
     def osdx_tep_eval(self, y, perm, parity, mask, index=None, count=None):
         """``osd_tep_eval`` for any supported shape (mask [F] int64: bit p < k flips primed MRB position p).
         Returns dict(cw[F,words] int64 original bit order, metric[F] f32, hd[F] i32)."""
-        return self._osd_tep_eval(self.L.ldpc_osdx_tep_eval, "ldpc_osdx_tep_eval", y, perm, parity, mask, index, count)
+        return self._osd_tep_eval("osdx", y, perm, parity, mask, index, count)
 
     # ------------------------------------------------------------------ H-form OSD (DL-OSD stage)
     def hosd_front(self, order_llr):

@@ -269,7 +269,7 @@ def test_unsupported_shapes_are_refused(name):
         assert torch.equal(bufs[k], clean[k]), k
 
 
-def test_bad_arguments_are_refused_and_the_old_entry_points_keep_their_refusal():
+def test_bad_arguments_are_refused_and_the_old_entry_points_keep_their_refusal(monkeypatch):
     dec = decoder("ldpc_96_48")
     y, _ = osdx_model.frames("ldpc_96_48", 1.5, 4, 2)
     yd = to_dev(y, dec)
@@ -318,6 +318,19 @@ def test_bad_arguments_are_refused_and_the_old_entry_points_keep_their_refusal()
     torch.cuda.synchronize()
     for k in bufs:
         assert torch.equal(bufs[k], clean[k]), k
+    # a mask with fewer rows than frames (the kernels read a row per frame) is refused before any launch: every call of the
+    # library asks for the stream
+    ccsds = decoder("ccsds")
+    yc = to_dev(osdx_model.frames("ccsds", 1.5, 4, 2)[0], ccsds)
+    perm, parity, _ = ccsds.osd_front(yc)
+    torch.cuda.synchronize()
+
+    def no_launch():
+        raise AssertionError("a launch was prepared")
+    monkeypatch.setattr(ccsds, "_stream", no_launch)
+    for tep_eval in (ccsds.osdx_tep_eval, ccsds.osd_tep_eval):
+        with pytest.raises(ValueError, match="mask: 3 rows for 4 frames"):
+            tep_eval(yc, perm, parity, mask[:3])
 
 
 def test_order_is_bounded_by_k():
