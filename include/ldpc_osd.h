@@ -434,10 +434,11 @@ int ldpc_osdx_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
 /* ---------------------------------------------------------------------------------------
  * OSD for high-rate short codes, i.e. every code with n <= 128 and 1 <= n-k <= 64 (hence every k from 1 to 127): the
  * reference's (121,80) array code, which the ldpc_osdx_* entry points above refuse for its k > 64.  Served: the front end,
- * the conventional search (orders 0..3), FS-OSD (orders 0..min(3, k)) and one-TEP evaluation.  Codes with k <= 64 are served
- * as well; there d_perm, d_cw, d_metric, d_best, d_ntep, d_hd and d_nswaps equal those of the ldpc_osdx_* call of the same
- * name bit for bit, and the first 64 rows of d_parity equal the d_parity of those calls.  PB-OSD stays with k <= 64
- * (ldpc_osdx_pb_*), the one-call pipeline with (128,64); codes with n-k > 64 or n > 128 are refused by every OSD entry point.
+ * the conventional search (orders 0..3), FS-OSD and PB-OSD (orders 0..min(3, k)) and one-TEP evaluation.  Codes with k <= 64
+ * are served as well; there d_perm, d_cw, d_metric, d_best, d_ntep, d_hd, d_nswaps and d_aux equal those of the ldpc_osdx_*
+ * call of the same name bit for bit, and the first 64 rows of d_parity equal the d_parity of those calls.  The staged PB
+ * routes, ldpc_pb_tuning, the LDPC_OSD_F_PB_* flags and the one-call pipeline stay with (128,64); codes with n-k > 64 or
+ * n > 128 are refused by every OSD entry point.
  * The contract is that of ldpc_osdx_front / _search / _decode -- d_index / d_count, ties of the sort, the pivot rule, the
  * TEP table of this code's k (first minimum), the float order of the metric, the nullable outputs, d_label_bits with
  * d_counts[3] as a pair or not at all, teps_total only with d_ntep -- with one layout changed:
@@ -462,6 +463,15 @@ int ldpc_osdx_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
  *   d_mask    [F][2] u64 : bit p of word 0 flips MRB position p, bit p of word 1 flips position 64 + p; bits at or
  *                          beyond k are ignored (for k <= 64 that is all of word 1)
  *   d_metric  [F] f32 and d_hd [F] i32 of ldpc_osdw_tep_eval: nullable, each on its own
+ * ldpc_osdw_pb_search / _pb_decode: the contract of ldpc_osdx_pb_search / _pb_decode, word for word -- `params` read for
+ * order (0..min(3, k)), algo (LDPC_OSD_PB), snr_db and d_aux ([F][4] i32, nullable: {frontier comparisons, suc1, suc2, stop
+ * reason}); the float conventions stated there with the chains over the MRB running over all k <= 127 positions;
+ * N_max = sum of C(k, w) over w <= order (341 504 at k = 127, order 3); d_best the rank in visit order, d_ntep cost_tep_num,
+ * or N_max when no rule fired; outputs nullable, each on its own; labels and counts as a pair or not at all; LDPC_E_ARG,
+ * naming the offender, for algo != LDPC_OSD_PB, an order outside 0..min(3, k), flags != 0, y_frames != 0 and a NULL in a
+ * required pointer; ldpc_osdw_pb_decode is ldpc_osdw_front plus the scan, two launches -- with d_parity [F][128] u64 as
+ * above.  The frontier lives in LDS, at most 1 + (k-1) + C(k-1, 2) = 8002 slots of 8 bytes at k = 127: an order-3 launch
+ * takes 28, 44 or 75 KiB of LDS per workgroup for k <= 64, k <= 91 and k <= 127; no workspace, no per-stream state.
  * ------------------------------------------------------------------------------------- */
 int ldpc_osdw_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
 int ldpc_osdw_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
@@ -483,6 +493,13 @@ int ldpc_osdw_fs_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
 int ldpc_osdw_tep_eval(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
                        const uint8_t *d_perm, const uint64_t *d_parity, const uint64_t *d_mask, uint64_t *d_cw,
                        float *d_metric, int32_t *d_hd, void *stream);
+int ldpc_osdw_pb_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *params, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, void *stream);
+int ldpc_osdw_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const ldpc_osd_params *params, uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits,
+                        int64_t *d_counts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H):

@@ -1,6 +1,6 @@
 """NMS + order-p OSD (conventional, FS-OSD or PB-OSD) of any short code (1 <= k <= 64, 1 <= n-k <= 64): FER before and after the
-OSD, and the two OSD kernels timed.  A high-rate code (k > 64, n <= 128, n-k <= 64) runs the conventional search or FS-OSD
-through the ldpc_osdw_* family.
+OSD, and the two OSD kernels timed.  A high-rate code (k > 64, n <= 128, n-k <= 64) runs the same three searches through the
+ldpc_osdw_* family.
 
     python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2
     python scripts/osdx_fer.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --snr 2.5 --frames 131072 --T 10 --order 2 \
@@ -23,9 +23,11 @@ same frames through the literal replay route (LDPC_OSD_F_PB_REPLAY: the same alg
 A code that ldpc_osdx_* refuses and ldpc_osdw_* serves (k > 64, e.g. tests/golden/ArrayCode_N121_K80_r0.66.alist) runs the
 conventional search through ldpc_osdw_decode, osdw_front_kernel and osdw_search_kernel timed like the other legs.  --osd fs runs
 ldpc_osdw_fs_decode there: the same line of TEPs per frame, the FER of the conventional scan of the same order on the same frames
-next to it, and osdw_fs_kernel timed next to osdw_search_kernel.  --osd pb exits with a message there (PB-OSD stays with
-k <= 64).  On a code both families serve, the conventional run also times the osdw kernels on the same frames in the same run,
-alternating with the osdx kernels, and the --osd fs run times osdw_fs_kernel alternating with osdx_fs_kernel.
+next to it, and osdw_fs_kernel timed next to osdw_search_kernel.  --osd pb runs ldpc_osdw_pb_decode there: the same line of TEPs
+per frame and stop shares, osdw_pb_kernel timed next to osdw_search_kernel of the same order and, with --tau-e, osdw_fs_kernel
+on the same frames.  On a code both families serve, the conventional run also times the osdw kernels on the same frames in the
+same run, alternating with the osdx kernels, the --osd fs run times osdw_fs_kernel alternating with osdx_fs_kernel and the
+--osd pb run osdw_pb_kernel alternating with osdx_pb_kernel.
 One JSON line at the end."""
 import argparse
 import json
@@ -101,12 +103,9 @@ def main(argv=None):
         args.tau_e = 6.5
 
     dec = Decoder(Code(args.alist) if args.alist else Code(), 0)
-    wide = dec.osdw_supported and not dec.osdx_supported     # k > 64: the high-rate family, conventional search and FS-OSD
+    wide = dec.osdw_supported and not dec.osdx_supported     # k > 64: the high-rate family
     if not dec.osdx_supported and not dec.osdw_supported:
         raise SystemExit(f"osdx_fer: the OSD kernels serve n <= 128 and 1 <= n-k <= 64; this code is ({dec.n},{dec.k})")
-    if wide and pb:
-        raise SystemExit(f"osdx_fer: --osd {args.osd} needs 1 <= k <= 64; this code is ({dec.n},{dec.k}), which only the conventional "
-                         "search and FS-OSD serve (ldpc_osdw_decode, ldpc_osdw_fs_decode: drop --osd or take --osd fs)")
     B = args.frames
     y, labels = make_frames(dec, B, args.seed, args.snr)
     res = dec.nms(y, args.T, args.alpha)
@@ -123,7 +122,8 @@ def main(argv=None):
     elif pb:
         aux = torch.zeros((idx.shape[0], 4), dtype=torch.int32, device=dec.device)
         pbp = dec.osd_params(args.order, _lib.OSD_PB, snr_db=args.snr, aux=aux)
-        out = dec.osdx_pb_decode(y, pbp, index=idx, count=count, label_bits=labels, counts=counts)
+        pb_decode = dec.osdw_pb_decode if wide else dec.osdx_pb_decode
+        out = pb_decode(y, pbp, index=idx, count=count, label_bits=labels, counts=counts)
     elif wide:
         out = dec.osdw_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
     else:
@@ -190,8 +190,20 @@ def main(argv=None):
         if (dec.n, dec.k) == (128, 64):                  # the specialised kernel on the same front-end results, in the same run
             out2 = dec.osd_search(y, out["perm"], out["parity"], fsp, index=idx, count=count)
             legs.append(("osd_fs_kernel", lambda: dec.osd_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out2)))
+    elif pb and wide:
+        legs[1] = ("osdw_pb_kernel", lambda: dec.osdw_pb_search(y, out["perm"], out["parity"], pbp, index=idx, count=count, out=out))
+        outc = dec.osdw_search(y, out["perm"], out["parity"], args.order, index=idx, count=count)
+        legs.append(("osdw_search_kernel", lambda: dec.osdw_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=outc)))
+        if args.tau_e is not None:                       # FS-OSD of the same order on the same frames
+            fsp = dec.osd_params(args.order, _lib.OSD_FS, fs_beta=args.beta, fs_tau_e=args.tau_e, fs_tau_psc=args.tau_psc)
+            outf = dec.osdw_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count)
+            legs.append(("osdw_fs_kernel", lambda: dec.osdw_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=outf)))
     elif pb:
         legs[1] = ("osdx_pb_kernel", lambda: dec.osdx_pb_search(y, out["perm"], out["parity"], pbp, index=idx, count=count, out=out))
+        if dec.osdw_supported:                           # both families serve the code: osdw_pb_kernel on the same frames
+            outw = dec.osdw_pb_decode(y, dec.osd_params(args.order, _lib.OSD_PB, snr_db=args.snr), index=idx, count=count)
+            pbw = dec.osd_params(args.order, _lib.OSD_PB, snr_db=args.snr)
+            legs.append(("osdw_pb_kernel", lambda: dec.osdw_pb_search(y, outw["perm"], outw["parity"], pbw, index=idx, count=count, out=outw)))
         if (dec.n, dec.k) == (128, 64):                  # the specialised routes on the same front-end results, in the same run
             for name, path in (("osd_search(PB replay)", "replay"), ("osd_search(PB staged)", None)):
                 pr = dec.osd_params(args.order, _lib.OSD_PB, snr_db=args.snr, pb_path=path)

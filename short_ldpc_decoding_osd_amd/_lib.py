@@ -24,7 +24,7 @@ SYMBOLS = (
     "ldpc_osdx_supported", "ldpc_osdx_front", "ldpc_osdx_search", "ldpc_osdx_decode",
     "ldpc_osdx_fs_search", "ldpc_osdx_fs_decode", "ldpc_osdx_tep_eval", "ldpc_osdx_pb_search", "ldpc_osdx_pb_decode",
     "ldpc_osdw_supported", "ldpc_osdw_front", "ldpc_osdw_search", "ldpc_osdw_decode",
-    "ldpc_osdw_fs_search", "ldpc_osdw_fs_decode", "ldpc_osdw_tep_eval",
+    "ldpc_osdw_fs_search", "ldpc_osdw_fs_decode", "ldpc_osdw_tep_eval", "ldpc_osdw_pb_search", "ldpc_osdw_pb_decode",
     "ldpc_hosd_pattern_teps", "ldpc_hosd_front", "ldpc_hosd_search", "ldpc_hosd_sliding", "ldpc_dia_cnn",
     "ldpc_pipeline_run", "ldpc_pipeline_timing",
 )
@@ -117,8 +117,6 @@ def load():
         "ldpc_osd_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
         "ldpc_osd_tep_eval": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "ldpc_osd_counts": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, vp]),
-        "ldpc_osdx_pb_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
-        "ldpc_osdx_pb_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ldpc_hosd_pattern_teps": (i64, [i32, pi32, pi32, C.POINTER(C.c_uint8)]),
         "ldpc_hosd_front": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, vp]),
         "ldpc_hosd_search": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -138,6 +136,8 @@ def load():
             f"ldpc_{fam}_fs_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
             f"ldpc_{fam}_fs_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
             f"ldpc_{fam}_tep_eval": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+            f"ldpc_{fam}_pb_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
+            f"ldpc_{fam}_pb_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         })
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError here = ABI/header drift, which must be loud

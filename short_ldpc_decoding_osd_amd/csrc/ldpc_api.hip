@@ -59,8 +59,9 @@ int ldpc_ctx_create(const ldpc_code *code, int32_t device, ldpc_ctx **out)
             OsdwTablesHost host;
             if ((rc = pack_osdw_tables(ctx->code, ctx->osd_tables, w, host))) break;
             if (w.k && (rc = upload(host.Gcols, &w.d_Gcols))) break;
-            if (w.k && w.own_tep && ((rc = upload(host.tep, &w.d_tep)) || (rc = upload(host.tep_fs, &w.d_tep_fs)))) break;
-            if (w.k && !w.own_tep) { w.d_tep = ctx->osd_tables.d_tep; w.d_tep_fs = ctx->osd_tables.d_tep_fs; }
+            if (w.k && w.own_tep && ((rc = upload(host.tep, &w.d_tep)) || (rc = upload(host.tep_fs, &w.d_tep_fs)) ||
+                                       (rc = upload(host.pb, &w.d_pb)))) break;
+            if (w.k && !w.own_tep) { w.d_tep = ctx->osd_tables.d_tep; w.d_tep_fs = ctx->osd_tables.d_tep_fs; w.d_pb = ctx->osd_tables.d_pb; }
         }
         if ((rc = probe_dpp(&ctx->dpp_ror_up, &ctx->dpp_wave_rol_dir))) break;
         // event pool of ldpc_pipeline_run's timing slots: created (and recorded once: the first record of an
@@ -95,7 +96,9 @@ void ldpc_ctx_destroy(ldpc_ctx *ctx)
     (void)hipFree(ctx->osd_tables.d_Gcols); (void)hipFree(ctx->osd_tables.d_tep); (void)hipFree(ctx->osd_tables.d_tep_fs);
     (void)hipFree(ctx->osd_tables.d_pb);
     (void)hipFree(ctx->osdw_tables.d_Gcols);
-    if (ctx->osdw_tables.own_tep) { (void)hipFree(ctx->osdw_tables.d_tep); (void)hipFree(ctx->osdw_tables.d_tep_fs); }
+    if (ctx->osdw_tables.own_tep) {
+        (void)hipFree(ctx->osdw_tables.d_tep); (void)hipFree(ctx->osdw_tables.d_tep_fs); (void)hipFree(ctx->osdw_tables.d_pb);
+    }
     (void)hipFree(ctx->d_chk_ptr); (void)hipFree(ctx->d_chk_var);
     (void)hipFree(ctx->d_var_ptr); (void)hipFree(ctx->d_var_edge);
     if (ctx->timing) {

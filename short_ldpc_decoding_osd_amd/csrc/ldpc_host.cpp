@@ -262,6 +262,28 @@ static int pack_fs_table(int k, std::vector<uchar4> &out, int (&off)[4], int (&c
     return LDPC_OK;
 }
 
+// The code-only constants of PB-OSD with n and k as kernel arguments (kPbx* layout, ldpc_pbx.h): P[Bin(m, 1/2) <= b] by the float64
+// pmf recurrence of the oracle (q^m by left-to-right square-and-multiply, ratio p / q = 1), and the ratios of consecutive
+// binomial coefficients of m = n - k <= 64 and of k (its first 64: the kernels read i < order <= 3)
+static void pack_pb_table(int n, int k, std::vector<double> &pb)
+{
+    const int m = n - k;
+    pb.assign(65 + 64 + 64, 0.0);
+    double *cdf = pb.data(), *coef_m = cdf + 65, *coef_k = coef_m + 64;
+    for (int i = 0; i < m; ++i) coef_m[i] = (double)(m - i) / (double)(i + 1);
+    for (int i = 0; i < k && i < 64; ++i) coef_k[i] = (double)(k - i) / (double)(i + 1);
+    int top = 0;
+    while ((m >> (top + 1)) != 0) ++top;
+    double tt = 0.5;
+    for (int b = top - 1; b >= 0; --b) {
+        tt = tt * tt;
+        if ((m >> b) & 1) tt = tt * 0.5;
+    }
+    double acc = tt;
+    cdf[0] = acc;
+    for (int i = 0; i < m; ++i) { tt = tt * coef_m[i] * (0.5 / 0.5); acc = acc + tt; cdf[i + 1] = acc; }
+}
+
 int pack_osd_tables(const ldpc_code &c, OsdTables &t, OsdTablesHost &host)
 {
     t = OsdTables();
@@ -278,25 +300,7 @@ int pack_osd_tables(const ldpc_code &c, OsdTables &t, OsdTablesHost &host)
     if ((total = tep_table(c.k, 3, sup.data(), nullptr)) < 0) return (int)total;
     pack_supports(sup, host.tep);
     if (int rc = pack_fs_table(c.k, host.tep_fs, t.fs_off, t.fs_cnt)) return rc;
-    // any-shape PB-OSD: P[Bin(m, 1/2) <= b] by the float64 pmf recurrence of the oracle (q^m by left-to-right square-and-multiply,
-    // ratio p / q = 1), and the ratios of consecutive binomial coefficients of m and k
-    {
-        const int m = c.n - c.k;
-        host.pb.assign(65 + 64 + 64, 0.0);
-        double *cdf = host.pb.data(), *coef_m = cdf + 65, *coef_k = coef_m + 64;
-        for (int i = 0; i < m; ++i) coef_m[i] = (double)(m - i) / (double)(i + 1);
-        for (int i = 0; i < c.k; ++i) coef_k[i] = (double)(c.k - i) / (double)(i + 1);
-        int top = 0;
-        while ((m >> (top + 1)) != 0) ++top;
-        double tt = 0.5;
-        for (int b = top - 1; b >= 0; --b) {
-            tt = tt * tt;
-            if ((m >> b) & 1) tt = tt * 0.5;
-        }
-        double acc = tt;
-        cdf[0] = acc;
-        for (int i = 0; i < m; ++i) { tt = tt * coef_m[i] * (0.5 / 0.5); acc = acc + tt; cdf[i + 1] = acc; }
-    }
+    pack_pb_table(c.n, c.k, host.pb);
     t.n = c.n; t.k = c.k;
     return LDPC_OK;
 }
@@ -321,6 +325,7 @@ int pack_osdw_tables(const ldpc_code &c, const OsdTables &base, OsdwTables &t, O
         pack_supports(sup, host.tep);
         host.tep_fs.reserve((size_t)total);
         if (int rc = pack_fs_table(c.k, host.tep_fs, t.fs_off, t.fs_cnt)) return rc;
+        pack_pb_table(c.n, c.k, host.pb);
     } else {
         for (int w = 0; w < 4; ++w) { t.fs_off[w] = base.fs_off[w]; t.fs_cnt[w] = base.fs_cnt[w]; }
     }

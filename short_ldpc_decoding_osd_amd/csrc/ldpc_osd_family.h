@@ -122,7 +122,7 @@ int family_decode(ldpc_ctx *ctx, const OsdFrames &fr, int32_t order, uint8_t *d_
     return family_launch_search<FAM>(ctx, fr, d_perm, d_parity, order, o, c, (hipStream_t)stream);
 }
 
-// A scan that takes ldpc_osd_params (FS-OSD in both families, PB-OSD in ldpc_osdx.hip): what its entry points check and launch
+// A scan that takes ldpc_osd_params (FS-OSD and PB-OSD in both families; each family launches its own PB kernel): what its entry points check and launch
 struct OsdScan {
     int algo;
     const char *algo_name;

@@ -23,7 +23,7 @@ struct OsdTables {
     int64_t ntep[4] = {0, 0, 0, 0};
     uchar4 *d_tep_fs = nullptr;  // FS-OSD visit order (generate_sequential_teps) of this k: weight classes 1..min(3, k) back to back
     int fs_off[4] = {0, 0, 0, 0}, fs_cnt[4] = {0, 0, 0, 0};   // weight class w: offset / count inside d_tep_fs
-    double *d_pb = nullptr;      // any-shape PB-OSD (ldpc_osdx_pb.h): [65] P[Bin(n-k, 1/2) <= b], then [64] (n-k-i)/(i+1) and [64] (k-i)/(i+1)
+    double *d_pb = nullptr;      // PB-OSD of ldpc_osdx_pb.h / ldpc_osdw_pb.h (layout: ldpc_pbx.h): [65] P[Bin(n-k, 1/2) <= b], then [64] (n-k-i)/(i+1) and [64] (k-i)/(i+1)
 };
 
 // the host images of the device tables
@@ -44,20 +44,22 @@ struct OsdwTables {
     int n = 0, k = 0;            // the shape the tables were built for; k = 0: no tables (ldpc_osdw_* report UNSUPPORTED)
     u64 *d_Gcols = nullptr;      // [n][2] column v of G as two words: bit r of word 0 = G[r][v], bit r of word 1 = G[64 + r][v]
     uchar4 *d_tep = nullptr;     // conventional order-3 TEP table of this k; for k <= 64 it IS OsdTables::d_tep (one device copy)
-    bool own_tep = false;        // d_tep and d_tep_fs were allocated for this member (k > 64) and are freed with it
+    bool own_tep = false;        // d_tep, d_tep_fs and d_pb were allocated for this member (k > 64) and are freed with it
     int64_t ntep[4] = {0, 0, 0, 0};
     uchar4 *d_tep_fs = nullptr;  // FS-OSD visit order of this k, weight classes 1..min(3, k) back to back; for k <= 64 it IS OsdTables::d_tep_fs
     int fs_off[4] = {0, 0, 0, 0}, fs_cnt[4] = {0, 0, 0, 0};   // weight class w: offset / count inside d_tep_fs
+    double *d_pb = nullptr;      // PB-OSD (ldpc_osdw_pb.h), the layout of OsdTables::d_pb; for k <= 64 it IS OsdTables::d_pb
 };
 
 struct OsdwTablesHost {
     std::vector<u64> Gcols;      // [n][2]
     std::vector<uchar4> tep;     // filled only where `base` has no table of this k (k > 64)
     std::vector<uchar4> tep_fs;  // likewise (341 503 entries, 1.37 MB, at k = 127)
+    std::vector<double> pb;      // likewise (193 entries)
 };
 
 // For a code with n <= 128, 1 <= n - k <= 64, k >= 1 and G = [k][n]: fills `host` and the shape, boundaries, offsets and counts
-// of `t` (never a device pointer; t.own_tep tells whether host.tep and host.tep_fs were filled).  `base`: the OsdTables already
+// of `t` (never a device pointer; t.own_tep tells whether host.tep, host.tep_fs and host.pb were filled).  `base`: the OsdTables already
 // packed for the same code.  Any other code leaves t.k = 0.  LDPC_OK, or the error of tep_table / tep_table_fs.  Pure host code
 // (ldpc_host.cpp).
 int pack_osdw_tables(const ldpc_code &c, const OsdTables &base, OsdwTables &t, OsdwTablesHost &host);

@@ -1,10 +1,14 @@
 // OSD for high-rate short codes: the ldpc_osdw_* entry points.
 // For every code with n <= 128 and 1 <= n - k <= 64, hence k up to 127: the front end, the conventional order-p scan (device
-// code: ldpc_osdw.h), FS-OSD and the one-TEP primitive (ldpc_osdw_fs.h).
-// PB-OSD stays with ldpc_osdx_pb_* (k <= 64), the one-call pipeline with the (128,64) kernels.
+// code: ldpc_osdw.h), FS-OSD and the one-TEP primitive (ldpc_osdw_fs.h) and PB-OSD (ldpc_osdw_pb.h).  The PB tuning and routes and
+// the one-call pipeline stay with the (128,64) kernels of ldpc_osd.hip / ldpc_osd_pb.hip.
 // The two-word G columns and the TEP tables of k are the context's OsdwTables (ldpc_osd_tables.h), uploaded by ldpc_ctx_create.
-// Validation, launches and the bodies of the entry points are those of ldpc_osd_family.h, shared with ldpc_osdx.hip.
+// Validation, launches and the bodies of the entry points are those of ldpc_osd_family.h, shared with ldpc_osdx.hip; PB-OSD has a
+// kernel per family, so each family launches its own.
+#include <cmath>
+
 #include "ldpc_osdw_fs.h"
+#include "ldpc_osdw_pb.h"
 #include "ldpc_osd_family.h"
 
 namespace ldpc {
@@ -17,6 +21,29 @@ struct Osdw {
     static constexpr auto fs = osdw_fs_kernel;
     static constexpr auto tep_eval = osdw_tep_eval_kernel;
 };
+
+static int osdw_launch_pb(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *p,
+                          const OsdScanOut &o, OsdCounting c, hipStream_t s)
+{
+    const OsdwTables &t = ctx->osdw_tables;
+    PbxParams pp;
+    pp.order = p->order;
+    pp.nmax = (int)t.ntep[p->order];
+    pp.c4 = (float)(-4.0 * (1.0 / pow(10.0, (double)p->snr_db / 10.0)));    // -4 * noise_variance, pb_testing.py:50-52
+    // the frontier's LDS is sized by the order and, at order 3, by k: 128 slots up to order 2, then the smallest of 2048 (k <= 64),
+    // 4096 (k <= 91) and 8064 (k <= 127) that holds the k + C(k-1, 2) runs (occupancy: ldpc_osdw_pb.h)
+    const int slots = pbw_slots3(t.k);
+    const auto kern = p->order < 3   ? osdw_pb_kernel<false, 128>
+                      : slots <= 2048 ? osdw_pb_kernel<true, 2048>
+                      : slots <= 4096 ? osdw_pb_kernel<true, 4096>
+                                      : osdw_pb_kernel<true, 8064>;
+    hipLaunchKernelGGL(kern, dim3(frame_grid(fr.F)), dim3(64), 0, s, fr.y, fr.index, fr.count, (long long)fr.F, t.n, t.k, d_perm,
+                       reinterpret_cast<const u64 *>(d_parity), t.d_pb, pp, reinterpret_cast<u64 *>(o.cw), o.metric, o.best, o.ntep,
+                       static_cast<int *>(p->d_aux), c.label, c.counts);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+constexpr OsdScan osdw_pb_scan{LDPC_OSD_PB, "LDPC_OSD_PB", true, osdw_launch_pb};
 
 }  // namespace ldpc
 
@@ -62,6 +89,22 @@ int ldpc_osdw_fs_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
 {
     return family_scan_decode<Osdw>(ctx, {d_y, d_index, d_count, F}, params, fs_scan<Osdw>, d_perm, d_parity,
                                     {d_cw, d_metric, d_best, d_ntep}, osd_counting(d_label_bits, d_counts), stream, "ldpc_osdw_fs_decode");
+}
+
+int ldpc_osdw_pb_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F, const uint8_t *d_perm,
+                        const uint64_t *d_parity, const ldpc_osd_params *params, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                        int32_t *d_ntep, void *stream)
+{
+    return family_scan_search<Osdw>(ctx, {d_y, d_index, d_count, F}, d_perm, d_parity, params, osdw_pb_scan,
+                                    {d_cw, d_metric, d_best, d_ntep}, stream, "ldpc_osdw_pb_search");
+}
+
+int ldpc_osdw_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const ldpc_osd_params *params, uint8_t *d_perm, uint64_t *d_parity, uint64_t *d_cw, float *d_metric,
+                        int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits, int64_t *d_counts, void *stream)
+{
+    return family_scan_decode<Osdw>(ctx, {d_y, d_index, d_count, F}, params, osdw_pb_scan, d_perm, d_parity,
+                                    {d_cw, d_metric, d_best, d_ntep}, osd_counting(d_label_bits, d_counts), stream, "ldpc_osdw_pb_decode");
 }
 
 int ldpc_osdw_tep_eval(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F, const uint8_t *d_perm,

@@ -1,63 +1,74 @@
-// OSD for short codes of any shape: osdx_pb_kernel.
-// PB-OSD (pb_osd, PB_OSD/pb_testing.py:100-149) as pb_seq_kernel (ldpc_pb_seq.h) replays it -- pop the first minimum of the
-// frontier by (sum, insertion order), append at most two children, the promising rule, the cost, the success rule -- with the
-// code's n and k as kernel arguments, one frame per wavefront, the float conventions of oracle/ldpc_oracle.c orc_pb_osd with 64
-// replaced by k (MRB) and m = n - k (parity part).  The per-frame prologue and epilogue are osdx_prepare / osdx_finish.
+// OSD for high-rate short codes: osdw_pb_kernel.
+// PB-OSD (pb_osd, PB_OSD/pb_testing.py:100-149) as osdx_pb_kernel (ldpc_osdx_pb.h) replays it -- pop the first minimum of the
+// frontier by (sum, insertion order), append the extended and then the adjacent child, the promising rule, the cost, the success
+// rule, the same bookkeeping of cmp, suc1, suc2, stop and ntep -- for k up to 127: on SearchWLds (128 rows of P', 128 MRB
+// weights), with osdw_prepare / osdw_finish (ldpc_osdw_fs.h) as prologue and epilogue, one frame per wavefront.  The float
+// conventions are those of oracle/ldpc_oracle.c orc_pb_osd with 64 replaced by k (MRB) and m = n - k (parity part).
 //
-// The frontier needs no list that grows and no workspace.  Every TEP has one parent (ldpc_pb_common.h, fact 1), and an adjacent
-// child replaces its parent, so the live entries form RUNS: the weight-1 run, one weight-2 run per smaller index a, one weight-3
-// run per pair (a, b) with b < k - 1 -- 1 + (k - 1) + C(k - 1, 2) <= 2017 runs, one live entry each at most.  A run owns a fixed
-// slot of LDS; the slot number is the run's prefix, the slot holds the sum, the insertion sequence number and the cursor (the
-// largest index):
+// The frontier is the one of osdx_pb_kernel: the live entries form RUNS with one live entry each at most, a run owns a fixed
+// slot of LDS, the slot number is the run's prefix and the slot holds the sum, the insertion sequence number and the cursor:
 //   slot 0                        {c}
 //   slot 1 + a                    {a, c}        a = 0 .. k-2
 //   slot k + b (b - 1) / 2 + a    {a, b, c}     a < b <= k-2
-// A pop rewrites its own slot with the adjacent child (or empties it) and fills one other slot with the extended child.
-// Orders <= 2 use k <= 64 slots, one per lane: a pop is one wave arg-min.  Order 3 keeps the minimum of every chunk of 64 slots
-// in the registers of lane `chunk` (<= 32 chunks): a pop is an arg-min over those, a re-reduction of the popped slot's chunk and
-// a compare for the extended child's chunk.
+// What k > 64 changes:
+//   - the per-frame chains (the sum for pt, the product spl) run over k <= 127 MRB positions, q[] holds 128 + 64 entries;
+//   - orders <= 2 have up to 127 runs: a lane reads the slots lane and 64 + lane and a pop is one wave arg-min over the smaller
+//     of the two;
+//   - order 3 has up to 1 + 126 + 7875 = 8002 runs, 126 chunks of 64 slots: lane c holds the minima of the chunks c and 64 + c
+//     (CPL = 2 chunks per lane), a pop is a wave arg-min over the smaller of the two, a re-reduction of the popped slot's
+//     chunk and a compare for the extended child's chunk;
+//   - the b of a weight-3 slot is found by two ballots (candidates lane and 64 + lane);
+//   - the winner is remembered as its support (weight and up to three positions), from which osdw_finish gets its flips.
+// LDS, by the slot count SLOTS (a template parameter, chosen by the host from the order and k; SearchWLds is 10 000 B of it):
+//   orders <= 2      128 slots    12 832 B
+//   order 3          2048 slots   28 192 B   k <= 64     (5 workgroups per CU of 160 KiB)
+//                    4096 slots   44 576 B   k <= 91     (3)
+//                    8064 slots   76 320 B   k <= 127    (2)
+// No workspace and no per-stream state: the call is graph-capturable as it is.
 #pragma once
 
-#include "ldpc_osdx.h"
+#include "ldpc_osdw_fs.h"
 #include "ldpc_pb_expf.h"
 #include "ldpc_pbx.h"
 
 namespace ldpc {
 
-// PbxParams, the kPbx* layout of the context's PB table, kPbxEmpty, readlane_f64 and pbx_argmin: ldpc_pbx.h (shared with
-// osdw_pb_kernel)
-
 template <int SLOTS>
-struct __attribute__((aligned(16))) PbxLds {
+struct __attribute__((aligned(16))) PbwLds {
     double cdfA[65];         // P[Bin(m, p1) <= b]
     double cdfH[65];         // P[Bin(m, 1/2) <= b]
-    float q[128];            // q[l] = sigmoid(c4 |y'_l|) (MRB), q[64 + l] = the same of parity position k + l
+    float q[192];            // q[l] = sigmoid(c4 |y'_l|) (MRB, l < 128), q[128 + l] = the same of parity position k + l
     float fsum[SLOTS];       // the runs' live entries: reliability sum (+inf: none)
     int fmeta[SLOTS];        //                         seq << 8 | cursor
 };
 
-// per-frame PB quantities (wave-uniform): pb_frame_setup of ldpc_pb_common.h with the split at k.  w = |y'| in the layout of
-// osdx_prepare; coef_m / coef_k: lane i holds (m - i) / (i + 1) and (k - i) / (i + 1).
-struct PbxFrame {
+// the slots an order-3 frontier of k needs (orders <= 2 need k <= 127 of them)
+constexpr int pbw_slots3(int k) { return k + (k - 1) * (k - 2) / 2; }
+
+// per-frame PB quantities (wave-uniform): pbx_frame_setup of ldpc_osdx_pb.h on the layout of osdw_prepare (w[0..127] the MRB,
+// w[128..191] the parity part).  coef_m / coef_k: lane i holds (m - i) / (i + 1) and (k - i) / (i + 1).
+struct PbwFrame {
     float spl, lrb_mean;
     double p_t_suc, p_t_pro;
 };
-__device__ __forceinline__ PbxFrame pbx_frame_setup(const float *w, float *q, double *cdfA, const PbxParams &P, int k, int m, double coef_m,
+__device__ __forceinline__ PbwFrame pbw_frame_setup(const float *w, float *q, double *cdfA, const PbxParams &P, int k, int m, double coef_m,
                                                     double coef_k, float best0, int lane)
 {
     q[lane] = 1.0f / (1.0f + det_expf(-(P.c4 * w[lane])));
     q[lane + 64] = 1.0f / (1.0f + det_expf(-(P.c4 * w[lane + 64])));
+    q[lane + 128] = 1.0f / (1.0f + det_expf(-(P.c4 * w[lane + 128])));
     wave_fence();
     // four sequential chains, ascending position, one per lane 0..3 with one fused multiply-add per step (acc * 1 + x is the sum,
-    // acc * x + 0 the product, both rounded once like the plain operations); a chain ends at its own length
+    // acc * x + 0 the product, both rounded once like the plain operations); a chain ends at its own length (beyond it the
+    // step reads position 0 and is discarded)
     const int ch = lane & 3;
-    const float *src = ch == 0 ? q + 64 : (ch == 1 ? w + 64 : q);
+    const float *src = ch == 0 ? q + 128 : (ch == 1 ? w + 128 : q);
     const int len = ch < 2 ? m : k;
     const bool prod = ch == 3;
     float acc = prod ? 1.0f : 0.0f;
 #pragma unroll 8
-    for (int p = 0; p < 64; ++p) {
-        const float x = src[p];
+    for (int p = 0; p < 128; ++p) {
+        const float x = src[p < len ? p : 0];
         const float nx = __builtin_fmaf(acc, prod ? 1.0f - x : 1.0f, prod ? 0.0f : x);
         acc = p < len ? nx : acc;
     }
@@ -95,7 +106,7 @@ __device__ __forceinline__ PbxFrame pbx_frame_setup(const float *w, float *q, do
         for (int i = 0; i < P.order; ++i) { t = t * readlane_f64(coef_k, i) * ratio2; a = a + t; }
         niu = a;
     }
-    PbxFrame F;
+    PbwFrame F;
     F.spl = spl; F.lrb_mean = lrb_mean;
     F.p_t_suc = 0.99 * niu;
     F.p_t_pro = 0.002 * __builtin_sqrt((1.0 - niu) / (double)P.nmax);
@@ -103,23 +114,25 @@ __device__ __forceinline__ PbxFrame pbx_frame_setup(const float *w, float *q, do
     return F;
 }
 
+//   O3: the frontier holds weight-3 runs (order 3); SLOTS >= 64 * ceil(slots of this order and k / 64), 128 for orders <= 2
 //   aux_out [F][4] i32 (nullable): {frontier comparisons, suc1, suc2, stop reason}
 //   counts[3] += {frames, frames_wrong, teps_total} (with label; teps_total sums the frame's own ntep, only with ntep_out): one
 //   atomic per counter and wavefront, after its last frame.
-template <bool O3>
-__global__ __launch_bounds__(64) void osdx_pb_kernel(const float *__restrict__ y, const int *__restrict__ index, const int *__restrict__ count,
+template <bool O3, int SLOTS>
+__global__ __launch_bounds__(64) void osdw_pb_kernel(const float *__restrict__ y, const int *__restrict__ index, const int *__restrict__ count,
         long long F, int n, int k, const unsigned char *__restrict__ perm_in, const u64 *__restrict__ parity_in,
         const double *__restrict__ pbtab, PbxParams P, u64 *__restrict__ cw_out, float *__restrict__ metric_out,
         int *__restrict__ best_out, int *__restrict__ ntep_out, int *__restrict__ aux_out, const u64 *__restrict__ label,
         u64 *__restrict__ counts)
 {
-    constexpr int SLOTS = O3 ? 2048 : 64;
-    __shared__ SearchLds L;   // one wavefront per workgroup: compile-time LDS base for the LUT reads
-    __shared__ PbxLds<SLOTS> B;
+    static_assert(O3 ? SLOTS % 64 == 0 && SLOTS <= 128 * 64 : SLOTS == 128, "at most two chunks, or two slots, per lane");
+    constexpr int CPL = O3 ? (SLOTS / 64 + 63) / 64 : 2;   // per lane: chunk minima held (order 3), slots read (orders <= 2)
+    __shared__ SearchWLds L;   // one wavefront per workgroup: compile-time LDS base for the LUT reads
+    __shared__ PbwLds<SLOTS> B;
     const int lane = threadIdx.x;
     const int m = n - k;
     const int words = (n + 63) >> 6;
-    const int nchunks = O3 ? (k + (k - 1) * (k - 2) / 2 + 63) >> 6 : 1;
+    const int nchunks = O3 ? (pbw_slots3(k) + 63) >> 6 : 2;   // (the host keeps 64 * nchunks <= SLOTS)
     const long long nframes = frame_count(count, F);
     unsigned long long seen = 0, wrong = 0, nteps = 0;
     const double coef_m = pbtab[kPbxCoefM + lane], coef_k = pbtab[kPbxCoefK + lane];
@@ -129,42 +142,53 @@ __global__ __launch_bounds__(64) void osdx_pb_kernel(const float *__restrict__ y
 
     for (long long f = blockIdx.x; f < nframes; f += gridDim.x) {
         const long long src = index ? index[f] : f;
-        const OsdxFrame S = osdx_prepare(L, y, src, perm_in, parity_in, f, n, k, lane);
+        const OsdwFrame S = osdw_prepare(L, y, src, perm_in, parity_in, f, n, k, lane);
         float best = tep_cost(L, 0.0f, S.d0);      // all-zero TEP (:101-106)
-        u64 bestD = S.d0, bestE = 0;
+        u64 bestD = S.d0;
+        int bw = 0, b0 = 0, b1 = 0, b2 = 0;         // the winner's support: weight and positions (ascending)
         int bestidx = 0, ntep = P.nmax, stop = 0, cmp = 0, suc1 = 0, suc2 = 0;
         if (P.nmax > 1) {
-            const PbxFrame Fr = pbx_frame_setup(L.w, B.q, B.cdfA, P, k, m, coef_m, coef_k, best, lane);
+            const PbwFrame Fr = pbw_frame_setup(L.w, B.q, B.cdfA, P, k, m, coef_m, coef_k, best, lane);
             const float wk = L.w[k - 1];
             // the frontier: every run empty, then the starting point {k-1} (:109-110) in the weight-1 run
             for (int c = 0; c < nchunks; ++c) { B.fsum[c * 64 + lane] = __builtin_inff(); B.fmeta[c * 64 + lane] = kPbxEmpty; }
             wave_fence();
             if (lane == 0) { B.fsum[0] = wk; B.fmeta[0] = k - 1; }
             wave_fence();
-            // order 3: lane c holds the minimum of chunk c as (sum, meta, slot)
-            float csum = lane == 0 ? wk : __builtin_inff();
-            int cmeta = lane == 0 ? k - 1 : kPbxEmpty, cslot = lane * 64;
+            // order 3: lane c holds the minima of the chunks c + 64 i as (sum, meta, slot)
+            float csum[CPL];
+            int cmeta[CPL], cslot[CPL];
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) { csum[i] = __builtin_inff(); cmeta[i] = kPbxEmpty; cslot[i] = (i * 64 + lane) * 64; }
+            if (lane == 0) { csum[0] = wk; cmeta[0] = k - 1; }
             int seq = 1, nlive = 1;
             for (int j = 0; j < P.nmax - 1; ++j) {
-                // ---- pop the first minimum by (sum, seq)
-                float s;
-                int meta, slot;
-                if constexpr (O3) {
-                    s = csum; meta = cmeta;
+                // ---- pop the first minimum by (sum, seq): the smaller of the lane's own candidates, then the wave's
+                float s = 0.0f;
+                int meta = 0, slot;
+                {
+                    int ls = 0;
+#pragma unroll
+                    for (int i = 0; i < CPL; ++i) {
+                        const float s2 = O3 ? csum[i] : B.fsum[i * 64 + lane];
+                        const int m2 = O3 ? cmeta[i] : B.fmeta[i * 64 + lane], sl2 = O3 ? cslot[i] : i * 64 + lane;
+                        const bool lt = i == 0 || s2 < s || (s2 == s && m2 < meta);
+                        s = lt ? s2 : s; meta = lt ? m2 : meta; ls = lt ? sl2 : ls;
+                    }
                     const int wl = pbx_argmin(s, meta);
-                    slot = __builtin_amdgcn_readlane(cslot, wl);
-                } else {
-                    s = B.fsum[lane]; meta = B.fmeta[lane];
-                    slot = pbx_argmin(s, meta);
+                    slot = __builtin_amdgcn_readlane(ls, wl);
                 }
                 cmp += nlive == 1 ? 1 : 2;
                 const int last = meta & 0xFF;
                 int wt, p0, p1 = 0, p2 = 0;
                 if (slot == 0) { wt = 1; p0 = last; }
-                else if (slot < k) { wt = 2; p0 = slot - 1; p1 = last; }
+                else if (!O3 || slot < k) { wt = 2; p0 = slot - 1; p1 = last; }
                 else {
-                    const int t = slot - k;                // = b (b - 1) / 2 + a with a < b: lane b finds itself
-                    const int b = __builtin_ctzll(__ballot(lane >= 1 && lane * (lane - 1) / 2 <= t && t < lane * (lane + 1) / 2));
+                    const int t = slot - k;                // = b (b - 1) / 2 + a with a < b <= 125: candidate b finds itself
+                    const int bA = lane, bB = 64 + lane;
+                    const u64 hA = __ballot(bA >= 1 && bA * (bA - 1) / 2 <= t && t < bA * (bA + 1) / 2);
+                    const u64 hB = __ballot(bB * (bB - 1) / 2 <= t && t < bB * (bB + 1) / 2);
+                    const int b = hA ? __builtin_ctzll(hA) : 64 + __builtin_ctzll(hB);
                     wt = 3; p0 = t - b * (b - 1) / 2; p1 = b; p2 = last;
                 }
                 const int prev = wt == 2 ? p0 : p1;        // second largest index (wt > 1)
@@ -190,9 +214,13 @@ __global__ __launch_bounds__(64) void osdx_pb_kernel(const float *__restrict__ y
                     float ms = B.fsum[c0 * 64 + lane];
                     int mm = B.fmeta[c0 * 64 + lane];
                     const int wl = pbx_argmin(ms, mm);
-                    if (lane == c0) { csum = ms; cmeta = mm; cslot = c0 * 64 + wl; }
-                    if (has1 && ce != c0 && lane == ce && (esum < csum || (esum == csum && emeta < cmeta))) {
-                        csum = esum; cmeta = emeta; cslot = eslot;
+#pragma unroll
+                    for (int i = 0; i < CPL; ++i) {
+                        if ((c0 >> 6) == i && lane == (c0 & 63)) { csum[i] = ms; cmeta[i] = mm; cslot[i] = c0 * 64 + wl; }
+                        if (has1 && ce != c0 && (ce >> 6) == i && lane == (ce & 63) &&
+                            (esum < csum[i] || (esum == csum[i] && emeta < cmeta[i]))) {
+                            csum[i] = esum; cmeta[i] = emeta; cslot[i] = eslot;
+                        }
                     }
                 }
                 // ---- promising-probability rule (acquire_prob_promising :448-461)
@@ -204,19 +232,19 @@ __global__ __launch_bounds__(64) void osdx_pb_kernel(const float *__restrict__ y
                 bs = bs + w1 * (float)B.cdfA[beta];
                 bs = bs + w2 * (float)B.cdfH[beta];
                 if ((double)bs < Fr.p_t_pro) { stop = 1; ntep = j + 1; break; }
-                u64 D = S.d0 ^ L.P[p0], E = 1ull << p0;
-                if (wt > 1) { D ^= L.P[p1]; E |= 1ull << p1; }
-                if (wt > 2) { D ^= L.P[p2]; E |= 1ull << p2; }
+                u64 D = S.d0 ^ L.P[p0];
+                if (wt > 1) D ^= L.P[p1];
+                if (wt > 2) D ^= L.P[p2];
                 const float cost = tep_cost(L, rs, D);
                 ++suc1;
                 if (cost < best) {
-                    best = cost; bestD = D; bestE = E; bestidx = j + 1;
+                    best = cost; bestD = D; bw = wt; b0 = p0; b1 = p1; b2 = p2; bestidx = j + 1;
                     // success rule (acquire_p_e_suc :423-436)
                     const float ratio = (1.0f - w1) / w1;
                     float prod = 1.0f;
 #pragma unroll 4
                     for (int p = 0; p < m; ++p) {
-                        const float qp = B.q[64 + p];
+                        const float qp = B.q[128 + p];
                         prod = prod * (((D >> p) & 1) ? 2.0f * qp : 2.0f * (1.0f - qp));
                     }
                     const float p_suc = 1.0f / (1.0f + ratio / prod);
@@ -225,7 +253,8 @@ __global__ __launch_bounds__(64) void osdx_pb_kernel(const float *__restrict__ y
                 }
             }
         }
-        osdx_finish(L, S, bestE, bestD, f, words, lane, cw_out);
+        const auto flips = [&](int p) { return (bw > 0 && p == b0) || (bw > 1 && p == b1) || (bw > 2 && p == b2); };
+        osdw_finish(L, S, flips(lane), flips(64 + lane), bestD, f, words, lane, cw_out);
         store_results(f, lane, best, bestidx, ntep, metric_out, best_out, ntep_out);
         if (aux_out && lane == 0) { aux_out[f * 4] = cmp; aux_out[f * 4 + 1] = suc1; aux_out[f * 4 + 2] = suc2; aux_out[f * 4 + 3] = stop; }
         if (label) { seen += 1; wrong += cw_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }

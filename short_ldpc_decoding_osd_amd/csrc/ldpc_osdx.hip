@@ -3,8 +3,8 @@
 // ldpc_osdx.h), FS-OSD and the one-TEP primitive (ldpc_osdx_fs.h) and PB-OSD (ldpc_osdx_pb.h).  The PB tuning and routes and the
 // one-call pipeline stay with the (128,64) kernels of ldpc_osd.hip / ldpc_osd_pb.hip.
 // The G columns and the TEP tables are the context's OsdTables (ldpc_osd_tables.h), the set the (128,64) kernels read as well.
-// Validation, launches and the bodies of the entry points are those of ldpc_osd_family.h, shared with ldpc_osdw.hip; only PB-OSD,
-// which this family alone has, is launched here.
+// Validation, launches and the bodies of the entry points are those of ldpc_osd_family.h, shared with ldpc_osdw.hip; PB-OSD has a
+// kernel per family, so each family launches its own.
 #include <cmath>
 
 #include "ldpc_osdx_fs.h"

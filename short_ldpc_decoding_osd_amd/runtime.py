@@ -410,6 +410,18 @@ class Decoder:
         ``osdw_fs_search``; ``perm`` [F,128] u8 / ``parity`` [F,128] int64 / ``label_bits`` / ``counts`` as there."""
         return self._osd_decode("osdw", "fs_decode", y, C.byref(params), index, count, F, perm, parity, label_bits, counts, out)
 
+    def osdw_pb_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
+        """``osdx_pb_search`` for every code with n <= 128 and 1 <= n-k <= 64, on the results of ``osdw_front`` (perm [F,128]
+        u8, parity [F,128] int64).  ``params`` (``osd_params(order, _lib.OSD_PB, snr_db=..., aux=...)``, order 0..min(3, k))
+        and the returned dict as there."""
+        return self._osd_search("osdw", "pb_search", y, perm, parity, C.byref(params), index, count, F, out)
+
+    def osdw_pb_decode(self, y, params, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
+                       out=None):
+        """``osdx_pb_decode`` for every code with n <= 128 and 1 <= n-k <= 64: ``osdw_decode`` with the search of
+        ``osdw_pb_search``; ``perm`` [F,128] u8 / ``parity`` [F,128] int64 / ``label_bits`` / ``counts`` as there."""
+        return self._osd_decode("osdw", "pb_decode", y, C.byref(params), index, count, F, perm, parity, label_bits, counts, out)
+
     def osdw_tep_eval(self, y, perm, parity, mask, index=None, count=None):
         """``osdx_tep_eval`` for every code with n <= 128 and 1 <= n-k <= 64, on the results of ``osdw_front`` (parity [F,128]
         int64).  mask [F,2] int64: bit p of word 0 flips primed MRB position p, bit p of word 1 position 64 + p; bits at or
