@@ -502,7 +502,7 @@ int ldpc_osdw_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
                         int64_t *d_counts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
- * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H):
+ * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H; other shapes: ldpc_hosdx_* below):
  * DL_OSD_Testing_serial/ordered_statistics_decoding.py and nn_net.py: the per-frame sort / elimination /
  * candidate scan, the scan with the sliding-window early stop, and the bit-wise CNN.
  * ------------------------------------------------------------------------------------- */
@@ -575,6 +575,58 @@ int ldpc_hosd_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_me
                       int32_t group, const uint64_t *d_label_bits, int32_t *d_deep_limit, float *d_global_min,
                       float *d_truth, uint8_t *d_success, uint64_t *d_cw, float *d_metric, int32_t *d_best,
                       int32_t *d_teps_evaluated, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * H-form OSD primitives for short codes of any shape: ldpc_hosdx_*.
+ *
+ * Shapes served: every code with 1 <= k <= 64 and 1 <= m = n-k <= 64 (hence n <= 128) whose H, as given, has exactly n-k
+ * rows, i.e. full row rank: (96,48), (64,32), (128,64), ...  Everything else is refused with LDPC_E_UNSUPPORTED before any
+ * launch, and the message names the row count, n-k and (n,k); ldpc_hosdx_supported tells beforehand.
+ * The limit: an H with redundant rows (the array codes: (121,60) has 66 rows of rank 61) is not served.  The reference's
+ * full_gf2elim deletes zero rows as it meets them (ordered_statistics_decoding.py:239-242), so its column-exchange choice
+ * depends on the order of the redundant rows; serving that exactly needs columns of more than 64 rows.  That, with k > 64,
+ * is the follow-up (two-word columns); eliminating a row basis of H instead would be a different decoder.
+ *
+ * The contract is that of ldpc_hosd_front / _search / _sliding above, parameter for parameter, with 128 / 64 replaced:
+ *
+ * Sort.  Positions p < n are sorted by ascending |d_order_llr| ([F][n] f32); ties go to the lower index first.  Positions
+ * >= n do not exist: no padded lane ever sorts in front of a real one.
+ * Front end.  The columns of H are gathered in sorted order; the elimination follows the reference's rule (:222-257) on m
+ * rows -> [I_m | M]; updated positions 0..m-1 are the LRB in the order the elimination left them, m..n-1 the MRB, sorted
+ * ascending.
+ *   d_lri    [F][128] u8  : original bit at sorted position s < n; entries >= n are written as 0
+ *   d_uidx   [F][128] u8  : sorted position at updated position p < n; entries >= n are written as 0
+ *   d_M      [F][64] u64  : row r < m, bit j < k = updated_M[r][j]; rows >= m and bits >= k are written as 0.  As inputs
+ *                           the search calls ignore them (and the entries >= n of d_lri / d_uidx).
+ *   d_nswaps [F] i32 (nullable)
+ * Metric.  d_metric_llr is [F][n] f32.  The metric runs over the n updated positions as ONE sequence, LRB first, summed in
+ * bytes of eight positions (the last may be partial; a byte may straddle position m when m % 8 != 0), each byte ascending
+ * from 0.0f, the ceil(n/8) byte sums added ascending from byte 0: np_oracle.hosd_cost wherever n % 8 == 0, and the rule of
+ * the G-form families for the other shapes.
+ * Scan outputs.  d_cw and d_label_bits are [F][ceil(n/64)] u64 in original bit order.  d_block_min, d_block_arg, d_truth,
+ * d_metric, d_best, the sliding call's outputs, win, soft_margin, fcn_weights, group and the limit of 1024 TEP blocks are
+ * those of ldpc_hosd_search / ldpc_hosd_sliding, including which outputs are nullable.
+ * TEPs.  d_teps [ntep][4] u8 with positions < k, as ldpc_hosd_pattern_teps writes them for bounds within 0..k.  A position
+ * >= k is the caller's error: that frame's result is unspecified, but nothing is read or written outside the buffers.
+ * Validation and launch.  F == 0 is LDPC_OK.  A NULL in a required pointer is LDPC_E_ARG and the message names the entry
+ * point and the pointer; all validation happens before the first launch.  ldpc_ctx_create uploads the tables (the H
+ * columns as m-bit words); a call allocates nothing and synchronises nothing, so it can be captured in a graph.
+ * On (128,64) every output of every ldpc_hosdx_* call equals that of the ldpc_hosd_* call of the same name, bit for bit.
+ * ------------------------------------------------------------------------------------- */
+int ldpc_hosdx_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
+int ldpc_hosdx_front(ldpc_ctx *ctx, const float *d_order_llr, int64_t F, uint8_t *d_lri, uint8_t *d_uidx,
+                     uint64_t *d_M, int32_t *d_nswaps, void *stream);
+int ldpc_hosdx_search(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F,
+                      const uint8_t *d_lri, const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps,
+                      const int32_t *d_block_off, int32_t nblk, const uint64_t *d_label_bits, float *d_block_min,
+                      int32_t *d_block_arg, float *d_truth, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                      void *stream);
+int ldpc_hosdx_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F, const uint8_t *d_lri,
+                       const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps, const int32_t *d_block_off,
+                       int32_t nblk, int32_t win, double soft_margin, const float *fcn_weights, int32_t n_weights,
+                       int32_t group, const uint64_t *d_label_bits, int32_t *d_deep_limit, float *d_global_min,
+                       float *d_truth, uint8_t *d_success, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                       int32_t *d_teps_evaluated, void *stream);
 
 /* The bit-wise CNN of the DL-OSD stage, conv_bitwise.call (nn_net.py:174-197): for every frame f and
  * bit v, the sequence rows[f][0..L-1][v] (the retest layout of ldpc_nms_traj_rows, row 0 = channel

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Timing of the H-form OSD primitives (DL-OSD stage) on one GPU:
-ldpc_hosd_front and ldpc_hosd_search over a decoding path of 6-segment order patterns.
+front end, block scan and the scan with the sliding-window stop over a decoding path of 6-segment order patterns.  On
+(128,64) both families are timed on the same frames: the specialised kernels (ldpc_hosd_*) and the any-shape ones
+(ldpc_hosdx_*); any other code (--alist) runs the any-shape kernels.
 
-    python scripts/bench_hosd.py [--frames 32768] [--max-weight 2] [--snr 2.5]
+    python scripts/bench_hosd.py [--alist FILE] [--frames 32768] [--max-weight 2] [--snr 2.5] [--win 5]
 """
 import argparse
 import itertools
@@ -26,8 +28,10 @@ def main():
     ap.add_argument("--max-weight", type=int, default=2)
     ap.add_argument("--snr", type=float, default=2.5)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--alist", default=None, help="code definition (default: the CCSDS (128,64) code)")
+    ap.add_argument("--win", type=int, default=5, help="window of the sliding call")
     a = ap.parse_args()
-    code = Code()
+    code = Code(a.alist) if a.alist else Code()
     dec = Decoder(code)
     GL.set_map('code_parameters', code)
     GL.set_map('segment_num', 6)
@@ -51,14 +55,27 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.reps, r
 
-    t_front, front = timed(lambda: dec.hosd_front(yd))
-    t_search, out = timed(lambda: dec.hosd_search(yd, yd, front, teps, off, label_bits=lab))
-    hit = (out["metric"] == out["truth"]).float().mean().item()
-    print(json.dumps({"frames": a.frames, "blocks": len(blocks), "teps_per_frame": int(acc[-1]),
-                      "hosd_front_ms": round(t_front, 4), "hosd_search_ms": round(t_search, 4),
-                      "frames_per_s": round(a.frames / ((t_front + t_search) * 1e-3), 1),
-                      "teps_per_s": round(a.frames * int(acc[-1]) / (t_search * 1e-3), 1),
-                      "ml_hit_rate": round(hit, 5)}))
+    # the classifier of the sliding call: z1 - z0 = 0.35 k - 0.01 sum(window), stop at p1 > 0.9
+    d = a.win + 1
+    w2 = np.zeros((d, 2), np.float32)
+    w2[:a.win, 1], w2[a.win, 1] = -0.01, 0.35
+    fw = np.concatenate([np.eye(d, dtype=np.float32).ravel(), w2.ravel()])
+    res = {"code": [dec.n, dec.k], "frames": a.frames, "blocks": len(blocks), "teps_per_frame": int(acc[-1])}
+    fams = (["hosd"] if dec._hosd_fam() == "hosd" else []) + (["hosdx"] if dec.hosdx_supported else [])
+    if not fams:
+        raise SystemExit(f"bench_hosd: the H-form kernels do not serve this ({dec.n},{dec.k}) code")
+    for fam in fams:
+        t_front, front = timed(lambda: dec._hosd_front(fam, yd))
+        t_search, out = timed(lambda: dec._hosd_search(fam, yd, yd, front, teps, off, lab, True, True))
+        t_slide, sl = timed(lambda: dec._hosd_sliding(fam, yd, yd, front, teps, off, a.win, 0.9, fw, lab, 0, True))
+        hit = (out["metric"] == out["truth"]).float().mean().item()
+        res.update({f"{fam}_front_ms": round(t_front, 4), f"{fam}_search_ms": round(t_search, 4),
+                    f"{fam}_sliding_ms": round(t_slide, 4),
+                    f"{fam}_frames_per_s": round(a.frames / ((t_front + t_search) * 1e-3), 1),
+                    f"{fam}_teps_per_s": round(a.frames * int(acc[-1]) / (t_search * 1e-3), 1),
+                    f"{fam}_ml_hit_rate": round(hit, 5),
+                    f"{fam}_sliding_mean_depth": round(sl["deep_limit"].float().mean().item(), 3)})
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":

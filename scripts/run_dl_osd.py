@@ -3,10 +3,12 @@
 
     python scripts/run_dl_osd.py --data DIR --training DIR [--snr-lo 2.0 --snr-hi 3.0 --snr-num 6] [--batch 100]
                                  [--iters 12] [--type NMS-1] [--no-dia] [--convention-path] [--route device|host]
+                                 [--alist FILE]
 
 --data: the root holding <type>/<T>th/<snr>dB/ldpc-nonzero-retest.tfrecord (run_stages.py's output directory);
 --training: the training stage's directory (ckpts/ with the CNN and classifier checkpoints, log/ with the
-dist-error-pattern pickle).  The log goes to ./log/OSD-<order_sum>-<nn>.txt as in the reference.
+dist-error-pattern pickle); --alist: the code definition (default: the CCSDS (128,64) code; any code the H-form kernels
+serve, e.g. LDPC_N96_K48_P8_set0_dmin10.alist).  The log goes to ./log/OSD-<order_sum>-<nn>.txt as in the reference.
 """
 import argparse
 import os
@@ -30,7 +32,7 @@ def main():
     ap.add_argument("--snr-num", type=int, default=6)
     ap.add_argument("--batch", type=int, default=100)
     ap.add_argument("--iters", type=int, default=12)
-    ap.add_argument("--hfile", default="CCSDS_ldpc_n128_k64.alist")
+    ap.add_argument("--alist", "--hfile", dest="hfile", default="CCSDS_ldpc_n128_k64.alist")
     ap.add_argument("--type", default="NMS-1")
     ap.add_argument("--no-dia", action="store_true")
     ap.add_argument("--convention-path", action="store_true")
@@ -52,7 +54,7 @@ def main():
     for snr in snr_list:
         snr = round(float(snr), 2)
         f = os.path.join(a.data, a.type, f"{a.iters}th", f"{snr}dB", "ldpc-nonzero-retest.tfrecord")
-        ds = read_TFdata.data_handler(128, f, a.batch * L)
+        ds = read_TFdata.data_handler(GL.get_map('code_parameters').check_matrix_column, f, a.batch * L)
         FER, log_filename = NN_test.Testing_OSD(snr, ds, restore_list, indicator_list, prefix_list, DIA, route=a.route)
         FER_list.append((snr, FER))
     soft_margin = GL.get_map('soft_margin')

@@ -22,56 +22,7 @@ struct __attribute__((aligned(16))) FrontXLds {
     unsigned char perm[128]; // primed position -> original bit (zero beyond n)
 };
 
-// Gauss-Jordan over k pivot rows with the reference's pivot rule (full_gf2elim :231-266), columns in registers:
-//   C1 / C2 : sorted columns lane / k + lane, bit = PHYSICAL row (rows >= k do not exist: those bits are zero)
-//   rho     : lane l = logical row l -> physical row (row exchanges permute this map only)
-//   idx1/2  : the sorted position travelling with each column (:276-281)
-// Every choice is a select, never a branch on a lane-varying value, and nothing is indexed: the columns stay in
-// registers (no scratch).  Idle lanes hold zero columns, so they are never a pivot row nor an exchange partner.
-// Returns the number of column exchanges, or -1 for a rank-deficient matrix.
-__device__ __forceinline__ int gex_columns(u64 &C1, u64 &C2, int &rho, int &idx1, int &idx2, int k, int lane)
-{
-    int nsw = 0;
-    bool deficient = false;
-    const u64 rows = k >= 64 ? ~0ull : ((1ull << k) - 1ull);
-#pragma unroll 1
-    for (int i = 0; i < k; ++i) {
-        const u64 ge_i = rows & (~0ull << i);                  // logical rows (and first-half columns) >= i
-        u64 cj = readlane64(C1, i);
-        u64 bal = __ballot((cj >> rho) & 1ull) & ge_i;         // logical rows >= i with a 1 in column i
-        if (bal == 0) {
-            const int pri = __builtin_amdgcn_readlane(rho, i);
-            const u64 b1 = __ballot((C1 >> pri) & 1ull) & ge_i;
-            const u64 b2 = __ballot((C2 >> pri) & 1ull);
-            deficient |= (b1 | b2) == 0;                        // all-zero row: carry on with garbage, report at the end
-            const bool lo = b1 != 0;
-            const unsigned cl = lo ? __builtin_ctzll(b1) : (b2 ? __builtin_ctzll(b2) : 0);
-            const u64 cc1 = readlane64(C1, cl), cc2 = readlane64(C2, cl);
-            const int ic1 = __builtin_amdgcn_readlane(idx1, cl), ic2 = __builtin_amdgcn_readlane(idx2, cl);
-            const u64 cc = lo ? cc1 : cc2;
-            const int ic = lo ? ic1 : ic2;
-            const int ii = __builtin_amdgcn_readlane(idx1, i);
-            const bool hit = (unsigned)lane == cl;
-            C1 = (hit && lo) ? cj : C1;
-            idx1 = (hit && lo) ? ii : idx1;
-            C2 = (hit && !lo) ? cj : C2;
-            idx2 = (hit && !lo) ? ii : idx2;
-            C1 = (lane == i) ? cc : C1;
-            idx1 = (lane == i) ? ic : idx1;
-            ++nsw;
-            cj = cc;                                            // the exchanged-in column has its 1 in logical row i
-            bal = 1ull << i;
-        }
-        const int r = __builtin_ctzll(bal);
-        const int pr = __builtin_amdgcn_readlane(rho, r);
-        const int pi = __builtin_amdgcn_readlane(rho, i);
-        rho = (lane == i) ? pr : ((lane == r) ? pi : rho);      // exchange logical rows i and r (r == i: no change)
-        const u64 e = cj & ~(1ull << pr);                       // the pivot column without its pivot
-        C1 ^= ((C1 >> pr) & 1ull) ? e : 0ull;
-        C2 ^= ((C2 >> pr) & 1ull) ? e : 0ull;
-    }
-    return deficient ? -1 : nsw;
-}
+// (the elimination, gex_columns: ldpc_wave.h)
 
 // ---------------------------------------------------------------------------------------
 // front end: reliability sort, column gather, elimination, MRB / LRB bookkeeping

@@ -4,7 +4,8 @@ of nn_testing.py:65-82,120-148 and globalmap.py:57-76 that feed it.
 
 Everything per frame and per TEP -- ascending reliability sort, elimination of the permuted H, MRB
 bookkeeping, re-encoding and weighted-distance scan of every TEP block -- runs in the HIP kernels behind
-``ldpc_hosd_front`` / ``ldpc_hosd_search``.  ``sliding_osd`` evaluates ALL blocks of the decoding
+``ldpc_hosd_front`` / ``ldpc_hosd_search`` ((128,64)) or ``ldpc_hosdx_*`` (any shape with k, n-k <= 64 and an H of
+n-k rows; ``runtime.Decoder`` picks).  ``sliding_osd`` evaluates ALL blocks of the decoding
 path on the device (the reference evaluates them lazily) and then replays the reference's window
 loop on the block minima with a host callable ``fcn``, so decisions, window counts and complexity
 figures are the reference's.  ``sliding_osd_device`` runs the window loop inside the scan
@@ -99,7 +100,7 @@ class osd:   # noqa: N801  (name kept from the reference)
         """:25-28 -- ascending |inputs| argsort (ties: lower index first), computed on the device."""
         dec = _dec()
         x = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(np.asarray(inputs, dtype=np.float32)))).to(dec.device)
-        return dec.hosd_front(x)[0].cpu().numpy().astype(np.int64)
+        return dec.hosd_front(x)[0][:, :self.n_dims].cpu().numpy().astype(np.int64)
 
     def check_matrix_reorder(self, iteration_inputs, inputs, labels):
         """:30-41 -> (order_H_list [F,m,n], order_inputs, order_original_list, order_labels)."""
@@ -112,7 +113,7 @@ class osd:   # noqa: N801  (name kept from the reference)
         return order_H_list, take(inputs), order_original_list, take(labels)
 
     def full_gf2elim(self, M):
-        """:222-257 (the elimination rule shared by every stage; device for 64 x 128)."""
+        """:222-257 (the elimination rule shared by every stage; device for k x n = 64 x 128)."""
         return _full_gf2elim(M)
 
     def identify_mrb(self, order_H_list):
@@ -164,7 +165,9 @@ class osd:   # noqa: N801  (name kept from the reference)
         order = np.ones(self.n_dims, dtype=np.float32)
         order[self.m:] = np.where(np.asarray(initial_mrb).astype(bool), -1.0, 1.0)
         ident = torch.arange(128, dtype=torch.uint8, device=dec.device)[None].contiguous()
-        Mrows = np.packbits(np.ascontiguousarray(M_matrix, dtype=np.uint8), axis=1, bitorder="little").view(np.int64).reshape(1, 64)
+        Mpad = np.zeros((64, 64), dtype=np.uint8)                   # rows r < m, bits j < k of the [F,64] u64 layout
+        Mpad[:self.m, :self.k] = np.asarray(M_matrix, dtype=np.uint8)
+        Mrows = np.packbits(Mpad, axis=1, bitorder="little").view(np.int64).reshape(1, 64)
         teps = torch.from_numpy(_teps_from_matrix(error_pattern_matrix)).to(dec.device)
         off = torch.tensor([0, teps.shape[0]], dtype=torch.int32, device=dec.device)
         out = dec.hosd_search(torch.from_numpy(order[None]).to(dec.device), torch.from_numpy(metric[None]).to(dec.device),
@@ -193,7 +196,7 @@ class osd:   # noqa: N801  (name kept from the reference)
 
     def block_minima(self, input_list, inputs, labels, teps_list):
         """Device part of ``sliding_osd`` (:168-186 and every ``acquire_min``): -> dict of NumPy arrays
-        block_min [F,L], block_arg, truth [F], cw [F,2] (packed, original bit order), metric, best,
+        block_min [F,L], block_arg, truth [F], cw [F,ceil(n/64)] (packed, original bit order), metric, best,
         lri, uidx, nswaps."""
         dec = _dec()
         list_length = GL.get_map('num_iterations') + 1
@@ -269,5 +272,5 @@ class osd:   # noqa: N801  (name kept from the reference)
                 int(np.asarray(acc_block_size, dtype=np.int64)[deep].sum()))
 
     def unpack_codewords(self, cw):
-        """[F,2] packed words -> [F,128] 0/1 (original bit order)."""
+        """[F,ceil(n/64)] packed words -> [F,n] 0/1 (original bit order)."""
         return _unpack_rows(np.ascontiguousarray(cw)[:, None, :]).reshape(len(cw), -1)[:, :self.n_dims].astype(np.int64)

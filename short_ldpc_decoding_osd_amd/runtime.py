@@ -459,59 +459,92 @@ class Decoder:
         return self._osd_tep_eval("osdx", y, perm, parity, mask, index, count)
 
     # ------------------------------------------------------------------ H-form OSD (DL-OSD stage)
-    def hosd_front(self, order_llr):
-        """check_matrix_reorder + identify_mrb on [F,128] ordering values.  Returns (lri[F,128] u8,
-        uidx[F,128] u8, M[F,64] int64 rows of updated_M, nswaps[F] int32)."""
+    @property
+    def hosdx_supported(self):
+        """Whether the H-form calls serve this code beyond (128,64) (``ldpc_hosdx_*``: 1 <= k <= 64 and an H of exactly
+        n-k <= 64 rows)."""
+        return bool(self.L.ldpc_hosdx_supported(self._ctx))
+
+    def _hosd_fam(self):
+        """The entry-point family of the H-form calls: the (128,64) kernels for that shape, the any-shape ones otherwise
+        (which refuse what they do not serve)."""
+        return "hosd" if (self.n, self.k, self.m) == (128, 64, 64) else "hosdx"
+
+    def _hosd_front(self, fam, order_llr):
         self._chk(order_llr, torch.float32, (self.n,), "order_llr")
         F = order_llr.shape[0]
         lri = self.empty((F, 128), torch.uint8)
         uidx = self.empty((F, 128), torch.uint8)
         M = self.empty((F, 64), torch.int64)
         ns = self.empty((F,), torch.int32)
-        _lib.check(self.L.ldpc_hosd_front(self._ctx, _ptr(order_llr), F, _ptr(lri), _ptr(uidx), _ptr(M), _ptr(ns),
-                                          self._stream()), "ldpc_hosd_front")
+        self._osd_call(fam, "front", _ptr(order_llr), F, _ptr(lri), _ptr(uidx), _ptr(M), _ptr(ns))
         return lri, uidx, M, ns
 
-    def hosd_search(self, order_llr, metric_llr, front, teps, block_off, label_bits=None, want_arg=True, want_best=True):
-        """Block minima over the TEP blocks ``teps[block_off[b]:block_off[b+1]]`` (device tensors: [Nt,4] u8,
-        [nblk+1] int32).  Returns dict(block_min[F,nblk], block_arg, truth, cw, metric, best)."""
+    def _hosd_search(self, fam, order_llr, metric_llr, front, teps, block_off, label_bits, want_arg, want_best):
         lri, uidx, M, F, nblk = self._hosd_args(order_llr, metric_llr, front, teps, block_off)
         out = dict(block_min=self.empty((F, nblk), torch.float32),
                    block_arg=self.empty((F, nblk), torch.int32) if want_arg else None,
                    truth=self.empty((F,), torch.float32) if label_bits is not None else None,
-                   cw=self.empty((F, 2), torch.int64) if want_best else None,
+                   cw=self.empty((F, self.words), torch.int64) if want_best else None,
                    metric=self.empty((F,), torch.float32) if want_best else None,
                    best=self.empty((F,), torch.int32) if want_best else None)
-        _lib.check(self.L.ldpc_hosd_search(self._ctx, _ptr(order_llr), _ptr(metric_llr), F, _ptr(lri), _ptr(uidx), _ptr(M),
-                                           _ptr(teps), _ptr(block_off), nblk, _ptr(label_bits), _ptr(out["block_min"]),
-                                           _ptr(out["block_arg"]), _ptr(out["truth"]), _ptr(out["cw"]), _ptr(out["metric"]),
-                                           _ptr(out["best"]), self._stream()), "ldpc_hosd_search")
+        self._osd_call(fam, "search", _ptr(order_llr), _ptr(metric_llr), F, _ptr(lri), _ptr(uidx), _ptr(M), _ptr(teps),
+                       _ptr(block_off), nblk, _ptr(label_bits), _ptr(out["block_min"]), _ptr(out["block_arg"]),
+                       _ptr(out["truth"]), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]))
         return out
 
-    def hosd_sliding(self, order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights, label_bits=None,
-                     group=0, want_best=True):
-        """``hosd_search`` with the reference's sliding-window early stop: the blocks are scanned in groups of ``group``
-        consecutive blocks (0 = the library's default; results do not depend on it) and a frame stops when the classifier
-        (``fcn_weights``: dense1 [win+1,win+1] then dense2 [win+1,2], packed f32) fires with p1 > soft_margin.  Returns
-        dict(deep_limit[F] int32, global_min[F], truth[F], success[F] bool, cw[F,2], metric[F], best[F] (first minimum over
-        the blocks the reference evaluates), teps[F] int32 (TEPs scanned, speculative ones included))."""
+    def _hosd_sliding(self, fam, order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights, label_bits,
+                      group, want_best):
         lri, uidx, M, F, nblk = self._hosd_args(order_llr, metric_llr, front, teps, block_off)
         w = np.ascontiguousarray(np.asarray(fcn_weights, dtype=np.float32).reshape(-1))
         lab = label_bits is not None
         out = dict(deep_limit=self.empty((F,), torch.int32), global_min=self.empty((F,), torch.float32),
                    truth=self.empty((F,), torch.float32) if lab else None,
                    success=self.empty((F,), torch.bool) if lab else None,
-                   cw=self.empty((F, 2), torch.int64) if want_best else None,
+                   cw=self.empty((F, self.words), torch.int64) if want_best else None,
                    metric=self.empty((F,), torch.float32) if want_best else None,
                    best=self.empty((F,), torch.int32) if want_best else None,
                    teps=self.empty((F,), torch.int32))
-        _lib.check(self.L.ldpc_hosd_sliding(self._ctx, _ptr(order_llr), _ptr(metric_llr), F, _ptr(lri), _ptr(uidx), _ptr(M),
-                                            _ptr(teps), _ptr(block_off), nblk, int(win), float(soft_margin),
-                                            w.ctypes.data_as(C.POINTER(C.c_float)), w.size, int(group), _ptr(label_bits),
-                                            _ptr(out["deep_limit"]), _ptr(out["global_min"]), _ptr(out["truth"]),
-                                            _ptr(out["success"]), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]),
-                                            _ptr(out["teps"]), self._stream()), "ldpc_hosd_sliding")
+        self._osd_call(fam, "sliding", _ptr(order_llr), _ptr(metric_llr), F, _ptr(lri), _ptr(uidx), _ptr(M), _ptr(teps),
+                       _ptr(block_off), nblk, int(win), float(soft_margin), w.ctypes.data_as(C.POINTER(C.c_float)), w.size,
+                       int(group), _ptr(label_bits), _ptr(out["deep_limit"]), _ptr(out["global_min"]), _ptr(out["truth"]),
+                       _ptr(out["success"]), _ptr(out["cw"]), _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["teps"]))
         return out
+
+    def hosd_front(self, order_llr):
+        """check_matrix_reorder + identify_mrb on [F,n] ordering values.  Returns (lri[F,128] u8, uidx[F,128] u8 -- entries
+        at or beyond n are 0 --, M[F,64] int64 rows r < n-k of updated_M, bits j < k, 0 elsewhere, nswaps[F] int32).
+        (128,64) runs ``ldpc_hosd_front``, every other shape ``ldpc_hosdx_front``."""
+        return self._hosd_front(self._hosd_fam(), order_llr)
+
+    def hosdx_front(self, order_llr):
+        """``hosd_front`` through the any-shape kernels whatever the code (on (128,64) the same results)."""
+        return self._hosd_front("hosdx", order_llr)
+
+    def hosd_search(self, order_llr, metric_llr, front, teps, block_off, label_bits=None, want_arg=True, want_best=True):
+        """Block minima over the TEP blocks ``teps[block_off[b]:block_off[b+1]]`` (device tensors: [Nt,4] u8,
+        [nblk+1] int32).  Returns dict(block_min[F,nblk], block_arg, truth, cw[F,words], metric, best)."""
+        return self._hosd_search(self._hosd_fam(), order_llr, metric_llr, front, teps, block_off, label_bits, want_arg, want_best)
+
+    def hosdx_search(self, order_llr, metric_llr, front, teps, block_off, label_bits=None, want_arg=True, want_best=True):
+        """``hosd_search`` through the any-shape kernels whatever the code."""
+        return self._hosd_search("hosdx", order_llr, metric_llr, front, teps, block_off, label_bits, want_arg, want_best)
+
+    def hosd_sliding(self, order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights, label_bits=None,
+                     group=0, want_best=True):
+        """``hosd_search`` with the reference's sliding-window early stop: the blocks are scanned in groups of ``group``
+        consecutive blocks (0 = the library's default; results do not depend on it) and a frame stops when the classifier
+        (``fcn_weights``: dense1 [win+1,win+1] then dense2 [win+1,2], packed f32) fires with p1 > soft_margin.  Returns
+        dict(deep_limit[F] int32, global_min[F], truth[F], success[F] bool, cw[F,words], metric[F], best[F] (first minimum
+        over the blocks the reference evaluates), teps[F] int32 (TEPs scanned, speculative ones included))."""
+        return self._hosd_sliding(self._hosd_fam(), order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights,
+                                  label_bits, group, want_best)
+
+    def hosdx_sliding(self, order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights, label_bits=None,
+                      group=0, want_best=True):
+        """``hosd_sliding`` through the any-shape kernels whatever the code."""
+        return self._hosd_sliding("hosdx", order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights,
+                                  label_bits, group, want_best)
 
     def dia_cnn(self, rows, weights, out=None):
         """The bit-wise CNN (conv_bitwise) on retest rows ``[F, L, n]`` (or ``[F*L, n]`` with ``L`` taken from the
