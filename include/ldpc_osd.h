@@ -64,6 +64,7 @@ int ldpc_abi_version(void);
  * Code definition (host, one-time).
  * Replaces Ldpc_128_testing/fill_matrix_info.py: Code.load_code :70-129 (alist -> H),
  * Code.gf2elim :7-42 and Code.generator_matrix :44-69 (systematic G, H.G^T = 0 check).
+ * H may have redundant rows, as many as n or more: k = n - rank(H), and an H of rank n (no code) is LDPC_E_CODE.
  * ------------------------------------------------------------------------------------- */
 int ldpc_code_from_alist(const char *path, ldpc_code **out);
 int ldpc_code_from_dense(const int32_t *H /*[m][n] row-major 0/1*/, int32_t m, int32_t n, ldpc_code **out);
@@ -508,7 +509,7 @@ int ldpc_osdw_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
  * ------------------------------------------------------------------------------------- */
 
 /* Host: the TEPs of one order pattern, osd.error_pattern_gen (:81-98): pattern[s] flips inside
- * segment [bounds[s], bounds[s+1]) of the 64 MRB positions, for s = 0..nseg-1; itertools.product
+ * segment [bounds[s], bounds[s+1]) of the MRB positions (bounds within 0..128), for s = 0..nseg-1; itertools.product
  * over the segments (leftmost slowest) of itertools.combinations inside each.
  * teps: [count][4] u8 {p0, p1, p2, weight} (ascending positions, unused = 0), or NULL to get the
  * count.  Patterns of total weight > 3 are LDPC_E_UNSUPPORTED.                               */
@@ -584,8 +585,9 @@ int ldpc_hosd_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_me
  * launch, and the message names the row count, n-k and (n,k); ldpc_hosdx_supported tells beforehand.
  * The limit: an H with redundant rows (the array codes: (121,60) has 66 rows of rank 61) is not served.  The reference's
  * full_gf2elim deletes zero rows as it meets them (ordered_statistics_decoding.py:239-242), so its column-exchange choice
- * depends on the order of the redundant rows; serving that exactly needs columns of more than 64 rows.  That, with k > 64,
- * is the follow-up (two-word columns); eliminating a row basis of H instead would be a different decoder.
+ * depends on the order of the redundant rows; serving that exactly needs columns of more than 64 rows.  Those codes, and
+ * k > 64, are served by ldpc_hosdw_* below (two-word columns); eliminating a row basis of H instead would be a different
+ * decoder.
  *
  * The contract is that of ldpc_hosd_front / _search / _sliding above, parameter for parameter, with 128 / 64 replaced:
  *
@@ -622,6 +624,50 @@ int ldpc_hosdx_search(ldpc_ctx *ctx, const float *d_order_llr, const float *d_me
                       int32_t *d_block_arg, float *d_truth, uint64_t *d_cw, float *d_metric, int32_t *d_best,
                       void *stream);
 int ldpc_hosdx_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F, const uint8_t *d_lri,
+                       const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps, const int32_t *d_block_off,
+                       int32_t nblk, int32_t win, double soft_margin, const float *fcn_weights, int32_t n_weights,
+                       int32_t group, const uint64_t *d_label_bits, int32_t *d_deep_limit, float *d_global_min,
+                       float *d_truth, uint8_t *d_success, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                       int32_t *d_teps_evaluated, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * H-form OSD primitives for high-rate codes and for an H with redundant rows: ldpc_hosdw_*, a superset of ldpc_hosdx_* as
+ * ldpc_osdw_* is one of ldpc_osdx_*.
+ *
+ * Shapes served: n <= 128; H as given has R rows, 1 <= R <= 127, of rank m, 1 <= m <= 64; k = n - m, 1 <= k <= 127.  That is
+ * every code ldpc_hosdx_* serves, the array codes ((121,60): 66 rows of rank 61; (121,80): 44 rows of rank 41) and
+ * (87,70), (128,112), ...  Everything else (n > 128, a rank above 64, more than 127 rows) is refused with
+ * LDPC_E_UNSUPPORTED before any launch, and the message names the entry point, R, n-k and (n,k); ldpc_hosdw_supported tells
+ * beforehand.
+ *
+ * Redundant rows.  The elimination runs on all R rows of H as given and follows full_gf2elim (:222-257) to the letter: when
+ * column i has no 1 in the rows from i on and row i is all-zero, row i is deleted, the later rows move up, and step i is
+ * tried again; otherwise column i is exchanged with the first later column that has a 1 in row i.  Which exchanges happen
+ * therefore depends on the order of the rows of H, as it does in the reference.  d_nswaps counts the recorded column
+ * exchanges; deleted rows are not counted.
+ *
+ * The contract is that of ldpc_hosdx_front / _search / _sliding above, parameter for parameter (validation order, the
+ * messages that name the NULL pointer, F == 0, nullable outputs, the limit of 1024 TEP blocks; a call allocates nothing and
+ * synchronises nothing, so it can be captured in a graph), with m the RANK of H and these differences:
+ *   d_M  [F][128] u64 : entry r < m holds bits j = 0..63 of row r of updated_M, entry 64 + r bits j = 64..k-1; everything
+ *                       else (rows >= m, bits >= k) is written as 0, and ignored by the search calls as an input.  On a code
+ *                       that ldpc_hosdx_* serves the first 64 entries are its d_M and the rest are zero.
+ *   d_teps            : positions < k <= 127, as ldpc_hosd_pattern_teps writes them for bounds within 0..k; they are taken
+ *                       modulo 128, and a position >= k is the caller's error: that frame's result is unspecified, but
+ *                       nothing is read or written outside the buffers.
+ * ldpc_ctx_create uploads the H columns as two-word R-bit columns ([128][2] u64) when the code is in the family.
+ * Wherever ldpc_hosdx_* serves the code every other output of every ldpc_hosdw_* call equals that of the ldpc_hosdx_* call of
+ * the same name, bit for bit.
+ * ------------------------------------------------------------------------------------- */
+int ldpc_hosdw_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
+int ldpc_hosdw_front(ldpc_ctx *ctx, const float *d_order_llr, int64_t F, uint8_t *d_lri, uint8_t *d_uidx,
+                     uint64_t *d_M, int32_t *d_nswaps, void *stream);
+int ldpc_hosdw_search(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F,
+                      const uint8_t *d_lri, const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps,
+                      const int32_t *d_block_off, int32_t nblk, const uint64_t *d_label_bits, float *d_block_min,
+                      int32_t *d_block_arg, float *d_truth, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                      void *stream);
+int ldpc_hosdw_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F, const uint8_t *d_lri,
                        const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps, const int32_t *d_block_off,
                        int32_t nblk, int32_t win, double soft_margin, const float *fcn_weights, int32_t n_weights,
                        int32_t group, const uint64_t *d_label_bits, int32_t *d_deep_limit, float *d_global_min,

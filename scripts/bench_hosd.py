@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Timing of the H-form OSD primitives (DL-OSD stage) on one GPU:
-front end, block scan and the scan with the sliding-window stop over a decoding path of 6-segment order patterns.  On
-(128,64) both families are timed on the same frames: the specialised kernels (ldpc_hosd_*) and the any-shape ones
-(ldpc_hosdx_*); any other code (--alist) runs the any-shape kernels.
+front end, block scan and the scan with the sliding-window stop over a decoding path of 6-segment order patterns.  Every
+family that serves the code is timed on the same frames: the specialised kernels (ldpc_hosd_*) on (128,64), the any-shape
+ones (ldpc_hosdx_*) where k, n-k <= 64 and H has n-k rows, and the wide ones (ldpc_hosdw_*: k up to 127, redundant rows).
 
     python scripts/bench_hosd.py [--alist FILE] [--frames 32768] [--max-weight 2] [--snr 2.5] [--win 5]
 """
@@ -61,7 +61,8 @@ def main():
     w2[:a.win, 1], w2[a.win, 1] = -0.01, 0.35
     fw = np.concatenate([np.eye(d, dtype=np.float32).ravel(), w2.ravel()])
     res = {"code": [dec.n, dec.k], "frames": a.frames, "blocks": len(blocks), "teps_per_frame": int(acc[-1])}
-    fams = (["hosd"] if dec._hosd_fam() == "hosd" else []) + (["hosdx"] if dec.hosdx_supported else [])
+    fams = (["hosd"] if dec._hosd_fam() == "hosd" else []) + (["hosdx"] if dec.hosdx_supported else []) \
+        + (["hosdw"] if dec.hosdw_supported else [])
     if not fams:
         raise SystemExit(f"bench_hosd: the H-form kernels do not serve this ({dec.n},{dec.k}) code")
     for fam in fams:

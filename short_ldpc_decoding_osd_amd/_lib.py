@@ -26,7 +26,8 @@ SYMBOLS = (
     "ldpc_osdw_supported", "ldpc_osdw_front", "ldpc_osdw_search", "ldpc_osdw_decode",
     "ldpc_osdw_fs_search", "ldpc_osdw_fs_decode", "ldpc_osdw_tep_eval", "ldpc_osdw_pb_search", "ldpc_osdw_pb_decode",
     "ldpc_hosd_pattern_teps", "ldpc_hosd_front", "ldpc_hosd_search", "ldpc_hosd_sliding",
-    "ldpc_hosdx_supported", "ldpc_hosdx_front", "ldpc_hosdx_search", "ldpc_hosdx_sliding", "ldpc_dia_cnn",
+    "ldpc_hosdx_supported", "ldpc_hosdx_front", "ldpc_hosdx_search", "ldpc_hosdx_sliding",
+    "ldpc_hosdw_supported", "ldpc_hosdw_front", "ldpc_hosdw_search", "ldpc_hosdw_sliding", "ldpc_dia_cnn",
     "ldpc_pipeline_run", "ldpc_pipeline_timing",
 )
 
@@ -124,12 +125,13 @@ def load():
         "ldpc_hosd_sliding": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, C.c_double, C.POINTER(f32), i32, i32,
                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ldpc_hosdx_supported": (C.c_int, [vp]),
+        "ldpc_hosdw_supported": (C.c_int, [vp]),
         "ldpc_dia_cnn": (C.c_int, [vp, vp, i64, i32, C.POINTER(f32), i32, vp, vp]),
         "ldpc_pipeline_run": (C.c_int, [vp, C.POINTER(Pipeline), vp]),
         "ldpc_pipeline_timing": (C.c_int, [vp, i32, C.POINTER(f32)]),
     }
-    for op in ("front", "search", "sliding"):     # the any-shape H-form family: the signatures of ldpc_hosd_*
-        sig[f"ldpc_hosdx_{op}"] = sig[f"ldpc_hosd_{op}"]
+    for op in ("front", "search", "sliding"):     # the any-shape and the wide H-form family: the signatures of ldpc_hosd_*
+        sig[f"ldpc_hosdx_{op}"] = sig[f"ldpc_hosdw_{op}"] = sig[f"ldpc_hosd_{op}"]
     # the entry points that the any-shape and the high-rate family both have, under the same signatures
     for fam in ("osdx", "osdw"):
         sig.update({

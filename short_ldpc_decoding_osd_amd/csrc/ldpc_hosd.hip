@@ -1,5 +1,6 @@
 // H-form ordered-statistics primitives for the DL-OSD stage on gfx950 (MI355X): the (128,64) kernels here, the any-shape
-// kernels (ldpc_hosdx_*) in ldpc_hosdx.h.
+// kernels (ldpc_hosdx_*) in ldpc_hosdx.h, the ones for high-rate codes and an H with redundant rows (ldpc_hosdw_*) in
+// ldpc_hosdw.h.
 //
 // Reference (paths relative to LDPC_128/DL_OSD_Testing_serial/ of the reference):
 //   mag_input_gen / check_matrix_reorder   ordered_statistics_decoding.py:25-41
@@ -445,20 +446,30 @@ __global__ __launch_bounds__(256) void hosd_sliding_kernel(const float *__restri
 }  // namespace ldpc
 
 #include "ldpc_hosdx.h"   // the same three kernels for any shape with k, n - k <= 64
+#include "ldpc_hosdw.h"   // ... and for k up to 127 and an H of up to 127 rows of rank <= 64
 
 namespace ldpc {
 
-// The H columns as m-bit words for every shape the H-form kernels serve: 1 <= k <= 64, 1 <= m <= 64 and an H of exactly
-// n - k rows (full row rank as given).  ldpc_hosd_* take (128,64) alone, ldpc_hosdx_* all of them.
+// The H columns for every shape the H-form kernels serve.  ldpc_hosdw_* take n <= 128, an H of 1 <= R <= 127 rows as given
+// and rank 1 <= n - k <= 64 (two-word R-bit columns); of these ldpc_hosdx_* take 1 <= k <= 64 and an H of exactly n - k
+// rows (m-bit words), and ldpc_hosd_* (128,64) alone.
 int hosd_ctx_init(ldpc_ctx *ctx)
 {
     const ldpc_code &c = ctx->code;
-    ctx->hosd_ok = ctx->hosdx_ok = false;
-    if (c.k < 1 || c.k > 64 || c.m < 1 || c.m > 64 || c.m != c.n - c.k) return LDPC_OK;   // entry points will report UNSUPPORTED
-    std::vector<u64> cols(128, 0);
+    ctx->hosd_ok = ctx->hosdx_ok = ctx->hosdw_ok = false;
+    const int rank = c.n - c.k;
+    if (c.n > 128 || c.m < 1 || c.m > 127 || rank < 1 || rank > 64 || rank > c.m || c.k < 1 || c.k > 127)
+        return LDPC_OK;                                                                     // entry points will report UNSUPPORTED
+    std::vector<u64> wide(256, 0);
     for (int r = 0; r < c.m; ++r)
         for (int v = 0; v < c.n; ++v)
-            if (c.H[(size_t)r * c.n + v]) cols[v] |= 1ull << r;
+            if (c.H[(size_t)r * c.n + v]) wide[2 * v + (r >> 6)] |= 1ull << (r & 63);
+    LDPC_HIP(hipMalloc((void **)&ctx->d_HcolsW, sizeof(u64) * 256));
+    LDPC_HIP(hipMemcpy(ctx->d_HcolsW, wide.data(), sizeof(u64) * 256, hipMemcpyHostToDevice));
+    ctx->hosdw_ok = true;
+    if (c.k > 64 || c.m != rank) return LDPC_OK;
+    std::vector<u64> cols(128, 0);
+    for (int v = 0; v < c.n; ++v) cols[v] = wide[2 * v];
     LDPC_HIP(hipMalloc((void **)&ctx->d_Hcols, sizeof(u64) * 128));
     LDPC_HIP(hipMemcpy(ctx->d_Hcols, cols.data(), sizeof(u64) * 128, hipMemcpyHostToDevice));
     ctx->hosdx_ok = true;
@@ -469,7 +480,8 @@ int hosd_ctx_init(ldpc_ctx *ctx)
 void hosd_ctx_release(ldpc_ctx *ctx)
 {
     (void)hipFree(ctx->d_Hcols);
-    ctx->d_Hcols = nullptr;
+    (void)hipFree(ctx->d_HcolsW);
+    ctx->d_Hcols = ctx->d_HcolsW = nullptr;
 }
 
 static unsigned grid_for(int64_t F, int waves_per_block)
@@ -485,6 +497,15 @@ static int hosdx_check(const ldpc_ctx *ctx, const char *who)
     const ldpc_code &c = ctx->code;
     return fail(LDPC_E_UNSUPPORTED, "%s: H-form OSD kernels need 1 <= k <= 64 and an H of exactly n-k <= 64 rows; this H has %d rows, "
                 "n-k = %d, code (%d,%d)", who, c.m, c.n - c.k, c.n, c.k);
+}
+
+// The refusal of every ldpc_hosdw_* entry point for a code outside the family, LDPC_OK inside it.
+static int hosdw_check(const ldpc_ctx *ctx, const char *who)
+{
+    if (ctx->hosdw_ok) return LDPC_OK;
+    const ldpc_code &c = ctx->code;
+    return fail(LDPC_E_UNSUPPORTED, "%s: wide H-form OSD kernels need n <= 128, an H of 1 <= R <= 127 rows and 1 <= n-k <= 64; this H has "
+                "%d rows, n-k = %d, code (%d,%d)", who, c.m, c.n - c.k, c.n, c.k);
 }
 
 }  // namespace ldpc
@@ -649,6 +670,91 @@ int ldpc_hosdx_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_m
     for (int i = 0; i < 2 * d; ++i) w.w2[i] = fcn_weights[d * d + i];
     hipLaunchKernelGGL(hosdx_sliding_kernel, dim3(grid_for(F, 1)), dim3(256), 0, (hipStream_t)stream, d_order_llr, d_metric_llr,
                        (long long)F, ctx->code.n, ctx->code.m, d_lri, d_uidx, reinterpret_cast<const u64 *>(d_M),
+                       reinterpret_cast<const uchar4 *>(d_teps), d_block_off, (int)nblk, (int)win, soft_margin, w, (int)group,
+                       reinterpret_cast<const u64 *>(d_label_bits), d_deep_limit, d_global_min, d_truth, d_success,
+                       reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_teps_evaluated);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+int ldpc_hosdw_supported(const ldpc_ctx *ctx) { return ctx && ctx->hosdw_ok ? 1 : 0; }
+
+int ldpc_hosdw_front(ldpc_ctx *ctx, const float *d_order_llr, int64_t F, uint8_t *d_lri, uint8_t *d_uidx, uint64_t *d_M,
+                     int32_t *d_nswaps, void *stream)
+{
+    const char *who = "ldpc_hosdw_front";
+    if (!ctx || F < 0) return fail(LDPC_E_ARG, "%s: bad arguments (ctx %p, F %lld)", who, (void *)ctx, (long long)F);
+    if (F > 0)
+        if (int rc = first_null(who, {{"d_order_llr", d_order_llr}, {"d_lri", d_lri}, {"d_uidx", d_uidx}, {"d_M", d_M}})) return rc;
+    if (int rc = hosdw_check(ctx, who)) return rc;
+    if (F == 0) return LDPC_OK;
+    hipLaunchKernelGGL(hosdw_front_kernel, dim3(grid_for(F, 4)), dim3(256), 0, (hipStream_t)stream, d_order_llr, (long long)F,
+                       ctx->code.n, ctx->code.m, ctx->code.n - ctx->code.k, reinterpret_cast<const u64 *>(ctx->d_HcolsW), d_lri, d_uidx,
+                       reinterpret_cast<u64 *>(d_M), d_nswaps);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+int ldpc_hosdw_search(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F, const uint8_t *d_lri,
+                      const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps, const int32_t *d_block_off,
+                      int32_t nblk, const uint64_t *d_label_bits, float *d_block_min, int32_t *d_block_arg, float *d_truth,
+                      uint64_t *d_cw, float *d_metric, int32_t *d_best, void *stream)
+{
+    const char *who = "ldpc_hosdw_search";
+    if (!ctx || F < 0 || nblk < 0)
+        return fail(LDPC_E_ARG, "%s: bad arguments (ctx %p, F %lld, nblk %d)", who, (void *)ctx, (long long)F, (int)nblk);
+    if (F > 0) {
+        if (int rc = first_null(who, {{"d_order_llr", d_order_llr}, {"d_metric_llr", d_metric_llr}, {"d_lri", d_lri},
+                                      {"d_uidx", d_uidx}, {"d_M", d_M}, {"d_block_off", d_block_off}})) return rc;
+        if (nblk > 0)     // (the kernels read d_teps[0 .. d_block_off[nblk]), device data)
+            if (int rc = first_null(who, {{"d_teps", d_teps}, {"d_block_min", d_block_min}})) return rc;
+    }
+    if (d_truth && !d_label_bits) return fail(LDPC_E_ARG, "%s: d_truth needs d_label_bits", who);
+    if (int rc = hosdw_check(ctx, who)) return rc;
+    if (nblk > kHosdMaxBlocks) return fail(LDPC_E_UNSUPPORTED, "%s: %d TEP blocks, at most %d", who, nblk, kHosdMaxBlocks);
+    if (F == 0) return LDPC_OK;
+    // (the TEP table's size is device data: both forms are launched and one of them returns at once)
+    hipLaunchKernelGGL(hosdw_search_kernel<true>, dim3(grid_for(F, 1)), dim3(256), 0, (hipStream_t)stream, d_order_llr, d_metric_llr,
+                       (long long)F, ctx->code.n, ctx->code.n - ctx->code.k, d_lri, d_uidx, reinterpret_cast<const u64 *>(d_M),
+                       reinterpret_cast<const uchar4 *>(d_teps), d_block_off, (int)nblk,
+                       reinterpret_cast<const u64 *>(d_label_bits), d_block_min, d_block_arg, d_truth,
+                       reinterpret_cast<u64 *>(d_cw), d_metric, d_best);
+    hipLaunchKernelGGL(hosdw_search_kernel<false>, dim3(grid_for(F, 1)), dim3(256), 0, (hipStream_t)stream, d_order_llr, d_metric_llr,
+                       (long long)F, ctx->code.n, ctx->code.n - ctx->code.k, d_lri, d_uidx, reinterpret_cast<const u64 *>(d_M),
+                       reinterpret_cast<const uchar4 *>(d_teps), d_block_off, (int)nblk,
+                       reinterpret_cast<const u64 *>(d_label_bits), d_block_min, d_block_arg, d_truth,
+                       reinterpret_cast<u64 *>(d_cw), d_metric, d_best);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+int ldpc_hosdw_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F, const uint8_t *d_lri,
+                       const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps, const int32_t *d_block_off,
+                       int32_t nblk, int32_t win, double soft_margin, const float *fcn_weights, int32_t n_weights,
+                       int32_t group, const uint64_t *d_label_bits, int32_t *d_deep_limit, float *d_global_min,
+                       float *d_truth, uint8_t *d_success, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                       int32_t *d_teps_evaluated, void *stream)
+{
+    const char *who = "ldpc_hosdw_sliding";
+    if (!ctx || F < 0 || win < 1 || win > kSlideMaxWin || nblk < win || group < 0)
+        return fail(LDPC_E_ARG, "%s: bad arguments (ctx %p, F %lld, win %d, nblk %d, group %d)", who, (void *)ctx, (long long)F,
+                    (int)win, (int)nblk, (int)group);
+    if (int rc = first_null(who, {{"fcn_weights", fcn_weights}})) return rc;
+    if (F > 0)
+        if (int rc = first_null(who, {{"d_order_llr", d_order_llr}, {"d_metric_llr", d_metric_llr}, {"d_lri", d_lri},
+                                      {"d_uidx", d_uidx}, {"d_M", d_M}, {"d_teps", d_teps}, {"d_block_off", d_block_off}})) return rc;
+    const int d = win + 1;
+    if (n_weights != d * d + 2 * d)
+        return fail(LDPC_E_ARG, "%s: %d classifier weights, a window of %d takes %d", who, (int)n_weights, (int)win, d * d + 2 * d);
+    if ((d_truth || d_success) && !d_label_bits) return fail(LDPC_E_ARG, "%s: d_truth / d_success need d_label_bits", who);
+    if (int rc = hosdw_check(ctx, who)) return rc;
+    if (nblk > kHosdMaxBlocks) return fail(LDPC_E_UNSUPPORTED, "%s: %d TEP blocks, at most %d", who, nblk, kHosdMaxBlocks);
+    if (F == 0) return LDPC_OK;
+    SlideFcnArg w = {};
+    for (int i = 0; i < d * d; ++i) w.w1[i] = fcn_weights[i];
+    for (int i = 0; i < 2 * d; ++i) w.w2[i] = fcn_weights[d * d + i];
+    hipLaunchKernelGGL(hosdw_sliding_kernel, dim3(grid_for(F, 1)), dim3(256), 0, (hipStream_t)stream, d_order_llr, d_metric_llr,
+                       (long long)F, ctx->code.n, ctx->code.n - ctx->code.k, d_lri, d_uidx, reinterpret_cast<const u64 *>(d_M),
                        reinterpret_cast<const uchar4 *>(d_teps), d_block_off, (int)nblk, (int)win, soft_margin, w, (int)group,
                        reinterpret_cast<const u64 *>(d_label_bits), d_deep_limit, d_global_min, d_truth, d_success,
                        reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_teps_evaluated);

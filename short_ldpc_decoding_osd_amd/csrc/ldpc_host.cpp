@@ -342,7 +342,7 @@ int64_t hosd_pattern_teps(int nseg, const int32_t *bounds, const int32_t *patter
     int64_t total = 1;
     for (int s = 0; s < nseg; ++s) {
         const int len = bounds[s + 1] - bounds[s];
-        if (bounds[s] < 0 || bounds[s + 1] > 64 || len < 0 || pattern[s] < 0)
+        if (bounds[s] < 0 || bounds[s + 1] > 128 || len < 0 || pattern[s] < 0)
             return fail(LDPC_E_ARG, "hosd_pattern_teps: segment %d = [%d, %d), %d flips", s, bounds[s], bounds[s + 1], pattern[s]);
         weight += pattern[s];
         total *= pattern[s] > len ? 0 : binom(len, pattern[s]);   // combinations() of too many items is empty
@@ -385,7 +385,8 @@ int ldpc_abi_version(void) { return LDPC_OSD_ABI_VERSION; }
 
 int ldpc_code_from_dense(const int32_t *H, int32_t m, int32_t n, ldpc_code **out)
 {
-    if (!H || !out || m <= 0 || n <= m) return fail(LDPC_E_ARG, "ldpc_code_from_dense: bad arguments");
+    // (m >= n is an H with redundant rows; one of rank n is refused by build_code: no code)
+    if (!H || !out || m <= 0 || n <= 0) return fail(LDPC_E_ARG, "ldpc_code_from_dense: bad arguments");
     ldpc_code *c = new ldpc_code();
     c->m = m; c->n = n;
     c->H.resize((size_t)m * n);

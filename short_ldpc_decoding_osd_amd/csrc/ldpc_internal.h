@@ -75,11 +75,13 @@ struct ldpc_ctx {
     ldpc::OsdTables osd_tables;    // G columns and TEP tables of any shape with k, n-k <= 64: read by every OSD family
     ldpc::OsdwTables osdw_tables;  // two-word G columns and the TEP table of k <= 127 (n <= 128, n-k <= 64): the ldpc_osdw_* family
     uint64_t *d_Hcols = nullptr;   // [128] column v < n of H as an m-bit word (bit r = H[r][v]), zero beyond n; with hosdx_ok only
+    uint64_t *d_HcolsW = nullptr;  // [128][2] column v < n of H as given, rows 0..63 / 64..127, zero beyond n; with hosdw_ok only
     bool dpp_ror_up = true;        // probed: row_ror:n moves data towards higher lanes
     int dpp_wave_rol_dir = 0;      // probed: wave_rol:1 -- +1 lane j receives lane j-1, -1 lane j+1, 0 unusable
     bool osd_ok = false;
     bool hosd_ok = false;          // (128,64): ldpc_hosd_*
     bool hosdx_ok = false;         // 1 <= k <= 64, an H of exactly n - k <= 64 rows: ldpc_hosdx_*
+    bool hosdw_ok = false;         // n <= 128, an H of 1 <= R <= 127 rows and rank 1 <= n - k <= 64: ldpc_hosdw_*
     void *osd_state = nullptr;     // ldpc::OsdState ((128,64) constants; per-stream workspaces behind its mutex)
     hipEvent_t *timing = nullptr;  // [LDPC_TIMING_SLOTS][6] events of ldpc_pipeline_run, created with the context
     unsigned timing_recorded[LDPC_TIMING_SLOTS] = {};   // bit i: event i of the slot was recorded by the last run that used it

@@ -3,7 +3,8 @@
 ``Testing_OSD`` keeps the reference's arguments, console and log lines, log file name, return value and termination
 rule (stop after the batch on which the failure count reaches 'termination_threshold').  Per batch of retest rows the
 default route stays on the device: the bit-wise CNN (``ldpc_dia_cnn``), the front end (``ldpc_hosd_front``) and the
-block scan with the sliding-window early stop (``ldpc_hosd_sliding``) -- no per-frame host work.  ``route="host"`` is
+block scan with the sliding-window early stop (``ldpc_hosd_sliding``) -- no per-frame host work; beyond (128,64) the
+``ldpc_hosdx_*`` or ``ldpc_hosdw_*`` calls of the same names, as ``runtime.Decoder.hosd_stage`` picks.  ``route="host"`` is
 the cross-check: every block on the device, then the reference's window loop replayed on the host frame by frame with
 the NumPy classifier (``osd.sliding_osd``).
 

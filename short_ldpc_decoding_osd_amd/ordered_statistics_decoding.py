@@ -4,8 +4,9 @@ of nn_testing.py:65-82,120-148 and globalmap.py:57-76 that feed it.
 
 Everything per frame and per TEP -- ascending reliability sort, elimination of the permuted H, MRB
 bookkeeping, re-encoding and weighted-distance scan of every TEP block -- runs in the HIP kernels behind
-``ldpc_hosd_front`` / ``ldpc_hosd_search`` ((128,64)) or ``ldpc_hosdx_*`` (any shape with k, n-k <= 64 and an H of
-n-k rows; ``runtime.Decoder`` picks).  ``sliding_osd`` evaluates ALL blocks of the decoding
+``ldpc_hosd_front`` / ``ldpc_hosd_search`` ((128,64)), ``ldpc_hosdx_*`` (any shape with k, n-k <= 64 and an H of
+n-k rows) or ``ldpc_hosdw_*`` (k up to 127, or an H with redundant rows; ``runtime.Decoder.hosd_stage`` picks).
+``sliding_osd`` evaluates ALL blocks of the decoding
 path on the device (the reference evaluates them lazily) and then replays the reference's window
 loop on the block minima with a host callable ``fcn``, so decisions, window counts and complexity
 figures are the reference's.  ``sliding_osd_device`` runs the window loop inside the scan
@@ -100,7 +101,7 @@ class osd:   # noqa: N801  (name kept from the reference)
         """:25-28 -- ascending |inputs| argsort (ties: lower index first), computed on the device."""
         dec = _dec()
         x = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(np.asarray(inputs, dtype=np.float32)))).to(dec.device)
-        return dec.hosd_front(x)[0][:, :self.n_dims].cpu().numpy().astype(np.int64)
+        return dec.hosd_stage("front")(x)[0][:, :self.n_dims].cpu().numpy().astype(np.int64)
 
     def check_matrix_reorder(self, iteration_inputs, inputs, labels):
         """:30-41 -> (order_H_list [F,m,n], order_inputs, order_original_list, order_labels)."""
@@ -165,14 +166,15 @@ class osd:   # noqa: N801  (name kept from the reference)
         order = np.ones(self.n_dims, dtype=np.float32)
         order[self.m:] = np.where(np.asarray(initial_mrb).astype(bool), -1.0, 1.0)
         ident = torch.arange(128, dtype=torch.uint8, device=dec.device)[None].contiguous()
-        Mpad = np.zeros((64, 64), dtype=np.uint8)                   # rows r < m, bits j < k of the [F,64] u64 layout
+        wide = dec.hosd_stage_family() == "hosdw"                   # [F,128]: bits j < 64 at entry r, bits j >= 64 at 64 + r
+        Mpad = np.zeros((64, 128 if wide else 64), dtype=np.uint8)  # rows r < m, bits j < k of the [F,64] u64 layout
         Mpad[:self.m, :self.k] = np.asarray(M_matrix, dtype=np.uint8)
-        Mrows = np.packbits(Mpad, axis=1, bitorder="little").view(np.int64).reshape(1, 64)
+        Mrows = np.packbits(Mpad, axis=1, bitorder="little").view(np.int64).reshape(64, -1).T.reshape(1, -1)
         teps = torch.from_numpy(_teps_from_matrix(error_pattern_matrix)).to(dec.device)
         off = torch.tensor([0, teps.shape[0]], dtype=torch.int32, device=dec.device)
-        out = dec.hosd_search(torch.from_numpy(order[None]).to(dec.device), torch.from_numpy(metric[None]).to(dec.device),
-                              (ident, ident, torch.from_numpy(Mrows).to(dec.device)), teps, off, want_arg=False,
-                              want_best=False)
+        out = dec.hosd_stage("search")(torch.from_numpy(order[None]).to(dec.device), torch.from_numpy(metric[None]).to(dec.device),
+                                       (ident, ident, torch.from_numpy(np.ascontiguousarray(Mrows)).to(dec.device)), teps, off,
+                                       want_arg=False, want_best=False)
         return np.float32(out["block_min"].cpu().numpy()[0, 0])
 
     def sliding_window_ops(self, fcn, window, global_min, k):
@@ -204,8 +206,8 @@ class osd:   # noqa: N801  (name kept from the reference)
         metric = torch.from_numpy(np.ascontiguousarray(np.asarray(input_list, dtype=np.float32)[0::list_length])).to(dec.device)
         lab = dec.pack_bits(torch.from_numpy(np.ascontiguousarray(labels).astype(np.uint8)).to(dec.device))
         teps, off = self._device_blocks(dec, teps_list)
-        front = dec.hosd_front(order)
-        out = dec.hosd_search(order, metric, front, teps, off, label_bits=lab)
+        front = dec.hosd_stage("front")(order)
+        out = dec.hosd_stage("search")(order, metric, front, teps, off, label_bits=lab)
         res = {k: v.cpu().numpy() for k, v in out.items() if v is not None}
         res.update(lri=front[0].cpu().numpy(), uidx=front[1].cpu().numpy(), nswaps=front[3].cpu().numpy())
         return res
@@ -261,9 +263,9 @@ class osd:   # noqa: N801  (name kept from the reference)
         metric = torch.from_numpy(np.ascontiguousarray(np.asarray(input_list, dtype=np.float32)[0::list_length])).to(dec.device)
         lab = dec.pack_bits(torch.from_numpy(np.ascontiguousarray(labels).astype(np.uint8)).to(dec.device))
         teps, off = self._device_blocks(dec, teps_list)
-        front = dec.hosd_front(order)
-        out = dec.hosd_sliding(order, metric, front, teps, off, win, GL.get_map('soft_margin'), fcn.packed(), label_bits=lab,
-                               group=group)
+        front = dec.hosd_stage("front")(order)
+        out = dec.hosd_stage("sliding")(order, metric, front, teps, off, win, GL.get_map('soft_margin'), fcn.packed(),
+                                        label_bits=lab, group=group)
         res = {k: v.cpu().numpy() for k, v in out.items() if v is not None}
         deep = res["deep_limit"].astype(np.int64)
         self.last = res

@@ -465,23 +465,46 @@ class Decoder:
         n-k <= 64 rows)."""
         return bool(self.L.ldpc_hosdx_supported(self._ctx))
 
+    @property
+    def hosdw_supported(self):
+        """Whether the wide H-form calls serve this code (``ldpc_hosdw_*``: n <= 128, an H of at most 127 rows as given, of
+        rank n-k <= 64; k up to 127)."""
+        return bool(self.L.ldpc_hosdw_supported(self._ctx))
+
+    def hosd_stage_family(self):
+        """The H-form family the DL-OSD stage runs on this code: ``"hosd"`` on (128,64), ``"hosdx"`` where
+        ``hosdx_supported``, else ``"hosdw"`` (high rate, or an H with redundant rows; it refuses what it does not serve).
+        ``hosd_stage(op)`` is that family's ``front`` / ``search`` / ``sliding`` method."""
+        if (self.n, self.k, self.m) == (128, 64, 64):
+            return "hosd"
+        return "hosdx" if self.hosdx_supported else "hosdw"
+
+    def hosd_stage(self, op):
+        return getattr(self, f"{self.hosd_stage_family()}_{op}")
+
     def _hosd_fam(self):
         """The entry-point family of the H-form calls: the (128,64) kernels for that shape, the any-shape ones otherwise
         (which refuse what they do not serve)."""
         return "hosd" if (self.n, self.k, self.m) == (128, 64, 64) else "hosdx"
+
+    def _hosd_M(self, fam, M):
+        """The wide family reads 128 words of M per frame: front-end results of another family are refused here."""
+        if fam == "hosdw" and tuple(M.shape[1:]) != (128,):
+            raise ValueError(f"front: hosdw takes M [*, 128] (hosdw_front's), got {tuple(M.shape)}")
 
     def _hosd_front(self, fam, order_llr):
         self._chk(order_llr, torch.float32, (self.n,), "order_llr")
         F = order_llr.shape[0]
         lri = self.empty((F, 128), torch.uint8)
         uidx = self.empty((F, 128), torch.uint8)
-        M = self.empty((F, 64), torch.int64)
+        M = self.empty((F, 128 if fam == "hosdw" else 64), torch.int64)
         ns = self.empty((F,), torch.int32)
         self._osd_call(fam, "front", _ptr(order_llr), F, _ptr(lri), _ptr(uidx), _ptr(M), _ptr(ns))
         return lri, uidx, M, ns
 
     def _hosd_search(self, fam, order_llr, metric_llr, front, teps, block_off, label_bits, want_arg, want_best):
         lri, uidx, M, F, nblk = self._hosd_args(order_llr, metric_llr, front, teps, block_off)
+        self._hosd_M(fam, M)
         out = dict(block_min=self.empty((F, nblk), torch.float32),
                    block_arg=self.empty((F, nblk), torch.int32) if want_arg else None,
                    truth=self.empty((F,), torch.float32) if label_bits is not None else None,
@@ -496,6 +519,7 @@ class Decoder:
     def _hosd_sliding(self, fam, order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights, label_bits,
                       group, want_best):
         lri, uidx, M, F, nblk = self._hosd_args(order_llr, metric_llr, front, teps, block_off)
+        self._hosd_M(fam, M)
         w = np.ascontiguousarray(np.asarray(fcn_weights, dtype=np.float32).reshape(-1))
         lab = label_bits is not None
         out = dict(deep_limit=self.empty((F,), torch.int32), global_min=self.empty((F,), torch.float32),
@@ -544,6 +568,22 @@ class Decoder:
                       group=0, want_best=True):
         """``hosd_sliding`` through the any-shape kernels whatever the code."""
         return self._hosd_sliding("hosdx", order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights,
+                                  label_bits, group, want_best)
+
+    def hosdw_front(self, order_llr):
+        """``hosd_front`` through the wide kernels (``ldpc_hosdw_front``): M is [F,128] int64, entry r < n-k bits j = 0..63 of
+        row r of updated_M, entry 64 + r bits j = 64..k-1, 0 elsewhere; the elimination deletes redundant rows of H as the
+        reference does."""
+        return self._hosd_front("hosdw", order_llr)
+
+    def hosdw_search(self, order_llr, metric_llr, front, teps, block_off, label_bits=None, want_arg=True, want_best=True):
+        """``hosd_search`` through the wide kernels on ``hosdw_front``'s results (TEP positions < k <= 127)."""
+        return self._hosd_search("hosdw", order_llr, metric_llr, front, teps, block_off, label_bits, want_arg, want_best)
+
+    def hosdw_sliding(self, order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights, label_bits=None,
+                      group=0, want_best=True):
+        """``hosd_sliding`` through the wide kernels on ``hosdw_front``'s results."""
+        return self._hosd_sliding("hosdw", order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights,
                                   label_bits, group, want_best)
 
     def dia_cnn(self, rows, weights, out=None):
