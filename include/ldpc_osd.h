@@ -200,6 +200,58 @@ int ldpc_unpack_bits(ldpc_ctx *ctx, const uint64_t *d_words, int64_t B, void *d_
                      void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Frame generator: random message . G, BPSK, AWGN or block Rayleigh fading, and the packed labels, in one launch.
+ * Replaces Testing_data_gen_128/data_generating.py:13-51 and Training_data_gen_128/data_generating.py:41-81 on the
+ * device.  Frame i of a call is a pure function of (seed, frame0 + i, sigma, mean, flags, fade_len) and of the code:
+ * a set does not depend on how it is cut into calls, on the stream, or on the device count.
+ *
+ * The random stream (a contract: a change of any item below changes every frame).
+ *   Philox4x32-10 (Salmon et al., SC'11): multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85,
+ *   ten rounds.  Key = {seed low 32 bits, seed high 32 bits}; counter = {idx low, idx high, block, stream}; the four
+ *   output words of a call are x0..x3.  Known answers (counter, key -> output):
+ *     {0,0,0,0}, {0,0}                                             -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *     all ffffffff, all ffffffff                                   -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     {243f6a88,85a308d3,13198a2e,03707344}, {a4093822,299f31d0}   -> d16cfe09 94fdcceb 5001e420 24126ea1
+ *   stream 0, message bits: idx = global frame number frame0 + i (64 bit); block b yields message bits 128 b .. 128 b + 127,
+ *     word w of the block bits 32 w .., LSB first; bits at positions >= k are discarded.
+ *   stream 1, noise: idx = global frame number; block b yields the normals of columns 4 b .. 4 b + 3 (columns >= n are
+ *     discarded).  With ua(x) = float(x) 2^-32 + 2^-33 in f32, conversion and sum rounded to nearest, in (0, 1], and
+ *     tb(x) = float(x >> 8) 2^-24, exact, in [0, 1):
+ *       r = sqrtf(-2 logf(ua(x0))), z0 = r cospif(2 tb(x1)), z1 = r sinpif(2 tb(x1)); z2, z3 likewise from (x2, x3).
+ *     |z| <= 6.77; ua = 1 gives radius 0, never an infinity.
+ *   stream 2, fading amplitude: idx = fading-block number q = (frame n + column) / fade_len, an unsigned 64-bit division
+ *     on the global sample index (taken modulo 2^64); block 0 only; a = sqrtf(-logf(ua(x0))), a Rayleigh amplitude with
+ *     E[a^2] = 1 (in distribution the reference's |h| / sqrt(2), h complex normal, data_generating.py:30-37).  The
+ *     fading blocks run on through frame boundaries and calls; there is no zero tail (the reference's h stays 0 past its
+ *     last whole block).
+ *   per sample: v = mean + sigma z (AWGN) or v = mean a + sigma z (Rayleigh), each product and sum rounded on its own
+ *     (no FMA); y = bit ? -v : v, an exact negation.  The codeword is message . G mod 2 with the context's G.
+ * The results of logf / sqrtf / sincospif are the device library's: a CPU restatement agrees to a few ULP, not bit for bit.
+ *
+ *   d_y           [B][n] f32 channel values (nullable)
+ *   d_label_bits  [B][ceil(n/64)] u64 code bits, the layout of ldpc_pack_bits, pad bits zero (nullable)
+ * Each output is switched off on its own; the other does not change.  B = 0 returns LDPC_OK without a launch.
+ * With LDPC_GEN_F_ALL_ZEROS the labels are zero, stream 0 is not drawn and y = v: the values that the coded set negates.
+ * LDPC_E_ARG: p NULL, B < 0, frame0 < 0, sigma negative or not finite, fade_len < 1 with LDPC_GEN_F_RAYLEIGH, unknown
+ * flag bits.  One launch, no atomics, no workspace, nothing per stream: graph-capturable, and calls on different streams
+ * of one context may run concurrently.
+ * ------------------------------------------------------------------------------------- */
+#define LDPC_GEN_F_ALL_ZEROS (1u << 0) /* ALL_ZEROS_CODEWORD_TESTING / _TRAINING of the reference's globalmap */
+#define LDPC_GEN_F_RAYLEIGH  (1u << 1) /* Rayleigh_fading: block fading, fade_len samples per block          */
+
+typedef struct ldpc_gen_params {
+    uint64_t seed;      /* Philox key */
+    int64_t  frame0;    /* global number of the batch's first frame, >= 0 */
+    float    sigma;     /* noise standard deviation, >= 0 */
+    float    mean;      /* channel mean (1.0f for test sets; the blended mean for training sets) */
+    uint32_t flags;     /* LDPC_GEN_F_ALL_ZEROS | LDPC_GEN_F_RAYLEIGH */
+    int32_t  fade_len;  /* samples per fading block, >= 1 (the reference's int(16 * duration)); read only with _RAYLEIGH */
+} ldpc_gen_params;
+
+int ldpc_gen_frames(ldpc_ctx *ctx, const ldpc_gen_params *p, int64_t B, float *d_y /*[B][n], nullable*/,
+                    uint64_t *d_label_bits /*[B][ceil(n/64)], nullable*/, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * OSD (n = 128, k = 64 codes).  Frames are addressed as d_y[ d_index ? d_index[f] : f ].
  * If d_count is non-NULL the number of frames is min(*d_count, F) read ON THE DEVICE (so a
  * compaction can feed the OSD without a host round trip); F is then the capacity: a count above F is truncated to F,

@@ -28,6 +28,8 @@ per frame and stop shares, osdw_pb_kernel timed next to osdw_search_kernel of th
 on the same frames.  On a code both families serve, the conventional run also times the osdw kernels on the same frames in the
 same run, alternating with the osdx kernels, the --osd fs run times osdw_fs_kernel alternating with osdx_fs_kernel and the
 --osd pb run osdw_pb_kernel alternating with osdx_pb_kernel.
+--gen hip draws the frames with the library's counter-based generator (Decoder.gen_frames: frames 0 .. --frames - 1 of the set
+--seed, one launch) instead of the torch ops; the JSON line says which.
 One JSON line at the end."""
 import argparse
 import json
@@ -87,6 +89,7 @@ def main(argv=None):
     ap.add_argument("--alpha", type=float, default=0.669435, help="effective check normaliser of NMS-1")
     ap.add_argument("--order", type=int, default=2)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--gen", choices=("torch", "hip"), default="torch", help="frame source: torch ops, or the library's generator")
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
@@ -107,7 +110,7 @@ def main(argv=None):
     if not dec.osdx_supported and not dec.osdw_supported:
         raise SystemExit(f"osdx_fer: the OSD kernels serve n <= 128 and 1 <= n-k <= 64; this code is ({dec.n},{dec.k})")
     B = args.frames
-    y, labels = make_frames(dec, B, args.seed, args.snr)
+    y, labels = dec.gen_frames(B, seed=args.seed, snr_db=args.snr) if args.gen == "hip" else make_frames(dec, B, args.seed, args.snr)
     res = dec.nms(y, args.T, args.alpha)
     nms_counts = dec.eval_counts(res["hard"], labels, res["fail"])
     index, count = dec.compact(res["fail"])
@@ -137,7 +140,7 @@ def main(argv=None):
     print(f"({dec.n},{dec.k}) {args.snr} dB, {B} frames, NMS-{args.T}: FER {fer_nms:.3e} ({nc[1]} wrong, {nf} with a non-zero syndrome, "
           f"{nc[3]} undetected)", flush=True)
     result = dict(n=dec.n, k=dec.k, snr_db=args.snr, frames=B, T=args.T, order=args.order, failures=nf, fer_nms=fer_nms, fer_osd=fer_osd,
-                  kernels={})
+                  gen=args.gen, kernels={})
     if fs:
         table = sum(math.comb(dec.k, w) for w in range(args.order + 1))
         ntep = out["ntep"][:nf].to(torch.float64)

@@ -15,6 +15,9 @@ rank leaves on the same macro-batch), so a point overshoots by up to one macro-b
 small `--batch` with it; the JSON line says so (`stop_rule`).  By default every point decodes the requested number of frames.
 `--cpu-check` decodes a bounded sample of every point with the CPU port (oracle/ldpc_oracle.c, the checker) on rank 0 and
 prints `fer_vs_cpu` beside the GPU figures: +-5 % judged when both sides hold >= 1600 frame errors, else "not judged".
+`--gen hip` draws the frames with the library's counter-based generator (`Decoder.gen_frames`, one launch per batch) instead
+of the torch ops: the seed belongs to the SNR point and every batch starts at its first GLOBAL frame number, so a point
+decodes the same frames for every world size, `--batch` and `--streams`; the JSON line says `"gen": "hip"`.
 """
 import argparse
 import json
@@ -92,6 +95,9 @@ def main():
     ap.add_argument("--cpu-check", action="store_true",
                     help="rank 0: decode a bounded sample of every SNR point with the CPU port too and print fer_vs_cpu")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--cpu-check: CPU time budget per SNR point")
+    ap.add_argument("--gen", choices=("torch", "hip"), default="torch",
+                    help="frame source: torch ops with one torch generator per rank (the frames depend on the layout), or the "
+                         "library's counter-based generator (frame i of a point is the same for every layout)")
     ap.add_argument("--streams", type=int, default=3,
                     help="decode streams: consecutive batches rotate over them, so the tail of one batch's search kernels "
                          "(a few long searches on an emptying chip) overlaps the next batches' decoding (scratch is per stream; "
@@ -132,9 +138,13 @@ def main():
     with_osd = args.order is not None
     max_batches = -(-shard_range(args.frames, 0, world)[1] // args.batch)       # rank 0 owns the largest shard
 
-    def produce(B, snr, st):
+    def produce(B, snr, st, k):
+        """Batch k of this rank's share of the point."""
         with torch.cuda.stream(gen_stream):          # (no wait on the decode streams: the generator depends on nothing there)
-            y, lab = frames_on_device(dec, B, snr, gen)
+            if args.gen == "hip":
+                y, lab = dec.gen_frames(B, seed=20241020 + int(round(snr * 100)), snr_db=snr, frame0=lo + k * args.batch)
+            else:
+                y, lab = frames_on_device(dec, B, snr, gen)
             ev = torch.cuda.Event()
             ev.record(gen_stream)
         for t in (y, lab):
@@ -145,11 +155,11 @@ def main():
         snr = round(float(snr), 2)
         sizes = [min(args.batch, mine - k * args.batch) for k in range(max_batches) if mine - k * args.batch > 0]
         if args.resident:
-            ahead = [produce(b, snr, dstreams[k % len(dstreams)]) for k, b in enumerate(sizes)]
+            ahead = [produce(b, snr, dstreams[k % len(dstreams)], k) for k, b in enumerate(sizes)]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if not args.resident:
-            ahead = [produce(sizes[0], snr, dstreams[0])] if sizes else []
+            ahead = [produce(sizes[0], snr, dstreams[0], 0)] if sizes else []
         taken = [0]
         pool = {}      # (stream number, batch size) -> pipeline object of this point: its output buffers are made once, not per batch
 
@@ -158,7 +168,7 @@ def main():
             st = dstreams[taken[0] % len(dstreams)]
             taken[0] += 1
             if taken[0] < len(sizes) and not args.resident:
-                ahead.append(produce(sizes[taken[0]], snr, dstreams[taken[0] % len(dstreams)]))
+                ahead.append(produce(sizes[taken[0]], snr, dstreams[taken[0] % len(dstreams)], taken[0]))
             assert y.shape[0] == B
             with torch.cuda.stream(st):
                 st.wait_event(ev)
@@ -184,7 +194,7 @@ def main():
         if rank == 0:
             c = total.cpu().numpy()
             out = combine_fer(c)
-            out.update(snr_db=snr, osd=args.osd, order=args.order, alpha=alpha, n_gpus=world, macro_batches=ran,
+            out.update(snr_db=snr, osd=args.osd, order=args.order, alpha=alpha, n_gpus=world, macro_batches=ran, gen=args.gen,
                        stop_errors=args.stop_errors, **{"frames_per_s_resident_inputs" if args.resident else "frames_per_s_incl_generation": int(c[0]) / dt},
                        stop_rule=("end-to-end errors >= %d, checked per macro-batch of %d x %d frames" % (args.stop_errors, args.batch, world)) if args.stop_errors else "none: every frame decoded")
             if args.cpu_check:

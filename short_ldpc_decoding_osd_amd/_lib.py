@@ -20,6 +20,7 @@ SYMBOLS = (
     "ldpc_code_get_H", "ldpc_code_get_G", "ldpc_gf2elim_host", "ldpc_tep_table", "ldpc_tep_table_fs", "ldpc_crc32c",
     "ldpc_ctx_create", "ldpc_ctx_destroy", "ldpc_ctx_nms_kernel", "ldpc_ctx_get_pb_tuning", "ldpc_ctx_set_pb_tuning",
     "ldpc_nms_decode", "ldpc_nms_traj_rows", "ldpc_nms_train_grad", "ldpc_eval_counts", "ldpc_compact", "ldpc_pack_bits", "ldpc_unpack_bits",
+    "ldpc_gen_frames",
     "ldpc_osd_reserve", "ldpc_osd_reserve_stream", "ldpc_osd_release_stream", "ldpc_osd_index_errors", "ldpc_osd_ge", "ldpc_osd_front", "ldpc_osd_search", "ldpc_osd_decode", "ldpc_osd_tep_eval", "ldpc_osd_counts",
     "ldpc_osdx_supported", "ldpc_osdx_front", "ldpc_osdx_search", "ldpc_osdx_decode",
     "ldpc_osdx_fs_search", "ldpc_osdx_fs_decode", "ldpc_osdx_tep_eval", "ldpc_osdx_pb_search", "ldpc_osdx_pb_decode",
@@ -41,6 +42,16 @@ class OsdParams(C.Structure):
     _fields_ = [("order", C.c_int32), ("algo", C.c_int32), ("snr_db", C.c_float), ("fs_beta", C.c_float),
                 ("fs_tau_e", C.c_float), ("fs_tau_psc", C.c_float), ("fs_reference_quirk", C.c_int32),
                 ("flags", C.c_int32), ("d_aux", C.c_void_p), ("y_frames", C.c_int64)]
+
+
+# ldpc_gen_params.flags (LDPC_GEN_F_*)
+GEN_F_ALL_ZEROS, GEN_F_RAYLEIGH = 1, 2
+
+
+class GenParams(C.Structure):
+    """ldpc_gen_params of include/ldpc_osd.h (the frame generator's seed, first frame number and channel)."""
+    _fields_ = [("seed", C.c_uint64), ("frame0", C.c_int64), ("sigma", C.c_float), ("mean", C.c_float),
+                ("flags", C.c_uint32), ("fade_len", C.c_int32)]
 
 
 class PbTuning(C.Structure):
@@ -109,6 +120,7 @@ def load():
         "ldpc_compact": (C.c_int, [vp, vp, i64, vp, vp, vp]),
         "ldpc_pack_bits": (C.c_int, [vp, vp, i32, i64, vp, vp]),
         "ldpc_unpack_bits": (C.c_int, [vp, vp, i64, vp, i32, vp]),
+        "ldpc_gen_frames": (C.c_int, [vp, C.POINTER(GenParams), i64, vp, vp, vp]),
         "ldpc_osd_reserve": (C.c_int, [vp, i64]),
         "ldpc_osd_reserve_stream": (C.c_int, [vp, i64, C.POINTER(OsdParams), vp]),
         "ldpc_osd_release_stream": (C.c_int, [vp, vp]),

@@ -81,6 +81,7 @@ int ldpc_ctx_create(const ldpc_code *code, int32_t device, ldpc_ctx **out)
         if (rc) break;
         if ((rc = osd_ctx_init(ctx))) break;
         if ((rc = hosd_ctx_init(ctx))) break;
+        if ((rc = gen_ctx_init(ctx))) break;
     } while (0);
     (void)hipSetDevice(prev);
     if (rc) { ldpc_ctx_destroy(ctx); return rc; }
@@ -93,6 +94,7 @@ void ldpc_ctx_destroy(ldpc_ctx *ctx)
     if (!ctx) return;
     osd_ctx_release(ctx);
     hosd_ctx_release(ctx);
+    gen_ctx_release(ctx);
     (void)hipFree(ctx->osd_tables.d_Gcols); (void)hipFree(ctx->osd_tables.d_tep); (void)hipFree(ctx->osd_tables.d_tep_fs);
     (void)hipFree(ctx->osd_tables.d_pb);
     (void)hipFree(ctx->osdw_tables.d_Gcols);
@@ -112,6 +114,22 @@ int ldpc_ctx_nms_kernel(const ldpc_ctx *ctx)
 {
     if (!ctx) return fail(LDPC_E_ARG, "ldpc_ctx_nms_kernel: null ctx");
     return ctx->code.qc16_ccsds ? LDPC_NMS_QC16 : LDPC_NMS_GENERIC;
+}
+
+int ldpc_gen_frames(ldpc_ctx *ctx, const ldpc_gen_params *p, int64_t B, float *d_y, uint64_t *d_label_bits, void *stream)
+{
+    if (!ctx) return fail(LDPC_E_ARG, "ldpc_gen_frames: ctx is NULL");
+    if (!p) return fail(LDPC_E_ARG, "ldpc_gen_frames: p is NULL");
+    if (B < 0) return fail(LDPC_E_ARG, "ldpc_gen_frames: B = %lld is negative", (long long)B);
+    if (p->frame0 < 0) return fail(LDPC_E_ARG, "ldpc_gen_frames: frame0 = %lld is negative", (long long)p->frame0);
+    if (!(p->sigma >= 0.0f) || !(p->sigma <= 3.402823466e+38f))   // (NaN fails both comparisons)
+        return fail(LDPC_E_ARG, "ldpc_gen_frames: sigma = %g is not a finite value >= 0", (double)p->sigma);
+    if (p->flags & ~(uint32_t)(LDPC_GEN_F_ALL_ZEROS | LDPC_GEN_F_RAYLEIGH))
+        return fail(LDPC_E_ARG, "ldpc_gen_frames: unknown flag bits 0x%x", p->flags & ~(uint32_t)(LDPC_GEN_F_ALL_ZEROS | LDPC_GEN_F_RAYLEIGH));
+    if ((p->flags & LDPC_GEN_F_RAYLEIGH) && p->fade_len < 1)
+        return fail(LDPC_E_ARG, "ldpc_gen_frames: fade_len = %d with LDPC_GEN_F_RAYLEIGH (want >= 1)", p->fade_len);
+    if (B == 0 || (!d_y && !d_label_bits)) return LDPC_OK;
+    return launch_gen(ctx, p, B, d_y, d_label_bits, (hipStream_t)stream);
 }
 
 int ldpc_nms_decode(ldpc_ctx *ctx, const float *d_llr, int64_t B, int32_t T, const float *alpha, float w_in,

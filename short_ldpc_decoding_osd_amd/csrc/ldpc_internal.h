@@ -75,6 +75,7 @@ struct ldpc_ctx {
     ldpc::OsdTables osd_tables;    // G columns and TEP tables of any shape with k, n-k <= 64: read by every OSD family
     ldpc::OsdwTables osdw_tables;  // two-word G columns and the TEP table of k <= 127 (n <= 128, n-k <= 64): the ldpc_osdw_* family
     uint64_t *d_Hcols = nullptr;   // [128] column v < n of H as an m-bit word (bit r = H[r][v]), zero beyond n; with hosdx_ok only
+    uint32_t *d_gen_G = nullptr;   // [ceil(k/32)][4][ceil(n/4)] G's columns packed over k, transposed for ldpc_gen_frames (ldpc_gen.hip)
     uint64_t *d_HcolsW = nullptr;  // [128][2] column v < n of H as given, rows 0..63 / 64..127, zero beyond n; with hosdw_ok only
     bool dpp_ror_up = true;        // probed: row_ror:n moves data towards higher lanes
     int dpp_wave_rol_dir = 0;      // probed: wave_rol:1 -- +1 lane j receives lane j-1, -1 lane j+1, 0 unusable
@@ -133,5 +134,9 @@ int osd_launch(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const in
                const uint64_t *d_label, int64_t *d_counts, hipStream_t s, bool *counted);
 int eval_and_compact(ldpc_ctx *ctx, const uint64_t *d_hard, const uint64_t *d_label, const uint8_t *d_fail, int64_t B,
                      int64_t *d_counts, int32_t *d_index, int32_t *d_count, hipStream_t st);
+// frame generator (ldpc_gen.hip): the context's packed G, and the launch on params that ldpc_gen_frames validated (B > 0)
+int gen_ctx_init(ldpc_ctx *ctx);
+void gen_ctx_release(ldpc_ctx *ctx);
+int launch_gen(ldpc_ctx *ctx, const ldpc_gen_params *p, int64_t B, float *d_y, uint64_t *d_label_bits, hipStream_t st);
 
 }  // namespace ldpc

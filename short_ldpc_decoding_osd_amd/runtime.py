@@ -250,6 +250,34 @@ class Decoder:
                    "ldpc_unpack_bits")
         return bits
 
+    # ------------------------------------------------------------------ frame generator
+    def gen_sigma(self, snr_db):
+        """sigma = sqrt(1 / (2 (k/n) 10^(snr/10))), as the reference computes it (data_generating.py:17)."""
+        return float(np.sqrt(1. / (2 * (float(self.k) / float(self.n)) * 10 ** (snr_db / 10))))
+
+    def gen_frames(self, B, *, seed, snr_db=None, sigma=None, mean=1.0, frame0=0, all_zeros=False, rayleigh=False, fade_len=16,
+                   want_y=True, want_labels=True, out=None):
+        """Frames ``frame0 .. frame0 + B - 1`` of the set ``seed`` (ldpc_gen_frames): random message . G, BPSK 0 -> +1,
+        ``mean + sigma z`` (AWGN) or ``mean a + sigma z`` (``rayleigh``: one amplitude per ``fade_len`` consecutive samples
+        of the set), in one launch.  Exactly one of ``snr_db`` (-> ``gen_sigma``) and ``sigma`` is given.  Frame i is a pure
+        function of (seed, frame0 + i, the channel parameters): any split of a set into calls gives the same bits.
+        Returns ``(y [B, n] f32, label_bits [B, words] int64)``; an output that is switched off is None and its buffer in
+        ``out`` (dict: ``y``, ``label_bits``), if any, is not touched.  ``all_zeros``: zero labels, ``y`` unsigned."""
+        if (snr_db is None) == (sigma is None):
+            raise ValueError("gen_frames: give exactly one of snr_db and sigma")
+        sigma = self.gen_sigma(snr_db) if sigma is None else float(sigma)
+        B = int(B)
+        out = self._outputs(out, {"y": ((B, self.n), torch.float32, want_y), "label_bits": ((B, self.words), torch.int64, want_labels)})
+        y = self._chk(out["y"], torch.float32, (self.n,), "y") if want_y else None
+        lab = self._chk(out["label_bits"], torch.int64, (self.words,), "label_bits") if want_labels else None
+        for t, name in ((y, "y"), (lab, "label_bits")):
+            if t is not None and t.shape[0] < B:
+                raise ValueError(f"gen_frames: {name} holds {t.shape[0]} frames, {B} asked for")
+        p = _lib.GenParams(int(seed) & 0xFFFFFFFFFFFFFFFF, int(frame0), sigma, float(mean),
+                           (_lib.GEN_F_ALL_ZEROS if all_zeros else 0) | (_lib.GEN_F_RAYLEIGH if rayleigh else 0), int(fade_len))
+        _lib.check(self.L.ldpc_gen_frames(self._ctx, C.byref(p), B, _ptr(y), _ptr(lab), self._stream()), "ldpc_gen_frames")
+        return y, lab
+
     # ------------------------------------------------------------------ OSD
     def osd_reserve(self, max_frames):
         """Pre-size the OSD workspace (needed before capturing decode calls into a graph)."""
