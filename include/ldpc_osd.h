@@ -742,6 +742,34 @@ int ldpc_dia_cnn(ldpc_ctx *ctx, const float *d_rows, int64_t F, int32_t L, const
                  float *d_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Training step of the bit-wise CNN: the loss of the DL-OSD training stage and its gradient with respect to EVERY
+ * weight, in one call.  Replaces, relative to LDPC_128/DL_Training_serial/ of the reference, conv_bitwise.call
+ * nn_net.py:173-196 under the tf.GradientTape of nn_training.py:390-398 with calculate_loss :293-297:
+ *   loss = sum_{f,v} max(z,0) - z y + log1p(exp(-|z|)),   z = -out[f][v],  y = label bit of (f, v)
+ * (tf.nn.sigmoid_cross_entropy_with_logits(logits = -out, labels = bit), summed over frames and bits).
+ * The forward pass is ldpc_dia_cnn's, same device code and float order: d_out equals its output bit for bit.
+ * The network has no activation, so out = bias + sum_r E[r] x[r] with an effective filter E of the weights alone; with
+ * g = dloss/dout = y - sigmoid(-out) (computed as y ? sigmoid(out) : -sigmoid(-out), each 1 / (1 + exp(-t)), f32)
+ *   dloss/dtheta = sum_r dE[r]/dtheta m[r],  m[r] = sum_{f,v} g[f][v] rows[f][r][v];   dloss/dbias = sum_{f,v} g[f][v]
+ * The products g x are f32 (one rounding each), every sum is f64, and the back-propagation at m runs in f64.  These are
+ * the gradient rules of the ops the reference uses; they are not pinned against TensorFlow, which is not available to
+ * check them, as for ldpc_nms_train_grad.
+ *   d_rows        [F][L][n] f32, weights / n_weights: as ldpc_dia_cnn (7 <= L <= 64, n_weights = 145 + 2(L-6))
+ *   d_label_bits  [F][ceil(n/64)] u64 packed code bits (the layout of ldpc_eval_counts)
+ * Outputs, any subset of them NULL:
+ *   d_out         [F][n] f32 refined values
+ *   d_loss_sum    [1] f64
+ *   d_grad_sum    [n_weights] f64, in the packed order of the weights
+ * No atomics: per-workgroup partial sums and a fixed tree whose shape depends on (F, n, L) alone, so repeated calls give
+ * the same bits on any stream.  Scratch for the partials (at most 2 MiB) is allocated and freed in stream order; the
+ * call makes no host-device copy and does not synchronise.  F = 0 writes nothing.  Refusals (LDPC_E_ARG, before any
+ * launch) name the call and the offending argument.
+ * ------------------------------------------------------------------------------------- */
+int ldpc_dia_cnn_grad(ldpc_ctx *ctx, const float *d_rows, const uint64_t *d_label_bits, int64_t F, int32_t L,
+                      const float *weights, int32_t n_weights, float *d_out, double *d_loss_sum, double *d_grad_sum,
+                      void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * One batch through the whole path with a single host call: the body of the reference drivers'
  * per-batch loops (ldpc_128_testing.py:117-131 then pb_testing.py / fs_testing.py per failed frame):
  *   NMS-T -> error counters -> failed-frame compaction -> OSD (front end + search) on the failures

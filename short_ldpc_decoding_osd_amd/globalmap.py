@@ -5,8 +5,9 @@ FS_OSD/globalmap.py:28-50).  The decoders read the same keys the reference reads
 'termination_num_threshlod' (sic), 'd_min', 'tau_psc', 'pb_osd', 'fs_osd', 'convention_osd',
 'miracle_view'; the DL-OSD stage's keys (DL_OSD_Testing_serial/globalmap.py:28-54, ``stage="DL"``):
 'convention_path', 'termination_threshold', 'threshold_sum', 'training_snr', 'segment_num',
-'soft_margin', 'decoding_length', 'sliding_win_width'.  Unlike the reference a missing key raises
-KeyError instead of printing.
+'soft_margin', 'decoding_length', 'sliding_win_width'; the DL-OSD training stage's settings and directories
+(DL_Training_serial/globalmap.py:28-64, :87-106, :140-159) are the ``dl_training_*`` functions.  Unlike the reference a
+missing key raises KeyError instead of printing.
 """
 from __future__ import annotations
 
@@ -107,6 +108,76 @@ def set_predict_model(DIA):   # noqa: N803
 def pattern_log_dir():
     """Directory of ``dist-error-pattern-<nn>.pkl`` (nn_testing.py:96-99: the 2.7-2.7 dB statistics)."""
     return _training_root() + 'log/' + get_map('selected_decoder_type') + '/2.7-2.7dB/'
+
+
+# ---- DL-OSD training stage (DL_Training_serial/globalmap.py).  It writes under 'dl_training_dir' too (default: the working
+# directory, as the reference does), so a run rooted at R is what the test-stage functions above find with
+# dl_training_dir = R and training_snr = snr_lo = snr_hi.
+def dl_training_setting(argv):
+    """Positional settings of the DL-OSD training stage: ``prog snr_lo snr_hi unit_batch T Hfile type`` (:28-64) with the
+    reference's defaults."""
+    from .fill_matrix_info import Code
+
+    set_map('snr_lo', float(argv[1]))
+    set_map('snr_hi', float(argv[2]))
+    set_map('unit_batch_size', int(argv[3]))
+    set_map('num_iterations', int(argv[4]))
+    set_map('H_filename', argv[5])
+    set_map('selected_decoder_type', argv[6])
+    set_map('ALL_ZEROS_CODEWORD_TRAINING', False)
+    set_map('epochs', 100)
+    set_map('initial_learning_rate', 0.001)
+    set_map('decay_rate', 0.95)
+    set_map('decay_step', 500)
+    set_map('termination_step', 2000)
+    set_map('termination_prediction_step', 2000)
+    set_map('threshold_sum', 3)
+    set_map('code_parameters', Code(get_map('H_filename')))
+    set_map('convention_path', False)
+    set_map('print_interval', 100)
+    set_map('record_interval', 100)
+    set_map('nn_train', True)
+    set_map('segment_num', 6)
+    set_map('reliability_enhance', False)
+    set_map('prediction_order_pattern', True)
+    set_map('regulation_weight', 10.)
+    set_map('decoding_length', 30)
+    set_map('regnerate_training_samples', True)
+    set_map('sliding_win_width', 5)
+
+
+def _dl_stage_root():
+    return os.path.join(get_map('dl_training_dir', './'), '')
+
+
+def _dl_stage_snr_info():
+    return str(round(get_map('snr_lo'), 2)) + '-' + str(round(get_map('snr_hi'), 2)) + 'dB/'
+
+
+def dl_training_logistic_setting(indicator_list, prefix_list):
+    """:87-106 -> [ckpts_dir, 'ldpc-ckpt', 'latest'] of the network being trained (the directory is created)."""
+    prefix = next(prefix_list[i] for i, e in enumerate(indicator_list) if e)
+    ckpts_dir = _dl_stage_root() + 'ckpts/' + prefix + '/' + _dl_stage_snr_info() + str(get_map('num_iterations')) + 'th/'
+    os.makedirs(ckpts_dir, exist_ok=True)
+    return [ckpts_dir, 'ldpc-ckpt', 'latest']
+
+
+def dl_training_log_dir():
+    """Where Training_NN leaves ``dist-error-pattern-<nn>.pkl`` (nn_training.py:489)."""
+    return _dl_stage_root() + 'log/' + get_map('selected_decoder_type') + '/' + _dl_stage_snr_info()
+
+
+def dl_training_data_setting(data_root):
+    """The cached retrain set (:140-159): ``<data_root>/snr<lo>-<hi>dB/<T>th/<type>/ldpc-*-retrain.tfrecord`` -- where
+    ``training_stage.post_process_input`` writes it -- in batches of unit_batch_size frames (T + 1 rows each);
+    ``data_root`` stands for the reference's '../Training_data_gen_<n>/data'."""
+    from .read_TFdata import data_handler
+    code = get_map('code_parameters')
+    list_length = get_map('num_iterations') + 1
+    name = 'ldpc-allzero-retrain.tfrecord' if get_map('ALL_ZEROS_CODEWORD_TRAINING') else 'ldpc-nonzero-retrain.tfrecord'
+    path = os.path.join(data_root, 'snr' + _dl_stage_snr_info()[:-1], str(get_map('num_iterations')) + 'th',
+                        get_map('selected_decoder_type'), name)
+    return data_handler(code.check_matrix_column, path, get_map('unit_batch_size') * list_length)
 
 
 def training_setting_global(argv):

@@ -69,6 +69,49 @@ class conv_bitwise:   # noqa: N801  (name kept from the reference)
         return np.concatenate([self.cnv_one.ravel(), self.cnv_two.ravel(), self.cnv_three.ravel(),
                                self.dense_kernel.ravel(), self.dense_bias.ravel()]).astype(F32)
 
+    TRAINABLE = ("cnv_one", "cnv_two", "cnv_three", "dense_kernel", "dense_bias")   # attributes, in the packed order
+
+    def initialize(self, seed=0):
+        """Fresh weights with the Keras defaults of the layers: ``glorot_uniform`` kernels -- uniform on [-a, a],
+        a = sqrt(6 / (fan_in + fan_out)), fan_in = 3 in and fan_out = 3 out for a Conv1D of kernel 3, (in, out) for the
+        Dense layer -- and a zero bias.  Drawn from ``numpy.random.default_rng(seed)``: the distribution is TensorFlow's,
+        the random stream is not, so a run does not reproduce a TensorFlow run weight for weight."""
+        rng = np.random.default_rng(seed)
+        sh = self.shapes()
+        drawn = {}
+        for name in ("cnv_one", "cnv_two", "cnv_three", "dense_kernel"):
+            shape = sh[name]
+            receptive = int(np.prod(shape[:-2]))
+            limit = np.sqrt(6.0 / (receptive * shape[-2] + receptive * shape[-1]))
+            drawn[name] = rng.uniform(-limit, limit, size=shape).astype(F32)
+        return self.set_weights(drawn["cnv_one"], drawn["cnv_two"], drawn["cnv_three"], drawn["dense_kernel"],
+                                np.zeros(sh["dense_bias"], F32))
+
+    def trainable_variables(self):
+        """[conv1, conv2, conv3, dense kernel, dense bias]: the arrays themselves, in the packed order."""
+        if self.cnv_one is None:
+            raise RuntimeError("conv_bitwise: no weights (initialize, restore a checkpoint or call set_weights)")
+        return [getattr(self, a) for a in self.TRAINABLE]
+
+    def loss_and_grads(self, rows, labels):
+        """The training step's loss (nn_training.py:293-297 of the training stage) on the retrain rows ([F, L, n] or
+        [F*L, n]; NumPy or a device tensor) against ``labels`` [F, n], and its gradient: (loss as a float, one float32
+        array per trainable variable, unpacked from the f64 gradient of ``ldpc_dia_cnn_grad``).  One synchronisation."""
+        from ._osd_common import _dec
+        dec = _dec()
+        if not isinstance(rows, torch.Tensor):
+            rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=F32)).to(dec.device)
+        rows = rows.reshape(-1, self.list_length, self.n_dims).contiguous()
+        if not isinstance(labels, torch.Tensor):
+            labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64)).to(dec.device)
+        loss_sum, grad, _ = dec.dia_cnn_grad(rows, dec.pack_bits(labels.contiguous()), self.packed())
+        both = torch.cat([loss_sum, grad]).cpu().numpy()
+        grads, at = [], 1
+        for v in self.trainable_variables():
+            grads.append(both[at:at + v.size].reshape(v.shape).astype(F32))
+            at += v.size
+        return float(both[0]), grads
+
     def preprocessing_inputs(self, input_slice):
         """:198-211 without the transpose -> (rows [F, L, n] f32, channel values [F, n], labels [F, n])."""
         original_input, original_label = np.asarray(input_slice[0]), np.asarray(input_slice[1])

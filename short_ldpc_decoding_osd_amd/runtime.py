@@ -632,6 +632,29 @@ class Decoder:
                                        _ptr(out), self._stream()), "ldpc_dia_cnn")
         return out
 
+    def dia_cnn_grad(self, rows, label_bits, weights, want_out=False):
+        """Training step of the bit-wise CNN (ldpc_dia_cnn_grad): the reference's loss (nn_training.py:293-297), summed
+        over the frames and bits of ``rows`` [F, L, n], and its gradient with respect to every weight, in one call.
+        ``label_bits``: packed code bits [F, words] int64 (``pack_bits``); ``weights``: as ``dia_cnn``.  Returns
+        (loss_sum [1] f64, grad [n_weights] f64 in the packed order of the weights, out [F, n] f32 -- ``dia_cnn``'s, bit
+        for bit -- or None)."""
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+        if rows.dtype != torch.float32 or rows.device != self.device or rows.dim() != 3 or rows.shape[2] != self.n \
+                or not rows.is_contiguous():
+            raise ValueError(f"rows: expected a contiguous float32 [F, L, {self.n}] tensor on {self.device}")
+        self._chk(label_bits, torch.int64, (self.words,), "label_bits")
+        F = rows.shape[0]
+        if label_bits.shape[0] != F:
+            raise ValueError(f"label_bits: {label_bits.shape[0]} frames for {F} frames of rows")
+        make = torch.empty if F > 0 else torch.zeros      # (F = 0 writes nothing: the sums are 0)
+        loss_sum = make((1,), dtype=torch.float64, device=self.device)
+        grad = make((w.size,), dtype=torch.float64, device=self.device)
+        out = self.empty((F, self.n), torch.float32) if want_out else None
+        _lib.check(self.L.ldpc_dia_cnn_grad(self._ctx, _ptr(rows), _ptr(label_bits), F, rows.shape[1],
+                                            w.ctypes.data_as(C.POINTER(C.c_float)), w.size, _ptr(out), _ptr(loss_sum), _ptr(grad),
+                                            self._stream()), "ldpc_dia_cnn_grad")
+        return loss_sum, grad, out
+
     def osd_counts(self, cw, label_bits, index=None, count=None, ntep=None, counts=None, F=None):
         """counts[3] += {frames, frames_wrong, teps_total}; labels are looked up through index."""
         F = cw.shape[0] if F is None else F
