@@ -770,6 +770,53 @@ int ldpc_dia_cnn_grad(ldpc_ctx *ctx, const float *d_rows, const uint64_t *d_labe
                       void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Training of the sliding-window early-stop classifier (Predict_outlier_light, the `fcn` of ldpc_hosd_sliding).
+ * Relative to LDPC_128/DL_Training_serial/ of the reference: reform_inputs interval_boundary.py:224-249 and the
+ * loss / tape / validation of predict_phase.py:104-135, :203-212, :236-260.
+ *
+ * Windows.  A record is the nblk block minima of one frame (a row of a search call's d_block_min); d_index [R] (nullable:
+ * frames 0..R-1) selects the kept frames, as ldpc_compact writes them, and d_success[f] says whether frame f's overall
+ * minimum is the label's metric (locate_phase != -1).  For window position i = 0 .. nblk-win and record r, output row
+ * i*R + r (window-major) holds
+ *   d_inputs [(nblk-win+1)*R][win+1] f32 : record[i .. i+win-1] in ascending order, then (float)i
+ *   d_labels [(nblk-win+1)*R] u8         : min(window) == min(record) && d_success[frame]
+ *   d_class_count [2] i64 (nullable)      : WRITTEN (not accumulated): rows with label 0, rows with label 1
+ * 1 <= win <= 15 and win <= nblk <= 1024, the limits of ldpc_hosd_sliding.  Sort, minimum and equality are exact, so the
+ * result is defined bit for bit; +inf is an ordinary value, a NaN makes that record's rows unspecified (nothing is read
+ * or written outside the buffers).  The entries of d_index are the caller's: each must name a row of d_block_min.
+ * Scratch (R floats) is allocated and freed in stream order; no host-device copy, no synchronisation.  R = 0 writes
+ * nothing.  Refusals (LDPC_E_ARG, before any launch) name the call and the argument.                                  */
+int ldpc_fcn_windows(ldpc_ctx *ctx, const float *d_block_min, const uint8_t *d_success, const int32_t *d_index, int64_t R,
+                     int32_t nblk, int32_t win, float *d_inputs, uint8_t *d_labels, int64_t *d_class_count, void *stream);
+
+/* Loss, gradient and counts of one batch of windows.  Sample b = 0..B-1 is row d_index[b] (nullable: row b; entries may
+ * repeat and come in any order, each must name a row) of
+ *   d_inputs [N][win+1] f32, d_labels [N] u8 (0 = continue, 1 = stop), d_weight [N] f32 (nullable: 1).
+ * fcn_weights / n_weights: HOST, as ldpc_hosd_sliding (dense1 [win+1][win+1] then dense2 [win+1][2]; (win+1)^2 + 2(win+1)).
+ * Forward, in the float order of ldpc_hosd_sliding: h = x.W1 and z = h.W2, each output a sequential f32 sum over its
+ * input index from the first product; m = max(z), e_c = expf(z_c - m), p_c = e_c / (e0 + e1); no fused multiply-adds.
+ * Per sample, with y the label, sw the weight, pred = p0 < p1, pen = (pred && y == 0) ? penalty : 1 (no gradient flows
+ * through it) and s = (double)sw * pen:
+ *   loss term  -s * log((double)max(p_y, 1e-30f))
+ *   g_c = p_y >= 1e-30f ? s * ((double)p_c - [c == y]) : 0          (dloss/dz_c)
+ * The network is linear up to the softmax: with the moments m[i][c] = sum_b x_i g_c (f64 products and sums)
+ *   dW1[i][j] = sum_c m[i][c] W2[j][c],   dW2[j][c] = sum_i W1[i][j] m[i][c]      (f64, ascending index).
+ * The kernel_regularizer of dense1 has no part in the reference's loss (model.losses is never added) and none here.
+ * Outputs, any subset of them NULL; the others keep their bits:
+ *   d_p        [B][2] f32
+ *   d_loss_sum [1] f64
+ *   d_grad_sum [n_weights] f64, in the packed order of the weights
+ *   d_acc      [2] f64 : sum sw [pred == y], sum sw     (the weighted CategoricalAccuracy's numerator and denominator)
+ *   d_counts   [3] i64 : #[y == pred], #[y > pred], #[y < pred]                      (S, F1, F2 of the validation)
+ * d_labels is required when any output but d_p is asked for.  No float atomics: per-workgroup partial sums and a fixed
+ * tree whose shape depends on (B, win) alone, so repeated calls give the same bits on any stream.  Scratch for the
+ * partials (at most 76 KiB) is allocated and freed in stream order; no host-device copy, no synchronisation.  B = 0
+ * writes nothing.  Refusals (LDPC_E_ARG, before any launch) name the call and the argument.                            */
+int ldpc_fcn_grad(ldpc_ctx *ctx, const float *d_inputs, const uint8_t *d_labels, const float *d_weight, const int32_t *d_index,
+                  int64_t B, int32_t win, const float *fcn_weights, int32_t n_weights, float penalty, float *d_p,
+                  double *d_loss_sum, double *d_grad_sum, double *d_acc, int64_t *d_counts, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * One batch through the whole path with a single host call: the body of the reference drivers'
  * per-batch loops (ldpc_128_testing.py:117-131 then pb_testing.py / fs_testing.py per failed frame):
  *   NMS-T -> error counters -> failed-frame compaction -> OSD (front end + search) on the failures

@@ -29,6 +29,7 @@ SYMBOLS = (
     "ldpc_hosd_pattern_teps", "ldpc_hosd_front", "ldpc_hosd_search", "ldpc_hosd_sliding",
     "ldpc_hosdx_supported", "ldpc_hosdx_front", "ldpc_hosdx_search", "ldpc_hosdx_sliding",
     "ldpc_hosdw_supported", "ldpc_hosdw_front", "ldpc_hosdw_search", "ldpc_hosdw_sliding", "ldpc_dia_cnn", "ldpc_dia_cnn_grad",
+    "ldpc_fcn_windows", "ldpc_fcn_grad",
     "ldpc_pipeline_run", "ldpc_pipeline_timing",
 )
 
@@ -140,6 +141,8 @@ def load():
         "ldpc_hosdw_supported": (C.c_int, [vp]),
         "ldpc_dia_cnn": (C.c_int, [vp, vp, i64, i32, C.POINTER(f32), i32, vp, vp]),
         "ldpc_dia_cnn_grad": (C.c_int, [vp, vp, vp, i64, i32, C.POINTER(f32), i32, vp, vp, vp, vp]),
+        "ldpc_fcn_windows": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
+        "ldpc_fcn_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, C.POINTER(f32), i32, f32, vp, vp, vp, vp, vp, vp]),
         "ldpc_pipeline_run": (C.c_int, [vp, C.POINTER(Pipeline), vp]),
         "ldpc_pipeline_timing": (C.c_int, [vp, i32, C.POINTER(f32)]),
     }

@@ -447,6 +447,7 @@ __global__ __launch_bounds__(256) void hosd_sliding_kernel(const float *__restri
 
 #include "ldpc_hosdx.h"   // the same three kernels for any shape with k, n - k <= 64
 #include "ldpc_hosdw.h"   // ... and for k up to 127 and an H of up to 127 rows of rank <= 64
+#include "ldpc_fcn.h"     // training of the sliding-window classifier: window builder, loss and gradient
 
 namespace ldpc {
 
@@ -760,6 +761,45 @@ int ldpc_hosdw_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_m
                        reinterpret_cast<u64 *>(d_cw), d_metric, d_best, d_teps_evaluated);
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
+}
+
+int ldpc_fcn_windows(ldpc_ctx *ctx, const float *d_block_min, const uint8_t *d_success, const int32_t *d_index, int64_t R,
+                     int32_t nblk, int32_t win, float *d_inputs, uint8_t *d_labels, int64_t *d_class_count, void *stream)
+{
+    static const char who[] = "ldpc_fcn_windows";
+    if (!ctx) return fail(LDPC_E_ARG, "%s: ctx is NULL", who);
+    if (R < 0) return fail(LDPC_E_ARG, "%s: R = %lld is negative", who, (long long)R);
+    if (win < 1 || win > kSlideMaxWin) return fail(LDPC_E_ARG, "%s: win = %d outside 1..%d", who, (int)win, kSlideMaxWin);
+    if (nblk < win || nblk > kHosdMaxBlocks)
+        return fail(LDPC_E_ARG, "%s: nblk = %d outside win = %d .. %d", who, (int)nblk, (int)win, kHosdMaxBlocks);
+    if (R == 0) return LDPC_OK;
+    if (int rc = first_null(who, {{"d_block_min", d_block_min}, {"d_success", d_success}, {"d_inputs", d_inputs},
+                                  {"d_labels", d_labels}})) return rc;
+    return fcn_windows_run(d_block_min, d_success, d_index, R, nblk, win, d_inputs, d_labels, d_class_count, (hipStream_t)stream);
+}
+
+int ldpc_fcn_grad(ldpc_ctx *ctx, const float *d_inputs, const uint8_t *d_labels, const float *d_weight, const int32_t *d_index,
+                  int64_t B, int32_t win, const float *fcn_weights, int32_t n_weights, float penalty, float *d_p,
+                  double *d_loss_sum, double *d_grad_sum, double *d_acc, int64_t *d_counts, void *stream)
+{
+    static const char who[] = "ldpc_fcn_grad";
+    if (!ctx) return fail(LDPC_E_ARG, "%s: ctx is NULL", who);
+    if (B < 0) return fail(LDPC_E_ARG, "%s: B = %lld is negative", who, (long long)B);
+    if (win < 1 || win > kSlideMaxWin) return fail(LDPC_E_ARG, "%s: win = %d outside 1..%d", who, (int)win, kSlideMaxWin);
+    const int d = win + 1, want = d * d + 2 * d;
+    if (n_weights != want) return fail(LDPC_E_ARG, "%s: n_weights = %d, win = %d takes %d", who, (int)n_weights, (int)win, want);
+    if (int rc = first_null(who, {{"fcn_weights", fcn_weights}})) return rc;
+    if (B == 0) return LDPC_OK;
+    if (int rc = first_null(who, {{"d_inputs", d_inputs}})) return rc;
+    const bool sums = d_loss_sum || d_grad_sum || d_acc || d_counts;
+    if (sums)
+        if (int rc = first_null(who, {{"d_labels", d_labels}})) return rc;
+    if (!sums && !d_p) return LDPC_OK;
+    SlideFcnArg w = {};
+    for (int i = 0; i < d * d; ++i) w.w1[i] = fcn_weights[i];
+    for (int i = 0; i < 2 * d; ++i) w.w2[i] = fcn_weights[d * d + i];
+    return fcn_grad_run(d_inputs, d_labels, d_weight, d_index, B, win, w, penalty, d_p, d_loss_sum, d_grad_sum, d_acc, d_counts,
+                        (hipStream_t)stream);
 }
 
 }  // extern "C"

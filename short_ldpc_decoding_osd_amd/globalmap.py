@@ -162,6 +162,17 @@ def dl_training_logistic_setting(indicator_list, prefix_list):
     return [ckpts_dir, 'ldpc-ckpt', 'latest']
 
 
+def dl_training_set_predict_model(DIA):   # noqa: N803
+    """:107-124 -> [ckpts_dir, 'ldpc-ckpt', 'latest'] of the sliding-window classifier being trained (the directory is
+    created): the directory ``set_predict_model(DIA)`` resolves with the same root and training_snr = snr_lo = snr_hi.
+    The reference names no restore step here; 'latest' resumes a run where the directory holds a checkpoint."""
+    nn_type = 'fcn' if DIA else 'benchmark'
+    ckpts_dir = (_dl_stage_root() + 'ckpts/' + nn_type + '/' + _dl_stage_snr_info() + str(get_map('num_iterations')) + 'th/len-'
+                 + str(get_map('decoding_length')) + '-order-' + str(get_map('threshold_sum')) + '/')
+    os.makedirs(ckpts_dir, exist_ok=True)
+    return [ckpts_dir, 'ldpc-ckpt', 'latest']
+
+
 def dl_training_log_dir():
     """Where Training_NN leaves ``dist-error-pattern-<nn>.pkl`` (nn_training.py:489)."""
     return _dl_stage_root() + 'log/' + get_map('selected_decoder_type') + '/' + _dl_stage_snr_info()

@@ -4,7 +4,8 @@
 kernel behind ``ldpc_dia_cnn``.  ``Predict_outlier_light`` (:136-149) is the sliding-window early-stop classifier; the
 device form lives in ``ldpc_hosd_sliding`` and ``__call__`` here is a NumPy f32 form in the same operation order, so the
 host replay of ``ordered_statistics_decoding.osd.sliding_osd`` can use it.  Weights are NumPy arrays in the Keras
-layouts, restored from the training stage's checkpoints by ``nn_testing.NN_gen``.
+layouts, restored from the training stage's checkpoints by ``nn_testing.NN_gen``.  Both networks are trained here too:
+``loss_and_grads`` of either class is one call of its HIP training kernel (``ldpc_dia_cnn_grad``, ``ldpc_fcn_grad``).
 
 Float order (shared with the kernels, include/ldpc_osd.h): every output of a Conv1D or Dense layer is a sequential f32
 sum over its flattened input index (Conv1D: (tap, in-channel), tap-major), starting from the first product, then
@@ -153,6 +154,40 @@ class Predict_outlier_light:   # noqa: N801
         if self.dense1 is None:
             raise RuntimeError("Predict_outlier_light: no weights (restore a checkpoint or call set_weights)")
         return np.concatenate([self.dense1.ravel(), self.dense2.ravel()]).astype(F32)
+
+    TRAINABLE = ("dense1", "dense2")   # attributes, in the packed order
+
+    def initialize(self, seed=0):
+        """Fresh weights with the initializers of the reference's layers (nn_net.py of the training stage): ``dense1``
+        RandomNormal(stddev 0.05), ``dense2`` the Keras default glorot_uniform, uniform on [-a, a] with
+        a = sqrt(6 / (win + 1 + 2)).  Drawn from ``numpy.random.default_rng(seed)``: the distributions are TensorFlow's,
+        the random stream is not."""
+        rng = np.random.default_rng(seed)
+        d = self.input_width
+        limit = np.sqrt(6.0 / (d + 2))
+        return self.set_weights((rng.standard_normal((d, d)) * 0.05).astype(F32),
+                                rng.uniform(-limit, limit, size=(d, 2)).astype(F32))
+
+    def trainable_variables(self):
+        """[dense1 kernel, dense2 kernel]: the arrays themselves, in the packed order."""
+        if self.dense1 is None:
+            raise RuntimeError("Predict_outlier_light: no weights (initialize, restore a checkpoint or call set_weights)")
+        return [getattr(self, a) for a in self.TRAINABLE]
+
+    def loss_and_grads(self, inputs, labels, weight=None, index=None, penalty=1.0):
+        """One training step's loss and gradients on the device (``Decoder.fcn_grad`` -> ldpc_fcn_grad): the windows
+        ``inputs`` [N, win+1] f32 / ``labels`` [N] uint8 / per-sample ``weight`` [N] f32 are device tensors, ``index``
+        [B] int32 names the rows of the batch (valid by the caller's construction; default: every row).  Returns (loss
+        as a float, [dW1, dW2] float32 in the Keras shapes, acc = (sum of the weights where the prediction is right, sum
+        of the weights), counts = (S, F1, F2)).  The l2 kernel_regularizer the reference declares on ``dense1`` never
+        reaches its hand-written loss (model.losses is not added there), so it has no part here.  One synchronisation."""
+        from ._osd_common import _dec
+        out = _dec().fcn_grad(inputs, labels, self.packed(), self.sliding_win_width, penalty, weight=weight, index=index,
+                              check_index=False)
+        both = torch.cat([out["loss_sum"], out["acc"], out["grad"]]).cpu().numpy()
+        d = self.input_width
+        grads = [both[3:3 + d * d].reshape(d, d).astype(F32), both[3 + d * d:].reshape(d, 2).astype(F32)]
+        return float(both[0]), grads, (float(both[1]), float(both[2])), tuple(int(c) for c in out["counts"].cpu().numpy())
 
     def __call__(self, inputs):
         x = np.asarray(inputs, dtype=F32).reshape(-1, self.input_width)

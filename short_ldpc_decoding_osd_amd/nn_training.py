@@ -109,11 +109,12 @@ def generate_pattern_dist(inputs, labels, pattern_cnt, boundary_MRB):   # noqa: 
 
 
 # ------------------------------------------------------------------------------------------------------ checkpoints
-def checkpoint_tensors(nn, optimizer):
-    """The bundle of tf.train.Checkpoint(myAwesomeModel=nn, myAwesomeOptimizer=optimizer) (:371): the five variables, the
-    optimizer's step count and its m / v slot of every variable that has one."""
+def checkpoint_tensors(nn, optimizer, paths=None):
+    """The bundle of tf.train.Checkpoint(myAwesomeModel=nn, myAwesomeOptimizer=optimizer) (:371): the variables (``paths``:
+    attribute -> object path; default the five of conv_bitwise), the optimizer's step count and its m / v slot of every
+    variable that has one."""
     t = {f"{OPTIMIZER_NAME}/iter{VARIABLE_SUFFIX}": np.array(optimizer.iterations, np.int64)}
-    for attr, path in VARIABLE_PATHS.items():
+    for attr, path in (VARIABLE_PATHS if paths is None else paths).items():
         t[f"{ROOT_NAME}/{path}{VARIABLE_SUFFIX}"] = getattr(nn, attr).copy()
         for slot, store in (("m", optimizer.m), ("v", optimizer.v)):
             if attr in store:
@@ -121,12 +122,12 @@ def checkpoint_tensors(nn, optimizer):
     return t
 
 
-def checkpoint_saver(nn, optimizer, ckpts_dir, ckpt_nm):
+def checkpoint_saver(nn, optimizer, ckpts_dir, ckpt_nm, paths=None):
     """CheckpointManager.save stand-in: writes ``<ckpts_dir>/<ckpt_nm>-<step>`` and the ``checkpoint`` state file (every
     checkpoint is kept; the reference keeps the last five)."""
     def save(checkpoint_number):
         return tf_checkpoint.write_checkpoint(os.path.join(ckpts_dir, f"{ckpt_nm}-{checkpoint_number}"),
-                                              checkpoint_tensors(nn, optimizer))
+                                              checkpoint_tensors(nn, optimizer, paths))
     return save
 
 
@@ -144,13 +145,13 @@ def retore_saved_model(restore_ckpts_dir, restore_step, ckpt_nm):
     return int(ckpt_f.split('-')[-1]), ckpt_f
 
 
-def restore_optimizer(optimizer, prefix):
-    """The optimizer's step count and slots from a bundle of ``checkpoint_tensors``."""
+def restore_optimizer(optimizer, prefix, paths=None):
+    """The optimizer's step count and slots from a bundle of ``checkpoint_tensors`` (``paths`` as there)."""
     tensors = tf_checkpoint.read_checkpoint(prefix)
     key = f"{OPTIMIZER_NAME}/iter{VARIABLE_SUFFIX}"
     if key in tensors:
         optimizer.iterations = int(tensors[key])
-    for attr, path in VARIABLE_PATHS.items():
+    for attr, path in (VARIABLE_PATHS if paths is None else paths).items():
         for slot, store in (("m", optimizer.m), ("v", optimizer.v)):
             key = f"{ROOT_NAME}/{path}/.OPTIMIZER_SLOT/{OPTIMIZER_NAME}/{slot}{VARIABLE_SUFFIX}"
             if key in tensors:

@@ -655,6 +655,85 @@ class Decoder:
                                             self._stream()), "ldpc_dia_cnn_grad")
         return loss_sum, grad, out
 
+    # ------------------------------------------------------------------ training of the sliding-window classifier
+    def _fcn_index(self, index, rows, name, check_index):
+        """A 1-D int32 row list on the device; with ``check_index`` its range is checked (one synchronisation)."""
+        if not isinstance(index, torch.Tensor) or index.device != self.device or index.dtype != torch.int32 \
+                or index.dim() != 1 or not index.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous 1-D int32 tensor on {self.device}")
+        if check_index and index.numel():
+            lo, hi = (int(v) for v in torch.aminmax(index))
+            if lo < 0 or hi >= rows:
+                raise ValueError(f"{name}: entries {lo}..{hi} outside the {rows} rows")
+        return index
+
+    def fcn_windows(self, block_min, success, index=None, win=5, check_index=True):
+        """Training windows of the sliding-window classifier (ldpc_fcn_windows; reform_inputs of the reference's training
+        stage).  ``block_min`` [F, nblk] f32: a search call's block minima; ``success`` [F] bool / uint8: the frame's
+        overall minimum is the label's metric; ``index`` [R] int32 (optional): the kept frames, as ``compact`` writes them
+        (pass ``index[:count]``).  Returns (inputs [(nblk-win+1)*R, win+1] f32: the ascending window then its position,
+        window-major, row i*R + r; labels [(nblk-win+1)*R] uint8; class_count [2] int64: rows with label 0 / 1).
+        ``check_index=False`` skips the range check of ``index`` (a synchronisation) where the list is valid by
+        construction."""
+        if not isinstance(block_min, torch.Tensor) or block_min.device != self.device or block_min.dtype != torch.float32 \
+                or block_min.dim() != 2 or not block_min.is_contiguous():
+            raise ValueError(f"block_min: expected a contiguous float32 [F, nblk] tensor on {self.device}")
+        F, nblk = block_min.shape
+        if not isinstance(success, torch.Tensor) or success.device != self.device or success.dtype not in (torch.bool, torch.uint8) \
+                or tuple(success.shape) != (F,) or not success.is_contiguous():
+            raise ValueError(f"success: expected a contiguous bool / uint8 [{F}] tensor on {self.device}")
+        win = int(win)
+        if not 1 <= win <= 15 or not win <= nblk <= 1024:
+            raise ValueError(f"fcn_windows: win = {win}, nblk = {nblk}: 1 <= win <= 15 and win <= nblk <= 1024")
+        R = F if index is None else self._fcn_index(index, F, "index", check_index).numel()
+        rows = (nblk - win + 1) * R
+        inputs = self.empty((rows, win + 1), torch.float32)
+        labels = self.empty((rows,), torch.uint8)
+        class_count = torch.zeros(2, dtype=torch.int64, device=self.device)      # (R = 0 writes nothing)
+        _lib.check(self.L.ldpc_fcn_windows(self._ctx, _ptr(block_min), _ptr(success), _ptr(index), R, nblk, win, _ptr(inputs),
+                                           _ptr(labels), _ptr(class_count), self._stream()), "ldpc_fcn_windows")
+        return inputs, labels, class_count
+
+    def fcn_grad(self, inputs, labels, weights, win, penalty, weight=None, index=None, want_p=False, want_grad=True,
+                 check_index=True):
+        """Training step of the sliding-window classifier (ldpc_fcn_grad): the reference's weighted, penalised
+        cross-entropy (calculation_loss of its training stage) summed over the batch, its gradient with respect to both
+        kernels, the weighted accuracy sums and the validation counts, in one call.  ``inputs`` [N, win+1] f32 and
+        ``labels`` [N] uint8 as ``fcn_windows`` returns them; ``weights``: the packed f32 vector of
+        ``nn_net.Predict_outlier_light.packed()``; ``weight`` [N] f32 (optional): the per-sample class weights;
+        ``index`` [B] int32 (optional): the rows of the batch, in any order, repeats allowed (default: all N rows).
+        Returns dict(loss_sum [1] f64, grad [n_weights] f64 in the packed order or None, acc [2] f64 = (sum of the weights
+        where the prediction is right, sum of the weights), counts [3] int64 = (S, F1, F2), p [B, 2] f32 or None)."""
+        win = int(win)
+        if not 1 <= win <= 15:
+            raise ValueError(f"fcn_grad: win = {win} outside 1..15")
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+        if w.size != (win + 1) ** 2 + 2 * (win + 1):
+            raise ValueError(f"weights: {w.size} values, a window of {win} takes {(win + 1) ** 2 + 2 * (win + 1)}")
+        if not isinstance(inputs, torch.Tensor) or inputs.dim() != 2:
+            raise ValueError(f"inputs: expected a float32 [N, {win + 1}] tensor on {self.device}")
+        self._chk(inputs, torch.float32, (win + 1,), "inputs")
+        N = inputs.shape[0]
+        self._chk(labels, torch.uint8, (), "labels")
+        if labels.shape[0] != N:
+            raise ValueError(f"labels: {labels.shape[0]} entries for {N} rows of inputs")
+        if weight is not None:
+            self._chk(weight, torch.float32, (), "weight")
+            if weight.shape[0] != N:
+                raise ValueError(f"weight: {weight.shape[0]} entries for {N} rows of inputs")
+        B = N if index is None else self._fcn_index(index, N, "index", check_index).numel()
+        make = torch.empty if B > 0 else torch.zeros      # (B = 0 writes nothing: the sums are 0)
+        out = dict(loss_sum=make((1,), dtype=torch.float64, device=self.device),
+                   grad=make((w.size,), dtype=torch.float64, device=self.device) if want_grad else None,
+                   acc=make((2,), dtype=torch.float64, device=self.device),
+                   counts=make((3,), dtype=torch.int64, device=self.device),
+                   p=self.empty((B, 2), torch.float32) if want_p else None)
+        _lib.check(self.L.ldpc_fcn_grad(self._ctx, _ptr(inputs), _ptr(labels), _ptr(weight), _ptr(index), B, win,
+                                        w.ctypes.data_as(C.POINTER(C.c_float)), w.size, float(penalty), _ptr(out["p"]),
+                                        _ptr(out["loss_sum"]), _ptr(out["grad"]), _ptr(out["acc"]), _ptr(out["counts"]),
+                                        self._stream()), "ldpc_fcn_grad")
+        return out
+
     def osd_counts(self, cw, label_bits, index=None, count=None, ntep=None, counts=None, F=None):
         """counts[3] += {frames, frames_wrong, teps_total}; labels are looked up through index."""
         F = cw.shape[0] if F is None else F
