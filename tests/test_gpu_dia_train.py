@@ -19,6 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 K, U = TM.K, TM.U      # the float32 chain length behind one product / loss term, and the unit roundoff
 CODES = {"ccsds": None, "96_48": "LDPC_N96_K48_P8_set0_dmin10.alist", "121_80": "ArrayCode_N121_K80_r0.66.alist"}
 SHAPES = [("ccsds", L, F) for L in (7, 8, 13, 64) for F in (1, 3, 100)] + [("96_48", 13, 3), ("121_80", 13, 3)]
+# dia_grad_kernel's workgroup: 256 threads up to L = 22, 128 up to L = 46, 64 beyond -- both sides of either switch point
+SHAPES += [("ccsds", L, F) for L in (22, 23, 46, 47) for F in (3, 100)]
 
 
 @pytest.fixture(scope="module")
@@ -130,12 +132,13 @@ def test_loss_and_gradient_within_bound_of_model(decs, code, L, F):
 
 
 # ------------------------------------------------------------------------------------------------ 3. exact forward
-@pytest.mark.parametrize("L", [7, 13])
+@pytest.mark.parametrize("L", [7, 13, 23, 47])
 def test_exact_forward_gradient_equals_autograd(decs, L):
     """Weights that are multiples of 1/8 in [-1, 1] and rows that are multiples of 1/4 in [-8, 8]: every product and
-    partial sum of the forward pass is a multiple of 2^-14, exact in float32 while it stays below 2^10 (these draws stay
-    below 2^8), so out is the float64 forward -- asserted below.  The gradient then equals torch autograd (no moment
-    identity) within the bound of the model test."""
+    partial sum of the forward pass is a multiple of 2^-14, exact in float32 while it stays below 2^10 (the outputs of
+    these draws stay below 2^8 up to L = 13, reach 270 at L = 23 and 703 at L = 47), so out is the float64 forward --
+    asserted below.  The gradient then equals torch autograd (no moment identity) within the bound of the model test.
+    L = 23 and 47 run the 128- and the 64-thread workgroup of dia_grad_kernel."""
     dec = decs("ccsds")
     rng = np.random.default_rng(L)
     F = 100
@@ -174,8 +177,14 @@ def test_many_elements_per_thread(decs):
 
 # ------------------------------------------------------------------------------------------------ 5. determinism
 def test_deterministic_on_any_stream_and_additive_over_the_batch(decs):
-    dec = decs("ccsds")
-    L, F = 13, 5000                      # 2500 workgroups: the finish kernel's lanes sum 39 or 40 partials each
+    _deterministic_and_additive(decs("ccsds"), 13, 5000)     # 2500 workgroups: the finish kernel's lanes sum 39 or 40 partials each
+
+
+def test_deterministic_and_additive_with_the_128_thread_workgroup(decs):
+    _deterministic_and_additive(decs("ccsds"), 23, 2500)     # L = 23: workgroups of 128, 2500 of them again
+
+
+def _deterministic_and_additive(dec, L, F):
     ws, rows, labels = _case(dec, L, F, 9)
     w = DM.pack_cnn(ws)
     rows_d, lab_d = to_dev(rows, dec), to_dev(pack_np(labels).view(np.int64), dec)
