@@ -24,7 +24,8 @@ struct FrontResult {
 
 
 // sort + column gather + elimination + bookkeeping of one frame (one wavefront); results in registers
-// (a1 / a2: the magnitude bits of y[lane] / y[64 + lane])
+// (a1 / a2: the magnitude bits of y[lane] / y[64 + lane]; Gcols: the 128 columns of G, in global memory or -- osd_front_kernel,
+//  which copies them once per workgroup -- in LDS: the function is inlined, so the gather below is then a ds_read_b64)
 template <bool GE_LANE_OPAQUE = false>
 __device__ __forceinline__ FrontResult front_device_vals(FrontLds &L, unsigned a1, unsigned a2, const u64 *__restrict__ Gcols, int lane)
 {
@@ -44,8 +45,8 @@ __device__ __forceinline__ FrontResult front_device_vals(FrontLds &L, unsigned a
     int rho = lane, idx1 = lane, idx2 = lane + 64;
     // The elimination compares the lane number with each of its 64 step numbers, in the exchange path only (a step in thirty).
     // Given the kernel's own `lane`, the compiler computes all 64 compares ahead of osd_front_kernel's frame loop and parks 37
-    // of the 64 SGPR pairs in lanes of two VGPRs: 64 v_cmp + 74 v_writelane per workgroup -- which is per frame when the grid
-    // covers the frames -- and a v_readlane pair wherever one is used.  GE_LANE_OPAQUE hands the elimination a copy of the
+    // of the 64 SGPR pairs in lanes of two VGPRs: 64 v_cmp + 74 v_writelane per workgroup, two VGPRs that the kernel does not
+    // have to spare at 8 waves per SIMD, and a v_readlane pair wherever one is used.  GE_LANE_OPAQUE hands the elimination a copy of the
     // lane number that the compiler cannot see through (an empty asm, no instruction), so each compare stays in the block
     // that uses it.  For osd_front_kernel only: in osd_fused2r_kernel, at 128 VGPRs, the same copy moves eight VGPRs to scratch.
     int ge_lane = lane;
@@ -76,13 +77,5 @@ __device__ __forceinline__ FrontResult front_device_vals(FrontLds &L, unsigned a
     wave_fence();
     return res;
 }
-
-template <bool GE_LANE_OPAQUE = false>
-__device__ __forceinline__ FrontResult front_device(FrontLds &L, const float *__restrict__ y, long long src,
-                                                    const u64 *__restrict__ Gcols, int lane)
-{
-    return front_device_vals<GE_LANE_OPAQUE>(L, __float_as_uint(y[src * 128 + lane]) & 0x7FFFFFFFu, __float_as_uint(y[src * 128 + 64 + lane]) & 0x7FFFFFFFu, Gcols, lane);
-}
-
 
 }  // namespace ldpc

@@ -42,6 +42,17 @@ inline int first_null(const char *who, std::initializer_list<NamedPtr> required)
 // decodes several frames in turn).
 inline unsigned frame_grid(int64_t F) { return (unsigned)(F < 65536 ? F : 65536); }
 
+// The grid of osd_front_kernel, a frame pipeline (ldpc_osd_small.h): kFrontGridX times the wavefronts that are resident at once,
+// 32 per CU (8 per SIMD: 64 VGPRs and 4.6 KiB of LDS per one-wavefront workgroup), and no more than F.  Workgroup b decodes
+// frames b, b + grid, b + 2 grid, ... below the device-side count, with the loads of the next frames in flight.  The time per
+// frame hardly varies, so the dispatcher has nothing to even out: 1x was the fastest of 1x, 2x and 4x (profiles/front_pipeline/).
+constexpr int kFrontGridX = 1;
+inline unsigned front_grid(int cu_count, int64_t F)
+{
+    const int64_t g = (int64_t)cu_count * 32 * kFrontGridX;
+    return (unsigned)(F < g ? F : g);
+}
+
 constexpr int kMaxIters = 64;  // alpha[] travels by value in the kernel arguments
 
 struct AlphaArg {

@@ -157,7 +157,7 @@ static unsigned osd_grid(int64_t F)
     return (unsigned)(want < 1 ? 1 : (want < 4096 ? want : 4096));
 }
 
-// (frame_grid, one wavefront per workgroup: ldpc_internal.h)
+// (frame_grid, one wavefront per workgroup, and front_grid, the front end's frame pipeline: ldpc_internal.h)
 
 // the rotation-paired kernels: 4 wavefronts per SIMD are resident (10 KiB of LDS each); the grid is 6x that, ~1.5 frames per
 // workgroup at the headline size: the dispatcher then evens out the different scan times, and the prefetch still covers the
@@ -167,7 +167,7 @@ static unsigned grid2r(const ldpc_ctx *ctx, int64_t F) { const int64_t g = (int6
 static void launch_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F, uint8_t *d_perm,
                          u64 *d_parity, int32_t *d_nswaps, hipStream_t s)
 {
-    hipLaunchKernelGGL(osd_front_kernel, dim3(frame_grid(F)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
+    hipLaunchKernelGGL(osd_front_kernel, dim3(front_grid(ctx->cu_count, F)), dim3(64), 0, s, d_y, d_index, d_count, (long long)F,
                        ctx->osd_tables.d_Gcols, d_perm, d_parity, d_nswaps);
 }
 

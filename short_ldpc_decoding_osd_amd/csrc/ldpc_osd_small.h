@@ -39,16 +39,42 @@ __global__ __launch_bounds__(64) void osd_front_kernel(const float *__restrict__
         long long F, const u64 *__restrict__ Gcols, unsigned char *__restrict__ perm_out, u64 *__restrict__ parity_out, int *__restrict__ nswaps)
 {
     __shared__ FrontLds L;   // one wavefront per workgroup
+    __shared__ u64 Gl[128];  // the columns of G: the same for every frame, so the gather after the sort reads LDS, not L2
     const int lane = threadIdx.x;
+    const u64 g1 = Gcols[lane], g2 = Gcols[64 + lane];              // in flight while the count and the first frames are fetched
     const long long nframes = frame_count(count, F);
-
-    for (long long f = blockIdx.x; f < nframes; f += gridDim.x) {
-        const long long src = index ? index[f] : f;
-        const FrontResult res = front_device<true>(L, y, src, Gcols, lane);     // (true: see GE_LANE_OPAQUE, ldpc_front.h)
-        perm_out[f * 128 + lane] = (unsigned char)res.o1;
-        perm_out[f * 128 + 64 + lane] = (unsigned char)res.o2;
-        parity_out[f * 64 + lane] = res.Prow;
-        if (nswaps && lane == 0) nswaps[f] = res.ns;
+    // Software pipeline over the frames of this workgroup (the launcher's grid is front_grid(): frames block, block + grid, ...):
+    // the frame number is asked for two frames ahead and the y row one frame ahead.  A list entry stays a 32-bit value until
+    // the trip that forms the row address with it (widening it is a use, and a use is where the wave waits for the load), and
+    // the row's magnitude bits are taken at the end of the trip before, so that nothing is awaited right behind its request.
+    const long long G = gridDim.x;
+    long long f0 = blockIdx.x, f1 = f0 + G, f2 = f1 + G;
+    int ia = 0, ib = 0;
+    unsigned a1 = 0, a2 = 0;
+    if (index && f0 < nframes) ia = index[f0];
+    if (index && f1 < nframes) ib = index[f1];
+    if (f0 < nframes) {
+        const long long src = index ? (long long)ia : f0;
+        a1 = __float_as_uint(y[src * 128 + lane]) & 0x7FFFFFFFu; a2 = __float_as_uint(y[src * 128 + 64 + lane]) & 0x7FFFFFFFu;
+    }
+    Gl[lane] = g1; Gl[64 + lane] = g2;                              // (read after the first wave_fence of front_device_vals)
+    while (f0 < nframes) {
+        unsigned yb1 = 0, yb2 = 0;
+        if (f1 < nframes) {
+            const long long src = index ? (long long)ib : f1;
+            yb1 = __float_as_uint(y[src * 128 + lane]); yb2 = __float_as_uint(y[src * 128 + 64 + lane]);
+        }
+        int ic = 0;
+        if (index && f2 < nframes) ic = index[f2];
+        // (true: see GE_LANE_OPAQUE, ldpc_front.h)
+        const FrontResult res = front_device_vals<true>(L, a1, a2, Gl, lane);
+        perm_out[f0 * 128 + lane] = (unsigned char)res.o1;
+        perm_out[f0 * 128 + 64 + lane] = (unsigned char)res.o2;
+        parity_out[f0 * 64 + lane] = res.Prow;
+        if (nswaps && lane == 0) nswaps[f0] = res.ns;
+        f0 = f1; f1 = f2; f2 += G;
+        asm volatile("" : "+v"(yb1), "+v"(yb2));    // (no instruction: keeps the two ANDs, the row's first use, down here)
+        ib = ic; a1 = yb1 & 0x7FFFFFFFu; a2 = yb2 & 0x7FFFFFFFu;
     }
 }
 
