@@ -1,6 +1,11 @@
 """-m gpu: decode calls on DIFFERENT streams of ONE context must not disturb each other (include/ldpc_osd.h,
 ldpc_ctx_create): the compaction uses no scratch, everything else a per-stream workspace.  Three pipelines with
-different batches run concurrently on three streams; every output must equal the single-stream run."""
+different batches run concurrently on three streams; every output must equal the single-stream run.  The compaction
+itself: ragged and unaligned inputs, and segments of more than one step per block (above 256 x 8192 flags), alone and with
+the counters riding along.
+
+Wall time on one MI355X: 5 s for the file's 10 cases; the slowest takes 1.3 s (test_three_streams_one_context[pb-3-72000]),
+a compaction case 0.3 s at the most."""
 import numpy as np
 import pytest
 import torch
@@ -83,3 +88,50 @@ def test_compact_unaligned_and_ragged(dec):
         assert int(count.cpu()[0]) == 5000 * val
         if val:
             assert np.array_equal(index.cpu().numpy(), np.arange(5000))
+
+
+COMPACT_ONE_STEP = 256 * 8192          # ldpc_util.hip: kMaxSeg segments of one step of compact_kernel<EVAL, 8> (1024 threads x 8 flags)
+
+
+@pytest.mark.parametrize("B,steps", [(COMPACT_ONE_STEP, 1), (COMPACT_ONE_STEP + 1, 2), (3 * 2 ** 20 + 12345, 2),
+                                     (4 * 2 ** 20 + 8192 + 5, 3)])
+def test_compact_segments_of_several_steps(dec, B, steps):
+    """Above 256 x 8192 flags a block of compact_kernel loops over its own segment (``c0 += kStep``, ``base += tot``): the
+    last size with one step per block, the first with two, and sizes with two and three; count and list against torch.nonzero."""
+    chunks = -(-B // 8192)
+    assert -(-chunks // 256) == steps                   # compact_geometry(): steps per segment
+    g = torch.Generator(device=dec.device).manual_seed(B)
+    base = torch.where(torch.rand(B + 3, device=dec.device, generator=g) < 0.3,
+                       torch.randint(1, 256, (B + 3,), device=dec.device, generator=g), 0).to(torch.uint8)
+    for off in (0, 3):
+        flag = base[off:off + B]
+        index, count = dec.compact(flag)
+        ref = torch.nonzero(flag).flatten().to(torch.int32)
+        n = int(count.cpu()[0])
+        assert n == ref.numel() and 0.29 * B < n < 0.31 * B and torch.equal(index[:n], ref), (B, off)
+
+
+def test_counting_compaction_segments_of_two_steps(dec):
+    """compact_kernel<true, 8> (ldpc_pipeline_run with labels) with two steps per segment: the NMS counters, the failure list
+    and the OSD stage over it against the separate calls on the same frames, all on the device (the parts are pinned
+    against the oracle at small sizes)."""
+    from short_ldpc_decoding_osd_amd.pipeline import BatchPipeline
+    B = COMPACT_ONE_STEP + 1 + 8192
+    y, lab = dec.gen_frames(B, seed=20241020, snr_db=4.0)
+    pipe = BatchPipeline(dec, B, 10, ALPHA0, osd_order=0, want_soft=False).bind(y, lab)
+    pipe.index.fill_(-7)
+    pipe.run()
+    res = dec.nms(y, 10, ALPHA0, want_soft=False)
+    five = dec.eval_counts(res["hard"], lab, res["fail"])
+    ref = torch.nonzero(res["fail"]).flatten().to(torch.int32)
+    nf = ref.numel()
+    out = dec.osd_decode(y, 0, index=ref)
+    three = dec.osd_counts(out["cw"], lab, index=ref, ntep=out["ntep"])
+    torch.cuda.synchronize()
+    c = pipe.counters()
+    assert 0 < nf < B and int(c[0]) == B and int(c[4]) == nf
+    assert torch.equal(pipe.hard, res["hard"]) and torch.equal(pipe.fail, res["fail"])
+    assert torch.equal(c[:5], five) and torch.equal(c[5:], three)
+    assert int(pipe.count[0]) == nf and torch.equal(pipe.index[:nf], ref) and bool((pipe.index[nf:] == -7).all())
+    for k in ("cw", "metric", "best"):
+        assert torch.equal(getattr(pipe, k)[:nf].view(torch.uint8), out[k].view(torch.uint8)), k
