@@ -1,7 +1,8 @@
 // H-form ordered-statistics primitives for high-rate codes and for an H with redundant rows (n <= 128, H of R <= 127 rows and
-// rank m <= 64 as given, k = n - m up to 127): the kernels of ldpc_hosdx.h with two-word columns on the row side of the front
-// end and 128 MRB columns in the scans.  Included from ldpc_hosd.hip after ldpc_hosdx.h, whose hosdx_cost it uses unchanged,
-// with hosd_frame_best, SlideLds / slide_p1 / key_metric and the kHosd* limits of ldpc_hosd.hip.
+// rank m <= 64 as given, k = n - m up to 127): what this family owns -- a front end with two-word columns on the row side,
+// an LDS plan with 128 MRB columns and its per-frame set-up -- and its traits (HosdW) for the scans of ldpc_hosd_scan.h, which
+// its search and sliding kernels call.  Included from ldpc_hosd.hip after ldpc_hosdx.h, whose metric (hosdx_cost) and shared
+// set-up parts (hosdx_updated_values, hosdx_label_metric) it uses unchanged.
 //   mag_input_gen / check_matrix_reorder   ordered_statistics_decoding.py:25-41
 //   identify_mrb / full_gf2elim            ordered_statistics_decoding.py:43-80, 222-257
 //   acquire_min / sliding_osd              ordered_statistics_decoding.py:153-218
@@ -131,16 +132,7 @@ __global__ __launch_bounds__(256) void hosdw_front_kernel(const float *__restric
     const bool mrbA = lane >= m && in1, mrbB = in2;      // ... and a column of the MRB side (m <= 64)
 
     for (long long f = wave; f < F; f += (long long)gridDim.x * 4) {
-        // ---- mag_input_gen (:25-28): the sort of hosdx_front_kernel, padded slots included -----------------
-        const unsigned a1 = in1 ? (__float_as_uint(x[f * n + lane]) & 0x7FFFFFFFu) : 0u;
-        const unsigned a2 = in2 ? (__float_as_uint(x[f * n + 64 + lane]) & 0x7FFFFFFFu) : 0u;
-        const float bs = bucket_scale(a1, a2);
-        const u64 k1 = in1 ? ~(((u64)a1 << 32) | (unsigned)lane) : (u64)(unsigned)~(unsigned)lane;
-        const u64 k2 = in2 ? ~(((u64)a2 << 32) | (unsigned)(lane + 64)) : (u64)(unsigned)~(unsigned)(lane + 64);
-        int r1, r2;
-        bucket_ranks(L.rank, k1, k2, in1 ? 63 - bucket_of(a1, bs) : 0, in2 ? 63 - bucket_of(a2, bs) : 0, lane, r1, r2);
-        L.lri[r1] = (unsigned char)lane;
-        L.lri[r2] = (unsigned char)(lane + 64);
+        hosd_sort_ascending(L, x, f, n, lane);               // mag_input_gen (:25-28), padded slots last
         if (lane < 4) L.mask[lane] = 0;
         L.col[0][lane] = 0ull; L.col[0][64 + lane] = 0ull; L.col[1][lane] = 0ull; L.col[1][64 + lane] = 0ull;
         L.uidx[lane] = 0; L.uidx[lane + 64] = 0;
@@ -225,42 +217,23 @@ __device__ __forceinline__ void hosd_apply(const HSearchWLds<RUNS> &L, uchar4 s,
     if (s.w > 2) { const ulonglong2 c = L.Mcol[s.z & 127]; lo ^= c.x; hi ^= c.y; }
 }
 
-// hosdx_frame_setup with Mrows [F][128] (two word-planes of 64 rows) and up to 127 MRB positions.  Rows >= m and bits >= k
+// The per-frame set-up with Mrows [F][128] (two word-planes of 64 rows) and up to 127 MRB positions.  Rows >= m and bits >= k
 // of Mrows, and lri / uidx entries >= n, are not looked at.
 // On return every thread sees the LUTs, the columns and the keys of blocks 0..nblk-1 reset to ~0.
 template <class LDS>
-__device__ __forceinline__ void hosdw_frame_setup(LDS &L, const float *__restrict__ xo, const float *__restrict__ xm, long long f,
-                                                  int n, int m, const unsigned char *__restrict__ lri,
-                                                  const unsigned char *__restrict__ uidx, const u64 *__restrict__ Mrows, int nblk,
-                                                  const u64 *__restrict__ label, float *__restrict__ truth, u64 &D0lo, u64 &D0hi)
+__device__ __forceinline__ void hosdw_frame_setup(LDS &L, const HShapeNM &sh, const HScanIn &in, long long f, float *__restrict__ truth,
+                                                  u64 &D0lo, u64 &D0hi)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int k = n - m, nb = (n + 7) >> 3, words = (n + 63) >> 6;
-    // ---- phase 0: values in updated order (:172-176), hard decisions, columns, key reset --------
+    const int n = sh.n, m = sh.m, k = n - m, nb = sh.nb, nblk = in.nblk;
+    // ---- phase 0: values in updated order, hard decisions, columns, key reset --------
     if (tid < 128) {
-        const bool live = tid < n;
-        int o = 0;
-        float mv = 0.0f;
-        bool h0 = false;
-        if (live) {
-            o = lri[f * 128 + (uidx[f * 128 + tid] & 127)];
-            o = o < n ? o : 0;                                            // (front-end results hold original bits < n)
-            mv = xm[f * n + o];
-            h0 = tid >= m && !(xo[f * n + o] > 0.0f);                     // initial_mrb (:186-187)
-        }
-        L.o[tid] = (unsigned char)o;
-        L.w[tid] = __builtin_fabsf(mv);
-        const u64 hg = __ballot(live && !(mv > 0.0f));                    // order_hard_original (:180)
-        const u64 hb = __ballot(h0);
-        if (lane == 0) {
-            if (wave == 0) { L.hgL = hg; L.h0L = hb; }
-            else { L.hgM = hg; L.h0H = hb; }
-        }
+        hosdx_updated_values(L, sh, in, f);
     } else {
         // wavefront 2 / 3: the word-plane of MRB positions 0..63 / 64..127
         const int j = 64 * (wave - 2) + lane, kw = k - 64 * (wave - 2);   // this lane's MRB position; MRB positions in the plane
         const u64 kmask = kw >= 64 ? ~0ull : (kw > 0 ? ((1ull << kw) - 1ull) : 0ull);
-        const u64 col = transpose64(lane < m ? (Mrows[f * 128 + 64 * (wave - 2) + lane] & kmask) : 0ull, lane);   // bit r = M[r][j]
+        const u64 col = transpose64(lane < m ? (in.Mrows[f * 128 + 64 * (wave - 2) + lane] & kmask) : 0ull, lane);   // bit r = M[r][j]
         const int p = m + j;                                              // the updated position of MRB position j
         const u64 unit = 1ull << (p & 63);
         ulonglong2 c;
@@ -284,18 +257,24 @@ __device__ __forceinline__ void hosdw_frame_setup(LDS &L, const float *__restric
     }
     __syncthreads();
     D0lo = L.DL0; D0hi = L.hgM ^ L.h0H;
-    if (label && wave == 1) {
-        const u64 l0 = label[f * words], l1 = words > 1 ? label[f * words + 1] : 0ull;
-        const int o1 = L.o[lane], o2 = L.o[64 + lane];
-        const u64 labL = __ballot(lane < n && (((o1 < 64 ? l0 : l1) >> (o1 & 63)) & 1));
-        const u64 labM = __ballot(64 + lane < n && (((o2 < 64 ? l0 : l1) >> (o2 & 63)) & 1));
-        const float t = hosdx_cost(L, labL ^ L.hgL, labM ^ L.hgM, nb);    // (:181-183)
-        if (lane == 0) { if (truth) truth[f] = t; L.truth = t; }
-    }
+    if (in.label && wave == 1) hosdx_label_metric(L, sh, in.label, f, truth);
 }
 
-// hosdx_search_kernel with up to 127 MRB positions: one frame per 256-thread workgroup, the per-thread-run form for a small
-// table (RUNS) and the work-item form otherwise, decided alike from device data by both instantiations.
+// The wide family for the scans of ldpc_hosd_scan.h: 128 two-word columns, the kernel's n and m, TEP positions of 7 bits taken
+// modulo 128; the metric is the any-shape family's.
+struct HosdW {
+    template <bool RUNS> using Lds = HSearchWLds<RUNS>;
+    static constexpr int kPosBits = 7;
+    static __device__ __forceinline__ unsigned pos(unsigned char v) { return v & 127; }
+    template <class LDS> static __device__ __forceinline__ float cost(const LDS &L, u64 lo, u64 hi, const HShapeNM &sh) { return hosdx_cost(L, lo, hi, sh.nb); }
+    template <class LDS>
+    static __device__ __forceinline__ void setup(LDS &L, const HShapeNM &sh, const HScanIn &in, long long f, float *__restrict__ truth, u64 &D0lo,
+                                                 u64 &D0hi)
+    {
+        hosdw_frame_setup(L, sh, in, f, truth, D0lo, D0hi);
+    }
+};
+
 template <bool RUNS>
 __global__ __launch_bounds__(256) void hosdw_search_kernel(const float *__restrict__ xo, const float *__restrict__ xm,
                                                            long long F, int n, int m, const unsigned char *__restrict__ lri,
@@ -307,195 +286,11 @@ __global__ __launch_bounds__(256) void hosdw_search_kernel(const float *__restri
                                                            u64 *__restrict__ cw_out, float *__restrict__ metric_out,
                                                            int *__restrict__ best_out)
 {
-    __shared__ HSearchWLds<RUNS> L;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nb = (n + 7) >> 3, words = (n + 63) >> 6;
-    int run0 = 0, run1 = 0, b0 = 0;
-    const int ntep = nblk > 0 ? block_off[nblk] : 0;
-    bool runs = ntep <= kHosdLdsTeps && nblk <= kHosdRunBlocks;
-    if (runs) {         // (uniform) any TEP of weight 3?
-        if (tid == 0) L.heavy = 0;
-        __syncthreads();
-        bool h = false;
-        for (int t = tid; t < ntep; t += 256) h |= teps[t].w > 2;
-        if (h) L.heavy = 1;
-        __syncthreads();
-        runs = L.heavy == 0;
-    }
-    if (runs != RUNS) return;
-    if constexpr (RUNS) {
-        // once per workgroup: the block offsets and the table in LDS, this thread's run and its first block
-        for (int b = tid; b <= nblk; b += 256) L.boff[b] = block_off[b];
-        for (int t = tid; t < ntep; t += 256) { const uchar4 s = teps[t]; L.tl[t] = (unsigned short)((s.x & 127) | ((s.y & 127) << 7) | (s.w << 14)); }
-        __syncthreads();
-        const int per = ((ntep + 255) / 256) | 1;      // (odd: a lane's run starts on its own LDS bank)
-        run0 = tid * per < ntep ? tid * per : ntep; run1 = run0 + per < ntep ? run0 + per : ntep;
-        int lo = 0, hi = nblk;       // the block that holds TEP run0: the last b with boff[b] <= run0 (blocks may be empty)
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (L.boff[mid] <= run0) lo = mid; else hi = mid; }
-        b0 = lo;
-    }
-
-    for (long long f = blockIdx.x; f < F; f += gridDim.x) {
-        u64 DL0, DM0;
-        hosdw_frame_setup(L, xo, xm, f, n, m, lri, uidx, Mrows, nblk, label, truth, DL0, DM0);
-        if constexpr (RUNS) {
-            // ---- phase 2: the scan: this thread's run, a flush per block boundary -----------------------------
-            int b = b0;
-            float best = INFINITY;
-            int bestt = 0;
-            for (int t = run0; t < run1; ++t) {
-                while (t >= L.boff[b + 1]) {      // the run leaves block b (the next ones may be empty)
-                    if (best < INFINITY) atomicMin(&L.keys[b], ((u64)(unsigned)__float_as_int(best) << 32) | (unsigned)bestt);
-                    best = INFINITY;
-                    ++b;
-                }
-                u64 DL = DL0, DM = DM0;
-                const unsigned tv = L.tl[t];
-                hosd_apply(L, make_uchar4((unsigned char)(tv & 127u), (unsigned char)((tv >> 7) & 127u), 0, (unsigned char)(tv >> 14)), DL, DM);
-                const float c = hosdx_cost(L, DL, DM, nb);
-                if (c < best) { best = c; bestt = t; }                     // ascending t: first minimum
-            }
-            if (best < INFINITY) atomicMin(&L.keys[b], ((u64)(unsigned)__float_as_int(best) << 32) | (unsigned)bestt);
-        } else {
-            // ---- phase 2: the scan; items are numbered block by block, slice by slice -----------------------
-            int item = 0, b = 0, s = nblk > 0 ? block_off[0] : 0, t1 = nblk > 0 ? block_off[1] : 0;
-            for (;;) {
-                int want = 0;
-                if (lane == 0) want = atomicAdd(&L.ticket, 1);
-                want = __builtin_amdgcn_readfirstlane(want);
-                // advance (b, s) to item `want`; empty blocks own no item
-                while (b < nblk) {
-                    if (s >= t1) { ++b; if (b < nblk) { s = block_off[b]; t1 = block_off[b + 1]; } continue; }
-                    if (item == want) break;
-                    ++item; s += kHosdChunk;
-                }
-                if (b >= nblk) break;
-                const int e = s + kHosdChunk < t1 ? s + kHosdChunk : t1;
-                float best = INFINITY;
-                int bestt = 0x7FFFFFFF;
-                for (int t = s + lane; t < e; t += 64) {
-                    u64 DL = DL0, DM = DM0;
-                    hosd_apply(L, teps[t], DL, DM);
-                    const float c = hosdx_cost(L, DL, DM, nb);
-                    if (c < best) { best = c; bestt = t; }                 // ascending t per lane: first minimum
-                }
-                const int wl = wave_argmin_lane(best, bestt);
-                if (lane == wl)
-                    atomicMin(&L.keys[b], ((u64)(unsigned)__float_as_int(best) << 32) | (unsigned)bestt);
-                ++item; s += kHosdChunk;
-            }
-        }
-        __syncthreads();
-        // ---- phase 3: per-block results, the overall first minimum, its codeword -------------------------
-        u64 mine = ~0ull;
-        for (int b = tid; b < nblk; b += 256) {
-            const u64 key = L.keys[b];
-            const bool empty = key == ~0ull;
-            block_min[f * nblk + b] = empty ? INFINITY : __int_as_float((int)(key >> 32));
-            if (block_arg) block_arg[f * nblk + b] = empty ? -1 : (int)(unsigned)key;
-            mine = key < mine ? key : mine;
-        }
-        if (mine != ~0ull) atomicMin(&L.best, mine);
-        __syncthreads();
-        if (wave == 0) hosd_frame_best(L, teps, f, DL0, DM0, cw_out, metric_out, best_out, words);
-        __syncthreads();
-    }
+    __shared__ HosdW::Lds<RUNS> L;
+    hosd_search_body<HosdW, RUNS>(L, HShapeNM(n, m), {xo, xm, F, lri, uidx, Mrows, teps, block_off, nblk, label}, block_min, block_arg,
+                                  {truth, cw_out, metric_out, best_out});
 }
 
-// hosdx_sliding_kernel with up to 127 MRB positions: the block scan in groups with the reference's sliding-window early stop.
-__global__ __launch_bounds__(256) void hosdw_sliding_kernel(const float *__restrict__ xo, const float *__restrict__ xm, long long F,
-                                                            int n, int m, const unsigned char *__restrict__ lri,
-                                                            const unsigned char *__restrict__ uidx, const u64 *__restrict__ Mrows,
-                                                            const uchar4 *__restrict__ teps, const int *__restrict__ block_off,
-                                                            int nblk, int win, double margin, SlideFcnArg fcn, int group,
-                                                            const u64 *__restrict__ label, int *__restrict__ deep_out,
-                                                            float *__restrict__ gmin_out, float *__restrict__ truth,
-                                                            unsigned char *__restrict__ success, u64 *__restrict__ cw_out,
-                                                            float *__restrict__ metric_out, int *__restrict__ best_out,
-                                                            int *__restrict__ nteps_out)
-{
-    __shared__ HSearchWLds<false> L;
-    __shared__ SlideLds S;
-    const int tid = threadIdx.x, wave = tid >> 6;
-    const int nb = (n + 7) >> 3, words = (n + 63) >> 6;
-    for (int b = tid; b <= nblk; b += 256) S.boff[b] = block_off[b];
-    __syncthreads();
-
-    for (long long f = blockIdx.x; f < F; f += gridDim.x) {
-        u64 DL0, DM0;
-        hosdw_frame_setup(L, xo, xm, f, n, m, lri, uidx, Mrows, nblk, label, truth, DL0, DM0);
-        int k = 0, deep = win;           // (lane 0) the next window decision, blocks evaluated so far in the reference's sense
-        float gmin = INFINITY;           // (lane 0) global_min
-        int g0 = 0, g1 = 0;
-        for (;;) {
-            // ---- the group [g0, g1): `group` blocks, or blocks until kSlideGroupTeps TEPs and the first window
-            if (group > 0) {
-                g1 = g0 + group < nblk ? g0 + group : nblk;
-            } else {
-                g1 = g0 + 1;
-                while (g1 < nblk && (g1 < win || S.boff[g1] - S.boff[g0] < kSlideGroupTeps)) ++g1;
-            }
-            const int t0 = S.boff[g0], nt = S.boff[g1] - t0, per = (nt + 255) / 256;
-            const int run0 = t0 + (tid * per < nt ? tid * per : nt), run1 = t0 + (tid * per + per < nt ? tid * per + per : nt);
-            if (run0 < run1) {
-                int lo = g0, hi = g1;    // the block that holds TEP run0: the last b with boff[b] <= run0 (blocks may be empty)
-                while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (S.boff[mid] <= run0) lo = mid; else hi = mid; }
-                int b = lo;
-                float best = INFINITY;
-                int bestt = 0;
-                for (int t = run0; t < run1; ++t) {
-                    while (t >= S.boff[b + 1]) {
-                        if (best < INFINITY) atomicMin(&L.keys[b], ((u64)(unsigned)__float_as_int(best) << 32) | (unsigned)bestt);
-                        best = INFINITY;
-                        ++b;
-                    }
-                    u64 DL = DL0, DM = DM0;
-                    hosd_apply(L, teps[t], DL, DM);
-                    const float c = hosdx_cost(L, DL, DM, nb);
-                    if (c < best) { best = c; bestt = t; }                     // ascending t: first minimum
-                }
-                if (best < INFINITY) atomicMin(&L.keys[b], ((u64)(unsigned)__float_as_int(best) << 32) | (unsigned)bestt);
-            }
-            __syncthreads();
-            // ---- lane 0: every decision whose window lies in the blocks scanned so far (:193-209)
-            if (tid == 0) {
-                bool stop = false;
-                for (; !stop && k <= nblk - win && k + win <= g1; ++k) {
-                    deep = k + win;
-                    if (k != 0 && key_metric(L.keys[k + win - 1]) > gmin) continue;       // :203-204
-                    for (int i = 0; i < win; ++i) {                                     // the window, ascending
-                        const float v = key_metric(L.keys[k + i]);
-                        int j = i;
-                        while (j > 0 && S.x[j - 1] > v) { S.x[j] = S.x[j - 1]; --j; }
-                        S.x[j] = v;
-                    }
-                    S.x[win] = (float)k;
-                    const float p1 = slide_p1(S, win, fcn);
-                    gmin = S.x[0] < gmin ? S.x[0] : gmin;                               // min(global_min, window.min())
-                    stop = (double)p1 > margin;
-                }
-                S.done = stop || g1 >= nblk;
-                S.deep = deep;
-            }
-            __syncthreads();
-            if (S.done) break;
-            g0 = g1;
-        }
-        // ---- per-frame results; the best candidate among the blocks the reference evaluates (0 .. deep_limit-1)
-        const int dl = S.deep;
-        if (tid == 0) {
-            if (deep_out) deep_out[f] = dl;
-            if (gmin_out) gmin_out[f] = gmin;
-            if (success) success[f] = gmin == L.truth;                                 // :213
-            if (nteps_out) nteps_out[f] = S.boff[g1] - S.boff[0];
-        }
-        u64 mine = ~0ull;
-        for (int b = tid; b < dl; b += 256) mine = L.keys[b] < mine ? L.keys[b] : mine;
-        if (mine != ~0ull) atomicMin(&L.best, mine);
-        __syncthreads();
-        if (wave == 0) hosd_frame_best(L, teps, f, DL0, DM0, cw_out, metric_out, best_out, words);
-        __syncthreads();
-    }
-}
+HOSD_SLIDING_KERNEL(hosdw_sliding_kernel, HosdW, HOSD_NM_SHAPE_PARAMS, HShapeNM sh(n, m))
 
 }  // namespace ldpc

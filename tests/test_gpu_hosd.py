@@ -113,6 +113,80 @@ def test_edge_cases(dec, np_code, blocks):
                                           None, None, None, None))
 
 
+def test_argument_errors_and_empty_batch(dec, np_code):
+    """The raw (128,64) entry points on F = 2 frames and a 3-block table of 5 TEPs: each required pointer set to NULL is named,
+    the other refusals keep their codes and texts, nothing is written before a refusal, and F = 0 is accepted and writes nothing."""
+    import ctypes as C
+    from short_ldpc_decoding_osd_amd import _lib
+    from tests.dlosd_model import stopping_fcn_weights
+    F, nblk, win = 2, 3, 2
+    x, y, cw = _frames(np_code, F, 5, refine=False)
+    teps = np.array([[0, 0, 0, 0], [1, 0, 0, 1], [2, 0, 0, 1], [3, 4, 0, 2], [5, 6, 0, 2]], dtype=np.uint8)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+    d = dict(x=to_dev(x, dec), y=to_dev(y, dec), lab=to_dev(pack_np(cw).view(np.int64), dec), teps=to_dev(teps, dec),
+             off=to_dev(np.array([0, 1, 3, 5], dtype=np.int32), dec))
+    fw = np.ascontiguousarray(np.concatenate([a.ravel() for a in stopping_fcn_weights(win)]), np.float32)
+
+    def buf(shape, dtype):
+        t = torch.empty(shape, dtype=dtype, device=dec.device)
+        t.view(torch.uint8).fill_(0xA5)
+        return t
+    b = dict(lri=buf((F, 128), torch.uint8), uidx=buf((F, 128), torch.uint8), M=buf((F, 64), torch.int64), nswaps=buf((F,), torch.int32),
+             block_min=buf((F, nblk), torch.float32), block_arg=buf((F, nblk), torch.int32), truth=buf((F,), torch.float32),
+             cw=buf((F, 2), torch.int64), metric=buf((F,), torch.float32), best=buf((F,), torch.int32),
+             deep_limit=buf((F,), torch.int32), global_min=buf((F,), torch.float32), success=buf((F,), torch.uint8),
+             teps=buf((F,), torch.int32))
+
+    def front(F=F, d=d, b=b, null=()):
+        g = lambda key: None if key in null or b is None else p(b[key])   # noqa: E731
+        return dec.L.ldpc_hosd_front(dec._ctx, p(d["x"]), F, g("lri"), g("uidx"), g("M"), g("nswaps"), dec._stream())
+
+    def search(F=F, d=d, b=b, nblk=nblk, null=()):
+        g = lambda key: None if key in null or b is None else p(b[key])   # noqa: E731
+        return dec.L.ldpc_hosd_search(dec._ctx, p(d["x"]), p(d["y"]), F, g("lri"), g("uidx"), g("M"), p(d["teps"]), p(d["off"]), nblk,
+                                      p(d["lab"]), g("block_min"), g("block_arg"), g("truth"), g("cw"), g("metric"), g("best"),
+                                      dec._stream())
+
+    def sliding(F=F, d=d, b=b, nblk=nblk, win=win, fw=fw, n_weights=None, null=()):
+        g = lambda key: None if key in null or b is None else p(b[key])   # noqa: E731
+        return dec.L.ldpc_hosd_sliding(dec._ctx, p(d["x"]), p(d["y"]), F, g("lri"), g("uidx"), g("M"), p(d["teps"]), p(d["off"]), nblk,
+                                       win, 0.9, None if fw is None else fw.ctypes.data_as(C.POINTER(C.c_float)),
+                                       fw.size if n_weights is None else n_weights, 0, p(d["lab"]), g("deep_limit"),
+                                       g("global_min"), g("truth"), g("success"), g("cw"), g("metric"), g("best"), g("teps"),
+                                       dec._stream())
+
+    def refused(rc, code, text):
+        with pytest.raises(_lib.LdpcError, match=rf"\({code}\): {text}"):
+            _lib.check(rc)
+
+    for key in ("lri", "uidx", "M"):
+        refused(front(null=(key,)), -1, f"ldpc_hosd_front: d_{key} is NULL")
+        refused(search(null=(key,)), -1, f"ldpc_hosd_search: d_{key} is NULL")
+        refused(sliding(null=(key,)), -1, f"ldpc_hosd_sliding: d_{key} is NULL")
+    refused(front(d=dict(d, x=None)), -1, "ldpc_hosd_front: d_order_llr is NULL")
+    for key, name in (("x", "d_order_llr"), ("y", "d_metric_llr"), ("off", "d_block_off"), ("teps", "d_teps")):
+        refused(search(d=dict(d, **{key: None})), -1, f"ldpc_hosd_search: {name} is NULL")
+        refused(sliding(d=dict(d, **{key: None})), -1, f"ldpc_hosd_sliding: {name} is NULL")
+    refused(search(null=("block_min",)), -1, "ldpc_hosd_search: d_block_min is NULL")
+    refused(sliding(fw=None, n_weights=fw.size), -1, "ldpc_hosd_sliding: fcn_weights is NULL")
+    refused(search(d=dict(d, lab=None)), -1, "ldpc_hosd_search: d_truth needs d_label_bits")
+    refused(sliding(d=dict(d, lab=None)), -1, "ldpc_hosd_sliding: d_truth / d_success need d_label_bits")
+    refused(sliding(n_weights=fw.size - 1), -1, f"ldpc_hosd_sliding: {fw.size - 1} classifier weights, a window of 2 takes 15")
+    refused(search(nblk=1025), -5, "ldpc_hosd_search: 1025 TEP blocks, at most 1024")
+    refused(sliding(nblk=1025), -5, "ldpc_hosd_sliding: 1025 TEP blocks, at most 1024")
+    w4 = np.ascontiguousarray(np.concatenate([a.ravel() for a in stopping_fcn_weights(4)]), np.float32)
+    refused(sliding(win=4, fw=w4), -1, r"ldpc_hosd_sliding: bad arguments \(.*win 4, nblk 3, group 0\)")
+    torch.cuda.synchronize()
+    for key, t in b.items():                                     # all of it refused before any launch
+        assert (t.view(torch.uint8) == 0xA5).all(), key
+    none = dict(x=None, y=None, lab=None, teps=None, off=None)
+    assert front(F=0, d=none, b=None) == 0 and search(F=0, d=none, b=None) == 0 and sliding(F=0, d=none, b=None) == 0
+    assert front(F=0) == 0 and search(F=0) == 0 and sliding(F=0) == 0
+    torch.cuda.synchronize()
+    for key, t in b.items():                                     # F = 0 writes nothing
+        assert (t.view(torch.uint8) == 0xA5).all(), key
+
+
 def test_full_scale_properties(dec, np_code, blocks):
     """65 536 frames: every winner is a codeword, never worse than the order-0 candidate; with the label's
     error pattern inside the scanned blocks the winner's metric is <= the label's; permutation outputs are

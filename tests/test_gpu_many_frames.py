@@ -36,9 +36,9 @@ TRIPS = {
     "osd_ge": lambda cu: 4096 * 4,            # ldpc_osd.hip osd_grid()
     "osd_tep_eval": lambda cu: 4096 * 4,      # ldpc_osd.hip osd_grid()
     "index_guard": lambda cu: 1024 * 256,     # ldpc_osd.hip guarded_index(), one entry per thread
-    "hosd_front": lambda cu: 8192 * 4,        # ldpc_hosd.hip:463 grid_for(F, 4)
-    "hosd_search": lambda cu: 8192,           # ldpc_hosd.hip:463 grid_for(F, 1), one frame per workgroup
-    "hosd_sliding": lambda cu: 8192,          # ldpc_hosd.hip:463 grid_for(F, 1)
+    "hosd_front": lambda cu: 8192 * 4,        # ldpc_hosd.hip:243 grid_for(F, 4)
+    "hosd_search": lambda cu: 8192,           # ldpc_hosd.hip:243 grid_for(F, 1), one frame per workgroup
+    "hosd_sliding": lambda cu: 8192,          # ldpc_hosd.hip:243 grid_for(F, 1)
     "nms_generic": lambda cu: 8192 * 4,       # ldpc_nms.hip:443, 4 waves per workgroup
     "nms_train": lambda cu: 32768 // 2 * 2,   # ldpc_nms_train.hip:288, 32768 / waves workgroups of waves frames; waves = 2 below
 }
