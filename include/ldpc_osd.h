@@ -555,6 +555,43 @@ int ldpc_osdw_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
                         int64_t *d_counts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * OSD for longer and low-rate codes, i.e. every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192: the reference's
+ * wimax-like (384,192) code and the codes with n <= 128 and n-k > 64, which the two families above refuse.  Served: the
+ * front end and the conventional search (orders 0..3).  FS-OSD, PB-OSD, one-TEP evaluation, the H-form primitives and the
+ * one-call pipeline are not served for these shapes; codes with n > 384, k > 192 or n-k > 192 -- wimax (1056,880) among
+ * them -- are refused by every OSD entry point.
+ * The contract is that of ldpc_osdx_front / _search / _decode -- d_index / d_count read on the device and nothing written at
+ * or beyond frame min(*d_count, F), ties of the sort to the lower index, the reference's pivot and exchange rule, the TEP
+ * table of this code's k (orders 0..3, first minimum), the float order of the metric (flipped MRB weights ascending from
+ * 0.0f, then the parity positions in bytes of eight from primed position k, each byte ascending from 0.0f, added in
+ * order), the nullable outputs, d_label_bits with d_counts[3] as a pair or not at all, teps_total only with d_ntep -- with
+ * the layouts changed.  With S = ceil(n/64), W = ceil(k/64) and Wp = ceil((n-k)/64):
+ *   d_perm    [F][64 S] u16     : original bit at primed position p < n (MRB 0..k-1, parity k..n-1); 0 for p >= n
+ *   d_parity  [F][64 W][Wp] u64 : row r < k, bit c of word w = P'[r][64 w + c]; rows >= k and bits >= n-k are written as 0
+ *             (as inputs, the search ignores those padded rows and bits; a d_perm entry >= n is the caller's error: that
+ *             frame's result is unspecified, but nothing is read or written outside the buffers)
+ *   d_cw      [F][ceil(n/64)] u64 best codeword, ORIGINAL bit order
+ * For a code that ldpc_osdx_* or ldpc_osdw_* also serves d_parity is byte for byte theirs ([F][64] beside ldpc_osdx_*,
+ * [F][128] beside ldpc_osdw_* with k > 64) and every other output equals theirs bit for bit, d_perm value for value.  (One
+ * case is settled here as the CPU oracle has it: when every cost of a frame is +inf the first TEP of the table wins.)
+ * ldpc_osdl_decode is two launches through the caller's d_perm / d_parity, which are scratch AND outputs and required: no
+ * library workspace, no per-stream state.  Before any launch: an unsupported shape is LDPC_E_UNSUPPORTED (the message names
+ * the limits n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192 and the code's (n,k)), an order outside 0..3 and a NULL in a
+ * required pointer are LDPC_E_ARG (naming the entry point and the offender), F == 0 is LDPC_OK.  The tables (G columns as W
+ * words each and the order-3 TEP table of k: 1 179 809 entries, 4.7 MB, at k = 192; the table another family keeps for this k
+ * is shared) are uploaded by ldpc_ctx_create; nothing is allocated and nothing synchronises in a call (graph-capturable).
+ * ------------------------------------------------------------------------------------- */
+int ldpc_osdl_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
+int ldpc_osdl_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                    uint16_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, void *stream);
+int ldpc_osdl_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                     const uint16_t *d_perm, const uint64_t *d_parity, int32_t order, uint64_t *d_cw, float *d_metric,
+                     int32_t *d_best, int32_t *d_ntep, void *stream);
+int ldpc_osdl_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                     int32_t order, uint16_t *d_perm, uint64_t *d_parity, uint64_t *d_cw, float *d_metric,
+                     int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits, int64_t *d_counts, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H; other shapes: ldpc_hosdx_* below):
  * DL_OSD_Testing_serial/ordered_statistics_decoding.py and nn_net.py: the per-frame sort / elimination /
  * candidate scan, the scan with the sliding-window early stop, and the bit-wise CNN.

@@ -28,6 +28,11 @@ per frame and stop shares, osdw_pb_kernel timed next to osdw_search_kernel of th
 on the same frames.  On a code both families serve, the conventional run also times the osdw kernels on the same frames in the
 same run, alternating with the osdx kernels, the --osd fs run times osdw_fs_kernel alternating with osdx_fs_kernel and the
 --osd pb run osdw_pb_kernel alternating with osdx_pb_kernel.
+A code that neither older family serves and ldpc_osdl_* does (n <= 384, k <= 192, n-k <= 192, e.g.
+tests/golden/wimaxlike_N384_K192_P16_set0.alist, or any code with n <= 128 and n-k > 64) runs the conventional search through
+ldpc_osdl_decode, osdl_front_kernel and osdl_search_kernel timed like the other legs; --osd fs and --osd pb are not served there.
+On a code that ldpc_osdw_* serves as well the conventional run also times the osdl kernels on the same frames, alternating.
+--oracle N times the C oracle's front end (oracle/c_oracle.osd_front, one core) on the first N failures and prints its frames/s.
 --gen hip draws the frames with the library's counter-based generator (Decoder.gen_frames: frames 0 .. --frames - 1 of the set
 --seed, one launch) instead of the torch ops; the JSON line says which.
 One JSON line at the end."""
@@ -98,6 +103,7 @@ def main(argv=None):
     ap.add_argument("--beta", type=float, default=0.1, help="FS-OSD: beta of the lower bound (Main_FS_OSD.py:20)")
     ap.add_argument("--tau-e", type=float, default=None, help="FS-OSD: the stop threshold on the Hamming distance")
     ap.add_argument("--tau-psc", type=float, default=30.0, help="FS-OSD: tau_psc (FS_OSD/globalmap.py:50)")
+    ap.add_argument("--oracle", type=int, default=0, help="time the C oracle's front end on this many of the failures (one core)")
     args = ap.parse_args(argv)
     fs, pb = args.osd == "fs", args.osd == "pb"
     if fs and args.tau_e is None:
@@ -107,8 +113,11 @@ def main(argv=None):
 
     dec = Decoder(Code(args.alist) if args.alist else Code(), 0)
     wide = dec.osdw_supported and not dec.osdx_supported     # k > 64: the high-rate family
-    if not dec.osdx_supported and not dec.osdw_supported:
-        raise SystemExit(f"osdx_fer: the OSD kernels serve n <= 128 and 1 <= n-k <= 64; this code is ({dec.n},{dec.k})")
+    long_ = dec.osdl_supported and not dec.osdx_supported and not dec.osdw_supported     # n > 128 or n-k > 64: the long / low-rate family
+    if not dec.osdx_supported and not dec.osdw_supported and not dec.osdl_supported:
+        raise SystemExit(f"osdx_fer: the OSD kernels serve n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192; this code is ({dec.n},{dec.k})")
+    if long_ and (fs or pb):
+        raise SystemExit(f"osdx_fer: --osd {args.osd} serves n <= 128 and 1 <= n-k <= 64; ({dec.n},{dec.k}) has the conventional search only")
     B = args.frames
     y, labels = dec.gen_frames(B, seed=args.seed, snr_db=args.snr) if args.gen == "hip" else make_frames(dec, B, args.seed, args.snr)
     res = dec.nms(y, args.T, args.alpha)
@@ -129,6 +138,8 @@ def main(argv=None):
         out = pb_decode(y, pbp, index=idx, count=count, label_bits=labels, counts=counts)
     elif wide:
         out = dec.osdw_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
+    elif long_:
+        out = dec.osdl_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
     else:
         out = dec.osdx_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
     torch.cuda.synchronize()
@@ -177,7 +188,18 @@ def main(argv=None):
     if wide:
         legs = [("osdw_front_kernel", lambda: dec.osdw_front(y, index=idx, count=count, out=front)),
                 ("osdw_search_kernel", lambda: dec.osdw_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=out))]
-    elif not fs and not pb and dec.osdw_supported:       # both families serve the code: the osdw kernels on the same frames
+    elif long_:
+        legs = [("osdl_front_kernel", lambda: dec.osdl_front(y, index=idx, count=count, out=front)),
+                ("osdl_search_kernel", lambda: dec.osdl_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=out))]
+    legs_l = []
+    if not fs and not pb and dec.osdw_supported and dec.osdl_supported:   # the osdl kernels on the same frames, alternating
+        outl = dec.osdl_decode(y, args.order, index=idx, count=count)
+        frontl = (outl["perm"], outl["parity"], None)
+        for key in ("cw", "metric", "best", "ntep"):
+            assert torch.equal(outl[key][:nf], out[key][:nf]), key
+        legs_l = [("osdl_front_kernel", lambda: dec.osdl_front(y, index=idx, count=count, out=frontl)),
+                  ("osdl_search_kernel", lambda: dec.osdl_search(y, outl["perm"], outl["parity"], args.order, index=idx, count=count, out=outl))]
+    if not wide and not fs and not pb and dec.osdw_supported:       # both families serve the code: the osdw kernels on the same frames
         outw = dec.osdw_decode(y, args.order, index=idx, count=count)
         frontw = (outw["perm"], outw["parity"], None)
         legs += [("osdw_front_kernel", lambda: dec.osdw_front(y, index=idx, count=count, out=frontw)),
@@ -218,6 +240,19 @@ def main(argv=None):
         out2 = dec.osd_search(y, perm2, par2, p, index=idx, count=count)
         legs += [("osd_front_kernel", lambda: dec.osd_front(y, index=idx, count=count, out=(perm2, par2, ns2))),
                  ("osd_search_kernel(table)", lambda: dec.osd_search(y, perm2, par2, p, index=idx, count=count, out=out2))]
+    legs += legs_l
+    if args.oracle > 0:
+        import time
+        from oracle import c_oracle
+        Gn = np.asarray(dec.code.G)
+        yo = y[idx[:min(nf, args.oracle)].long()].cpu().numpy()
+        c_oracle.osd_front(Gn, yo[0])
+        t0 = time.perf_counter()
+        for row in yo:
+            c_oracle.osd_front(Gn, row)
+        dt = time.perf_counter() - t0
+        result["oracle_front_frames_per_s"] = len(yo) / dt
+        print(f"  C oracle front end, one core: {len(yo)} frames in {dt:.3f} s, {len(yo) / dt:.1f} frames/s", flush=True)
     for _ in range(2):                                   # the legs alternate: two passes over all of them
         for name, fn in legs:
             us = timed(fn, args.calls, args.repeats, args.warmup)

@@ -333,6 +333,30 @@ int pack_osdw_tables(const ldpc_code &c, const OsdTables &base, OsdwTables &t, O
     return LDPC_OK;
 }
 
+int pack_osdl_tables(const ldpc_code &c, const OsdwTables &base, OsdlTables &t, OsdlTablesHost &host)
+{
+    t = OsdlTables();
+    host = OsdlTablesHost();
+    if (c.n > 384 || c.k < 1 || c.k > 192 || c.n - c.k < 1 || c.n - c.k > 192 || c.G.size() != (size_t)c.k * c.n) return LDPC_OK;
+    const int W = (c.k + 63) / 64;
+    host.Gcols.assign((size_t)c.n * W, 0);
+    for (int r = 0; r < c.k; ++r)
+        for (int v = 0; v < c.n; ++v)
+            if (c.G[(size_t)r * c.n + v]) host.Gcols[(size_t)v * W + (r >> 6)] |= 1ull << (r & 63);
+    // one table for order 3; orders 0..2 are its prefixes.  The context's OsdwTables hold the table of this k where they serve the code.
+    int64_t total = tep_table(c.k, 3, nullptr, t.ntep);
+    if (total < 0) return (int)total;
+    t.own_tep = base.k != c.k;
+    if (t.own_tep) {
+        std::vector<uint8_t> sup((size_t)total * 3);
+        if ((total = tep_table(c.k, 3, sup.data(), nullptr)) < 0) return (int)total;
+        host.tep.reserve((size_t)total);
+        pack_supports(sup, host.tep);
+    }
+    t.n = c.n; t.k = c.k;
+    return LDPC_OK;
+}
+
 // osd.error_pattern_gen (DL_OSD_Testing_serial/ordered_statistics_decoding.py:81-98): product over
 // the segments (leftmost slowest) of the lexicographic combinations inside each segment
 int64_t hosd_pattern_teps(int nseg, const int32_t *bounds, const int32_t *pattern, uint8_t *teps)

@@ -85,6 +85,7 @@ struct ldpc_ctx {
     int32_t *d_chk_ptr = nullptr, *d_chk_var = nullptr, *d_var_ptr = nullptr, *d_var_edge = nullptr;
     ldpc::OsdTables osd_tables;    // G columns and TEP tables of any shape with k, n-k <= 64: read by every OSD family
     ldpc::OsdwTables osdw_tables;  // two-word G columns and the TEP table of k <= 127 (n <= 128, n-k <= 64): the ldpc_osdw_* family
+    ldpc::OsdlTables osdl_tables;  // W-word G columns and the TEP table of k <= 192 (n <= 384, n-k <= 192): the ldpc_osdl_* family
     uint64_t *d_Hcols = nullptr;   // [128] column v < n of H as an m-bit word (bit r = H[r][v]), zero beyond n; with hosdx_ok only
     uint32_t *d_gen_G = nullptr;   // [ceil(k/32)][4][ceil(n/4)] G's columns packed over k, transposed for ldpc_gen_frames (ldpc_gen.hip)
     uint64_t *d_HcolsW = nullptr;  // [128][2] column v < n of H as given, rows 0..63 / 64..127, zero beyond n; with hosdw_ok only

@@ -1,10 +1,15 @@
-// The host side that the any-shape family (ldpc_osdx_*, ldpc_osdx.hip) and the high-rate family (ldpc_osdw_*, ldpc_osdw.hip)
-// share: validation, launches and the bodies of their entry points, written once.  Host code only; included after the
-// family's kernel headers.  A family is a traits struct FAM with
-//   tables(ctx)                     its tables in the context (OsdTables / OsdwTables: n, k, d_Gcols, d_tep, ntep, d_tep_fs,
-//                                   fs_off, fs_cnt under the same names); k = 0: the code is not served
+// The host side that the any-shape family (ldpc_osdx_*, ldpc_osdx.hip), the high-rate family (ldpc_osdw_*, ldpc_osdw.hip) and
+// the long / low-rate family (ldpc_osdl_*, ldpc_osdl.hip) share: validation, launches and the bodies of their entry points,
+// written once.  Host code only; included after the family's kernel headers.  A family is a traits struct FAM with
+//   tables(ctx)                     its tables in the context (OsdTables / OsdwTables / OsdlTables: n, k, d_Gcols, d_tep, ntep
+//                                   and, where the family has FS-OSD, d_tep_fs, fs_off, fs_cnt under the same names); k = 0:
+//                                   the code is not served
 //   needs                           the sentence of its UNSUPPORTED message
-//   front, search, fs, tep_eval     its kernels (the same argument lists in both families)
+//   perm_t                          the element of d_perm (uint8_t while n <= 128, uint16_t beyond); the strides of d_perm and
+//                                   d_parity follow from n and k inside the kernels
+//   front(t), search(t)             its front-end and scan kernels for the shape of the tables t (one kernel in the first two
+//                                   families, an instantiation per shape class in the third); the same argument lists in all
+//   fs, tep_eval                    its FS-OSD and one-TEP kernels (the first two families)
 // `who` is the name of the extern "C" entry point, for the error texts.
 // There is no library workspace: the decode entry points run their two launches through the caller's d_perm / d_parity, so the
 // calls hold no per-stream state, allocate nothing and are graph-capturable as they are.
@@ -51,27 +56,27 @@ inline int check_order(int order, const char *who)
 }
 
 // the pointers every scan with F > 0 needs
-inline int scan_required(const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const OsdScanOut &o, const char *who)
+inline int scan_required(const OsdFrames &fr, const void *d_perm, const uint64_t *d_parity, const OsdScanOut &o, const char *who)
 {
     return first_null(who, {{"d_y", fr.y}, {"d_perm", d_perm}, {"d_parity", d_parity}, {"d_cw", o.cw}});
 }
 
 template <class FAM>
-int family_launch_front(const ldpc_ctx *ctx, const OsdFrames &fr, uint8_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, hipStream_t s)
+int family_launch_front(const ldpc_ctx *ctx, const OsdFrames &fr, typename FAM::perm_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, hipStream_t s)
 {
     const auto &t = FAM::tables(ctx);
-    hipLaunchKernelGGL(FAM::front, dim3(frame_grid(fr.F)), dim3(64), 0, s, fr.y, fr.index, fr.count, (long long)fr.F, t.n, t.k, t.d_Gcols,
+    hipLaunchKernelGGL(FAM::front(t), dim3(frame_grid(fr.F)), dim3(64), 0, s, fr.y, fr.index, fr.count, (long long)fr.F, t.n, t.k, t.d_Gcols,
                        d_perm, reinterpret_cast<u64 *>(d_parity), d_nswaps);
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
 }
 
 template <class FAM>
-int family_launch_search(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, int order,
+int family_launch_search(const ldpc_ctx *ctx, const OsdFrames &fr, const typename FAM::perm_t *d_perm, const uint64_t *d_parity, int order,
                          const OsdScanOut &o, OsdCounting c, hipStream_t s)
 {
     const auto &t = FAM::tables(ctx);
-    hipLaunchKernelGGL(FAM::search, dim3(frame_grid(fr.F)), dim3(64), 0, s, fr.y, fr.index, fr.count, (long long)fr.F, t.n, t.k, d_perm,
+    hipLaunchKernelGGL(FAM::search(t), dim3(frame_grid(fr.F)), dim3(64), 0, s, fr.y, fr.index, fr.count, (long long)fr.F, t.n, t.k, d_perm,
                        reinterpret_cast<const u64 *>(d_parity), t.d_tep, (int)t.ntep[order], reinterpret_cast<u64 *>(o.cw), o.metric,
                        o.best, o.ntep, c.label, c.counts);
     LDPC_HIP(hipGetLastError());
@@ -91,7 +96,7 @@ int family_launch_fs(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_
 }
 
 template <class FAM>
-int family_front(ldpc_ctx *ctx, const OsdFrames &fr, uint8_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, void *stream, const char *who)
+int family_front(ldpc_ctx *ctx, const OsdFrames &fr, typename FAM::perm_t *d_perm, uint64_t *d_parity, int32_t *d_nswaps, void *stream, const char *who)
 {
     if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
     if (fr.F == 0) return LDPC_OK;
@@ -100,7 +105,7 @@ int family_front(ldpc_ctx *ctx, const OsdFrames &fr, uint8_t *d_perm, uint64_t *
 }
 
 template <class FAM>
-int family_search(ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, int32_t order, const OsdScanOut &o,
+int family_search(ldpc_ctx *ctx, const OsdFrames &fr, const typename FAM::perm_t *d_perm, const uint64_t *d_parity, int32_t order, const OsdScanOut &o,
                   void *stream, const char *who)
 {
     if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
@@ -111,7 +116,7 @@ int family_search(ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, con
 }
 
 template <class FAM>
-int family_decode(ldpc_ctx *ctx, const OsdFrames &fr, int32_t order, uint8_t *d_perm, uint64_t *d_parity, const OsdScanOut &o,
+int family_decode(ldpc_ctx *ctx, const OsdFrames &fr, int32_t order, typename FAM::perm_t *d_perm, uint64_t *d_parity, const OsdScanOut &o,
                   OsdCounting c, void *stream, const char *who)
 {
     if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;

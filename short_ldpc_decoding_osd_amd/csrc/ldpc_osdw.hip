@@ -16,8 +16,9 @@ namespace ldpc {
 struct Osdw {
     static const OsdwTables &tables(const ldpc_ctx *ctx) { return ctx->osdw_tables; }
     static constexpr const char *needs = "the high-rate OSD kernels need 1 <= n-k <= 64 and n <= 128";
-    static constexpr auto front = osdw_front_kernel;
-    static constexpr auto search = osdw_search_kernel;
+    using perm_t = uint8_t;
+    static constexpr auto front(const OsdwTables &) { return osdw_front_kernel; }
+    static constexpr auto search(const OsdwTables &) { return osdw_search_kernel; }
     static constexpr auto fs = osdw_fs_kernel;
     static constexpr auto tep_eval = osdw_tep_eval_kernel;
 };

@@ -16,8 +16,9 @@ namespace ldpc {
 struct Osdx {
     static const OsdTables &tables(const ldpc_ctx *ctx) { return ctx->osd_tables; }
     static constexpr const char *needs = "the any-shape OSD kernels need 1 <= k <= 64 and 1 <= n-k <= 64";
-    static constexpr auto front = osdx_front_kernel;
-    static constexpr auto search = osdx_search_kernel;
+    using perm_t = uint8_t;
+    static constexpr auto front(const OsdTables &) { return osdx_front_kernel; }
+    static constexpr auto search(const OsdTables &) { return osdx_search_kernel; }
     static constexpr auto fs = osdx_fs_kernel;
     static constexpr auto tep_eval = osdx_tep_eval_kernel;
 };

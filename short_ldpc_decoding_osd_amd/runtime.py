@@ -82,9 +82,19 @@ class Decoder:
         return (index.shape[0] if index is not None else y.shape[0]) if F is None else F
 
     # An OSD family is the prefix of its methods and library functions (``osd``: the (128,64) kernels, ``osdx``: any shape,
-    # ``osdw``: high rate) with the int64 words of a ``parity`` row and the shape tail of a ``tep_eval`` mask.
+    # ``osdw``: high rate, ``osdl``: long / low rate) with the int64 words of a ``parity`` row and the shape tail of a
+    # ``tep_eval`` mask.  ``osdl`` sizes its layouts by the code (``_osd_layout``).
     _OSD_PARITY_WORDS = {"osd": 64, "osdx": 64, "osdw": 128}
     _OSD_MASK_TAIL = {"osd": (), "osdx": (), "osdw": (2,)}
+
+    def _osd_layout(self, fam):
+        """(dtype of ``perm``, shape tail of ``perm``, shape tail of ``parity``) of the family on this code.  ``osdl``: perm
+        [*, 64 ceil(n/64)] int16 (the library's u16), parity [*, 64 ceil(k/64)] int64 with one word per row, or
+        [*, 64 ceil(k/64), ceil((n-k)/64)] with more."""
+        if fam != "osdl":
+            return torch.uint8, (128,), (self._OSD_PARITY_WORDS[fam],)
+        rows, wp = 64 * ((self.k + 63) // 64), (self.n - self.k + 63) // 64
+        return torch.int16, (64 * self.words,), ((rows,) if wp == 1 else (rows, wp))
 
     def _osd_call(self, fam, op, *args):
         """``ldpc_<fam>_<op>(ctx, *args, stream)``, checked."""
@@ -92,10 +102,11 @@ class Decoder:
         _lib.check(getattr(self.L, name)(self._ctx, *args, self._stream()), name)
 
     def _osd_front_results(self, fam, y, perm, parity, F=None):
-        """The checks of the calls that take front-end results (perm [*,128] u8, parity [*,64 or 128] int64).  Returns F."""
+        """The checks of the calls that take front-end results (perm and parity in the layouts of ``_osd_layout``).  Returns F."""
         self._chk(y, torch.float32, (self.n,), "y")
-        self._chk(perm, torch.uint8, (128,), "perm")
-        self._chk(parity, torch.int64, (self._OSD_PARITY_WORDS[fam],), "parity")
+        pdt, ptail, qtail = self._osd_layout(fam)
+        self._chk(perm, pdt, ptail, "perm")
+        self._chk(parity, torch.int64, qtail, "parity")
         return perm.shape[0] if F is None else F
 
     def _osd_front(self, fam, y, index, count, F, out):
@@ -104,8 +115,9 @@ class Decoder:
         if out is not None:
             perm, parity, ns = out
         else:
-            perm = self.empty((F, 128), torch.uint8)
-            parity = self.empty((F, self._OSD_PARITY_WORDS[fam]), torch.int64)
+            pdt, ptail, qtail = self._osd_layout(fam)
+            perm = self.empty((F,) + ptail, pdt)
+            parity = self.empty((F,) + qtail, torch.int64)
             ns = self.empty((F,), torch.int32)
         self._osd_call(fam, "front", _ptr(y), _ptr(index), _ptr(count), F, _ptr(perm), _ptr(parity), _ptr(ns))
         return perm, parity, ns
@@ -134,9 +146,9 @@ class Decoder:
         """``<fam>_<op>`` for the ``*decode`` calls: front end + scan through ``perm`` / ``parity``, which are checked when
         given, allocated when not, and returned in the dict.  F by the rule of ``_osd_frames``; ``arg`` as in ``_osd_search``."""
         F = self._osd_frames(y, index, F)
-        width = self._OSD_PARITY_WORDS[fam]
-        perm = self.empty((F, 128), torch.uint8) if perm is None else self._chk(perm, torch.uint8, (128,), "perm")
-        parity = self.empty((F, width), torch.int64) if parity is None else self._chk(parity, torch.int64, (width,), "parity")
+        pdt, ptail, qtail = self._osd_layout(fam)
+        perm = self.empty((F,) + ptail, pdt) if perm is None else self._chk(perm, pdt, ptail, "perm")
+        parity = self.empty((F,) + qtail, torch.int64) if parity is None else self._chk(parity, torch.int64, qtail, "parity")
         out = self._osd_outputs(out, F)
         self._osd_call(fam, op, _ptr(y), _ptr(index), _ptr(count), F, arg, _ptr(perm), _ptr(parity), _ptr(out["cw"]),
                        _ptr(out["metric"]), _ptr(out["best"]), _ptr(out["ntep"]), _ptr(label_bits), _ptr(counts))
@@ -455,6 +467,30 @@ class Decoder:
         int64).  mask [F,2] int64: bit p of word 0 flips primed MRB position p, bit p of word 1 position 64 + p; bits at or
         beyond k are ignored.  Returns dict(cw[F,words] int64 original bit order, metric[F] f32, hd[F] i32)."""
         return self._osd_tep_eval("osdw", y, perm, parity, mask, index, count)
+
+    # ------------------------------------------------------------------ OSD for longer and low-rate codes (n <= 384, k, n-k <= 192)
+    @property
+    def osdl_supported(self):
+        """Whether the ``osdl_*`` methods serve this code (n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192)."""
+        return bool(self.L.ldpc_osdl_supported(self._ctx))
+
+    def osdl_front(self, y, index=None, count=None, F=None, out=None):
+        """``osdx_front`` for every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192.  With S = ceil(n/64), W = ceil(k/64)
+        and Wp = ceil((n-k)/64), returns (perm [F, 64 S] int16: original bit at primed position p < n, 0 beyond; parity
+        [F, 64 W] int64 for Wp = 1, else [F, 64 W, Wp]: rows r < k of P', bit c of word w = P'[r][64 w + c], 0 elsewhere;
+        nswaps [F] int32); ``out`` may carry those three preallocated (nswaps may be None)."""
+        return self._osd_front("osdl", y, index, count, F, out)
+
+    def osdl_search(self, y, perm, parity, order, index=None, count=None, F=None, out=None):
+        """Conventional order-``order`` search on the results of ``osdl_front``.  Returns the dict of ``osdx_search``."""
+        return self._osd_search("osdl", "search", y, perm, parity, int(order), index, count, F, out)
+
+    def osdl_decode(self, y, order, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
+                    out=None):
+        """``osdx_decode`` for every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192: front end + conventional
+        order-``order`` search, two launches through ``perm`` / ``parity`` in the layouts of ``osdl_front`` (allocated when
+        not given; returned in the dict); ``label_bits`` / ``counts`` as there."""
+        return self._osd_decode("osdl", "decode", y, int(order), index, count, F, perm, parity, label_bits, counts, out)
 
     def osdx_fs_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
         """FS-OSD on front-end results of any supported shape.  ``params``: ``osd_params(order, _lib.OSD_FS, fs_beta=...,

@@ -1,0 +1,200 @@
+"""Host side of the long / low-rate OSD entry points (ldpc_osdl_*): declarations, the resource use of the kernels, the TEP
+table of k = 192, the (384,192) code definition, the self-check of the oracles the GPU tests rely on (tests/osdl_model.py) and
+the premises of the inputs those tests use."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import np_oracle
+from short_ldpc_decoding_osd_amd import Code, _lib, build
+from tests import osdl_model
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("ldpc_osdl_supported", "ldpc_osdl_front", "ldpc_osdl_search", "ldpc_osdl_decode")
+FRONTS = ((2, 1), (2, 2), (4, 1), (4, 2), (4, 3), (6, 1), (6, 2), (6, 3))      # (S, W) of every front-end instantiation
+
+
+def test_header_and_binding_declare_the_entry_points():
+    hdr = open(os.path.join(ROOT, "include", "ldpc_osd.h")).read()
+    declared = set(re.findall(r"\b(ldpc_[A-Za-z0-9_]+)\s*\(", hdr))
+    for name in NAMES:
+        assert name in declared, name
+        assert name in _lib.SYMBOLS, name
+        assert hasattr(_lib.load(), name), name
+    assert "OSD for longer and low-rate codes" in hdr
+    assert _lib.load().ldpc_abi_version() == 5
+
+
+def test_supported_of_no_context_is_false():
+    assert _lib.load().ldpc_osdl_supported(None) == 0
+
+
+def test_front_end_kernels_use_no_scratch(tmp_path):
+    """Device-only compile of ldpc_osdl.hip with the library's flags and the resource remarks: every front-end instantiation
+    keeps its columns in registers (0 bytes of scratch), within 128 VGPRs, and the scans fit the 64 KiB of LDS a workgroup may
+    take.  The table of profiles/osdl/README.md holds the same numbers."""
+    src = os.path.join(build.CSRC, "ldpc_osdl.hip")
+    cmd = [build._hipcc(), "-x", "hip", "--cuda-device-only", "-c", src, "-o", str(tmp_path / "osdl.o")] + build.FLAGS + [
+        "-Rpass-analysis=kernel-resource-usage"]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-2000:]
+    res = {}
+    for blk in p.stderr.split("Function Name: ")[1:]:
+        sym = blk.split()[0]
+        num = lambda key: int(re.search(key + r"[^:]*: (\d+)", blk).group(1))      # noqa: E731
+        res[sym] = (num("VGPRs"), num("LDS Size"), num("ScratchSize"))
+    readme = open(os.path.join(ROOT, "profiles", "osdl", "README.md")).read()
+    for s, w in FRONTS:
+        (sym,) = [k for k in res if f"osdl_front_kernelILi{s}ELi{w}E" in k]
+        vgprs, lds, scratch = res[sym]
+        print(f"osdl_front_kernel<{s},{w}>: {vgprs} VGPRs, {lds} B LDS, {scratch} B scratch")
+        assert scratch == 0 and vgprs <= 128 and lds <= 65536, (s, w, res[sym])
+        assert f"| `osdl_front_kernel<{s},{w}>` | {vgprs} | {lds} | {scratch} |" in readme
+    for wp in (1, 2, 3):
+        (sym,) = [k for k in res if f"osdl_search_kernelILi{wp}E" in k]
+        vgprs, lds, scratch = res[sym]
+        print(f"osdl_search_kernel<{wp}>: {vgprs} VGPRs, {lds} B LDS, {scratch} B scratch")
+        assert scratch == 0 and lds <= 65536, (wp, res[sym])
+        assert f"| `osdl_search_kernel<{wp}>` | {vgprs} | {lds} | {scratch} |" in readme
+    assert len(res) == len(FRONTS) + 3
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the TEP table of the largest k
+# ---------------------------------------------------------------------------------------------------------------------
+def test_order3_table_of_k_192():
+    L = _lib.load()
+    bounds = (C.c_int64 * 4)()
+    total = L.ldpc_tep_table(192, 3, None, bounds)
+    assert total == 1 + 192 + 18336 + 1161280 == 1179809
+    assert list(bounds) == [1, 193, 18529, 1179809]
+    sup = np.zeros((total, 3), np.uint8)
+    assert L.ldpc_tep_table(192, 3, sup.ctypes.data_as(C.POINTER(C.c_uint8)), None) == total
+    w = (sup != 0xFF).sum(axis=1)
+    assert np.array_equal(np.flatnonzero(np.diff(w)) + 1, [1, 193, 18529])          # the weight classes, back to back
+    assert int(sup[w == 3].max()) == 191 and np.all(sup[w == 3][:, 0] < sup[w == 3][:, 1]) and np.all(sup[w == 3][:, 1] < sup[w == 3][:, 2])
+    # inside a class: descending index sum
+    tot = np.where(sup == 0xFF, 0, sup).astype(np.int64).sum(axis=1)
+    for lo, hi in ((1, 193), (193, 18529), (18529, total)):
+        assert np.all(np.diff(tot[lo:hi]) <= 0)
+
+
+def test_order2_table_of_k_192_equals_the_oracle():
+    L = _lib.load()
+    want = np_oracle.tep_table(192, 2)
+    assert len(want) == 18529
+    sup = np.zeros((len(want), 3), np.uint8)
+    assert L.ldpc_tep_table(192, 2, sup.ctypes.data_as(C.POINTER(C.c_uint8)), None) == len(want)
+    assert [tuple(int(v) for v in row if v != 0xFF) for row in sup] == want
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the codes
+# ---------------------------------------------------------------------------------------------------------------------
+def test_wl384_code():
+    assert os.path.getsize(osdl_model.WL384) == 12786
+    code = Code(osdl_model.WL384)
+    ref = np_oracle.Code(osdl_model.WL384)
+    assert (code.check_matrix_column, code.check_matrix_row, code.k) == (384, 192, 192)
+    G, H = np.asarray(code.G), np.asarray(code.H)
+    assert np.array_equal(G, ref.G) and np.array_equal(H, ref.H)
+    assert not (H.dot(G.T) % 2).any()
+    assert int(H.sum(axis=1).max()) <= 7 and int(H.sum(axis=0).max()) <= 6
+
+
+def test_shapes_of_the_codes():
+    want = {"wl384": (384, 192, 6, 3, 3), "s128_32": (128, 32, 2, 1, 2), "s100_20": (100, 20, 2, 1, 2),
+            "s200_100": (200, 100, 4, 2, 2), "s321_130": (321, 130, 6, 3, 3), "s193_1": (193, 1, 4, 1, 3),
+            "s256_192": (256, 192, 4, 3, 1), "ccsds": (128, 64, 2, 1, 1), "ldpc_96_48": (96, 48, 2, 1, 1),
+            "array_121_80": (121, 80, 2, 2, 1), "s128_96": (128, 96, 2, 2, 1)}
+    assert set(want) == set(osdl_model.SERVED)
+    for name, shp in want.items():
+        assert osdl_model.shape(name) == shp, name
+        assert osdl_model.served(*shp[:2]), name
+        # the codes no other OSD family serves are exactly the new ones
+        n, k = shp[:2]
+        old = (k <= 64 and n - k <= 64) or (n <= 128 and n - k <= 64)
+        assert old == (name in osdl_model.CROSS), name
+    for name in tuple(osdl_model.REFUSED) + ("wimax_1056",):
+        n, k = osdl_model.shape(name)[:2]
+        assert not osdl_model.served(n, k), name
+    assert [osdl_model.shape(r)[:2] for r in osdl_model.REFUSED] == [(385, 193), (384, 193), (384, 191)]
+    code = Code(H=osdl_model.graph("s385_193")[0])                    # the library builds the codes it will refuse to decode
+    assert (code.check_matrix_column, code.k) == (385, 193)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the model agrees with itself
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", osdl_model.NEW)
+def test_oracle_self_check(name):
+    assert osdl_model.self_check(name, order=1)
+
+
+def test_oracle_self_check_at_order_2_on_wl384():
+    assert osdl_model.self_check("wl384", order=2, frames_=1)
+
+
+@pytest.mark.parametrize("name", osdl_model.SERVED)
+def test_layouts_round_trip(name):
+    n, k, S, W, Wp = osdl_model.shape(name)
+    G = osdl_model.graph(name)[1]
+    y, _ = osdl_model.frames(name, 1.5, 3, 9)
+    perm, parity, ns, Gps = osdl_model.front_oracle(G, y)
+    assert perm.shape == (3, 64 * S) and perm.dtype == np.uint16 and parity.shape == (3, 64 * W, Wp) and parity.dtype == np.uint64
+    for f in range(3):
+        p, P = osdl_model.unpack_front(perm[f], parity[f], n, k)
+        assert sorted(p.tolist()) == list(range(n))
+        assert np.array_equal(P, Gps[f][:, k:])
+        again = osdl_model.pack_front(p, np.concatenate([np.eye(k, dtype=np.int64), P], axis=1))
+        assert np.array_equal(again[0], perm[f]) and np.array_equal(again[1], parity[f])
+        assert not perm[f, n:].any() and not parity[f, k:].any()
+        if (n - k) % 64:
+            assert not (parity[f, :, Wp - 1] >> np.uint64((n - k) % 64)).any()
+    # beside the older families the bytes are theirs: [64] words per frame where k, n-k <= 64, [128] where k > 64 and n-k <= 64
+    if name in osdl_model.CROSS:
+        assert parity[0].tobytes() == osdl_model.pack_rows(Gps[0][:, k:], 1).tobytes() + bytes(8 * (64 * W - k))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the premises of the GPU tests' inputs, read back from the C oracle's exchange records
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["wl384", "s321_130"])
+def test_front_end_inputs_cover_every_path(name):
+    n, k, S, W, _ = osdl_model.shape(name)
+    y, (perm, parity, ns, Gps, sws) = osdl_model.front_case(name)
+    cls = osdl_model.exchange_classes(k, S, ns, sws)
+    assert (S, W) == (6, 3)
+    assert cls["words"] == [0, 1, 2]                                  # an exchange at a pivot step in every row word
+    # A partner is a column with a 1 in the pivot step's logical row; that row is a non-zero codeword, and neither code has a
+    # codeword of weight 1 (no zero column in H), so two of its positions lie at or beyond the partner: a partner can sit at
+    # n - 2 at the most.  wl384: slot 5 = positions 320..383; s321_130: slot 5 is position 320 alone, out of a partner's reach.
+    assert not (osdl_model.graph(name)[0].sum(axis=0) == 0).any()
+    last = (n - 2) >> 6
+    assert last == {"wl384": 5, "s321_130": 4}[name]
+    assert cls["slots"] == list(range(last + 1))
+    for w in range(W):                                                # per row word: the pivot's own slot up to the last one
+        have = [s for (a, s) in cls["pairs"] if a == w]
+        assert w in have and max(have) >= (last if w == W - 1 else w + 1), (w, have)
+    assert all(s >= a for a, s in cls["pairs"])
+    assert cls["frames_0"] >= 1 and cls["frames_ge3"] >= 1 and cls["most"] >= 40
+    if name == "wl384":                                               # what the natural frames alone leave out
+        nat = osdl_model.exchange_classes(k, S, ns[:48], sws[:48])
+        assert nat["words"] == [1, 2] and max(nat["slots"]) == 3 and nat["frames_0"] == 0 and 1 <= int(ns[:48].min()) and nat["most"] == 49
+
+
+@pytest.mark.parametrize("name", osdl_model.SERVED)
+def test_awkward_frames_hold_ties_zeros_and_saturation(name):
+    y = osdl_model.awkward_frames(name)
+    a = np.abs(y)
+    assert (a[0] == 1.0).all() and (y[0] < 0).any() and (y[1] == 1.0).all()
+    assert (y[2, ::2] == 0).all() and (y[2, 1::2] != 0).all() and (y[3] == 0).all()
+    assert (a[4] == np.float32(3.0e38)).all() and (a[5] == np.float32(3.0e38)).sum() == 3
+    with np.errstate(over="ignore"):
+        assert np.float32(3.0e38) + np.float32(3.0e38) == np.inf      # two discrepancies overflow the metric
+    all_y, front = osdl_model.front_case(name)
+    assert np.array_equal(all_y[-6:], y)
