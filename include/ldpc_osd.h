@@ -557,9 +557,9 @@ int ldpc_osdw_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
 /* ---------------------------------------------------------------------------------------
  * OSD for longer and low-rate codes, i.e. every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192: the reference's
  * wimax-like (384,192) code and the codes with n <= 128 and n-k > 64, which the two families above refuse.  Served: the
- * front end and the conventional search (orders 0..3).  FS-OSD, PB-OSD, one-TEP evaluation, the H-form primitives and the
- * one-call pipeline are not served for these shapes; codes with n > 384, k > 192 or n-k > 192 -- wimax (1056,880) among
- * them -- are refused by every OSD entry point.
+ * front end, the conventional search (orders 0..3), FS-OSD (orders 0..min(3, k)) and one-TEP evaluation.  PB-OSD, the H-form
+ * primitives and the one-call pipeline are not served for these shapes; codes with n > 384, k > 192 or n-k > 192 -- wimax
+ * (1056,880) among them -- are refused by every OSD entry point.
  * The contract is that of ldpc_osdx_front / _search / _decode -- d_index / d_count read on the device and nothing written at
  * or beyond frame min(*d_count, F), ties of the sort to the lower index, the reference's pivot and exchange rule, the TEP
  * table of this code's k (orders 0..3, first minimum), the float order of the metric (flipped MRB weights ascending from
@@ -578,8 +578,23 @@ int ldpc_osdw_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
  * library workspace, no per-stream state.  Before any launch: an unsupported shape is LDPC_E_UNSUPPORTED (the message names
  * the limits n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192 and the code's (n,k)), an order outside 0..3 and a NULL in a
  * required pointer are LDPC_E_ARG (naming the entry point and the offender), F == 0 is LDPC_OK.  The tables (G columns as W
- * words each and the order-3 TEP table of k: 1 179 809 entries, 4.7 MB, at k = 192; the table another family keeps for this k
- * is shared) are uploaded by ldpc_ctx_create; nothing is allocated and nothing synchronises in a call (graph-capturable).
+ * words each, the order-3 TEP table of k: 1 179 809 entries, 4.7 MB, at k = 192, and the FS visit order of k: 1 179 808
+ * entries; the tables another family keeps for this k are shared) are uploaded by ldpc_ctx_create; nothing is allocated and
+ * nothing synchronises in a call (graph-capturable).
+ * ldpc_osdl_fs_search / _fs_decode / _tep_eval: the contract of ldpc_osdw_fs_search / _fs_decode / _tep_eval, word for word
+ * -- `params` read for order, algo, fs_beta, fs_tau_e, fs_tau_psc and fs_reference_quirk; the lower bound of weight w the
+ * sum of |y'| at positions k-w .. k-1 (ascending from 0.0f, in whichever words of the MRB they lie) plus
+ * (float)((double)fs_beta * (n-k)); d_best the rank in visit order (0 = the all-zero TEP), d_ntep num_teps; with
+ * fs_reference_quirk = 0 a tau_e stop returns the stopping candidate, its own metric and its rank; outputs nullable, each on
+ * its own; labels and counts as a pair or not at all; LDPC_E_ARG, naming the offender, for algo != LDPC_OSD_FS, an order
+ * outside 0..min(3, k), flags != 0, d_aux != NULL, y_frames != 0 and a NULL in a required pointer; LDPC_E_UNSUPPORTED with
+ * the limits above; F == 0 is LDPC_OK; ldpc_osdl_fs_decode is ldpc_osdl_front plus the scan, two launches -- with the
+ * layouts of ldpc_osdl_front and
+ *   d_mask    [F][W] u64 : bit p of word w flips MRB position 64 w + p; bits at or beyond k are ignored
+ *   d_metric  [F] f32 and d_hd [F] i32 of ldpc_osdl_tep_eval: nullable, each on its own; HD = the weight of the TEP plus the
+ *                          set bits of all Wp words of its parity discrepancy
+ * The metric's float order is that of ldpc_osdl_search.  For a code that ldpc_osdx_* or ldpc_osdw_* also serves every output
+ * equals that of their call of the same name bit for bit (d_mask: [F] beside ldpc_osdx_*, [F][2] beside ldpc_osdw_*).
  * ------------------------------------------------------------------------------------- */
 int ldpc_osdl_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
 int ldpc_osdl_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
@@ -590,6 +605,17 @@ int ldpc_osdl_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, co
 int ldpc_osdl_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
                      int32_t order, uint16_t *d_perm, uint64_t *d_parity, uint64_t *d_cw, float *d_metric,
                      int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits, int64_t *d_counts, void *stream);
+
+int ldpc_osdl_fs_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const uint16_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *params, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, void *stream);
+int ldpc_osdl_fs_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const ldpc_osd_params *params, uint16_t *d_perm, uint64_t *d_parity, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits,
+                        int64_t *d_counts, void *stream);
+int ldpc_osdl_tep_eval(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                       const uint16_t *d_perm, const uint64_t *d_parity, const uint64_t *d_mask, uint64_t *d_cw,
+                       float *d_metric, int32_t *d_hd, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H; other shapes: ldpc_hosdx_* below):

@@ -30,8 +30,11 @@ same run, alternating with the osdx kernels, the --osd fs run times osdw_fs_kern
 --osd pb run osdw_pb_kernel alternating with osdx_pb_kernel.
 A code that neither older family serves and ldpc_osdl_* does (n <= 384, k <= 192, n-k <= 192, e.g.
 tests/golden/wimaxlike_N384_K192_P16_set0.alist, or any code with n <= 128 and n-k > 64) runs the conventional search through
-ldpc_osdl_decode, osdl_front_kernel and osdl_search_kernel timed like the other legs; --osd fs and --osd pb are not served there.
-On a code that ldpc_osdw_* serves as well the conventional run also times the osdl kernels on the same frames, alternating.
+ldpc_osdl_decode, osdl_front_kernel and osdl_search_kernel timed like the other legs.  --osd fs runs ldpc_osdl_fs_decode there:
+the line of TEPs per frame, the FER of the conventional scan of the same order on the same frames next to it, and osdl_fs_kernel
+timed next to osdl_search_kernel; --osd pb is not served there.  On a code that ldpc_osdw_* serves as well the conventional run
+also times the osdl kernels on the same frames, alternating; on a code an older family serves the --osd fs run asserts that
+ldpc_osdl_fs_decode gives the same outputs and times osdl_fs_kernel alternating with the older family's FS kernel.
 --oracle N times the C oracle's front end (oracle/c_oracle.osd_front, one core) on the first N failures and prints its frames/s.
 --gen hip draws the frames with the library's counter-based generator (Decoder.gen_frames: frames 0 .. --frames - 1 of the set
 --seed, one launch) instead of the torch ops; the JSON line says which.
@@ -116,8 +119,8 @@ def main(argv=None):
     long_ = dec.osdl_supported and not dec.osdx_supported and not dec.osdw_supported     # n > 128 or n-k > 64: the long / low-rate family
     if not dec.osdx_supported and not dec.osdw_supported and not dec.osdl_supported:
         raise SystemExit(f"osdx_fer: the OSD kernels serve n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192; this code is ({dec.n},{dec.k})")
-    if long_ and (fs or pb):
-        raise SystemExit(f"osdx_fer: --osd {args.osd} serves n <= 128 and 1 <= n-k <= 64; ({dec.n},{dec.k}) has the conventional search only")
+    if long_ and pb:
+        raise SystemExit(f"osdx_fer: --osd pb serves n <= 128 and 1 <= n-k <= 64; ({dec.n},{dec.k}) has the conventional search and FS-OSD only")
     B = args.frames
     y, labels = dec.gen_frames(B, seed=args.seed, snr_db=args.snr) if args.gen == "hip" else make_frames(dec, B, args.seed, args.snr)
     res = dec.nms(y, args.T, args.alpha)
@@ -129,7 +132,7 @@ def main(argv=None):
     counts = torch.zeros(3, dtype=torch.int64, device=dec.device)
     if fs:
         fsp = dec.osd_params(args.order, _lib.OSD_FS, fs_beta=args.beta, fs_tau_e=args.tau_e, fs_tau_psc=args.tau_psc)
-        fs_decode = dec.osdw_fs_decode if wide else dec.osdx_fs_decode
+        fs_decode = dec.osdw_fs_decode if wide else dec.osdl_fs_decode if long_ else dec.osdx_fs_decode
         out = fs_decode(y, fsp, index=idx, count=count, label_bits=labels, counts=counts)
     elif pb:
         aux = torch.zeros((idx.shape[0], 4), dtype=torch.int32, device=dec.device)
@@ -159,9 +162,9 @@ def main(argv=None):
         print(f"  order-{args.order} FS-OSD (beta {args.beta}, tau_e {args.tau_e}, tau_psc {args.tau_psc}) on the {nf} failures: FER {fer_osd:.3e} "
               f"({oc[1]} still wrong); TEPs per frame: mean {mean:.1f}, max {most}, table {table}", flush=True)
         result.update(osd="fs", beta=args.beta, tau_e=args.tau_e, tau_psc=args.tau_psc, teps_mean=mean, teps_max=most, teps_table=table)
-        if wide:                                             # the full scan of the same order on the same frames
+        if wide or long_:                                    # the full scan of the same order on the same frames
             cc = torch.zeros(3, dtype=torch.int64, device=dec.device)
-            outc = dec.osdw_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=cc)
+            outc = (dec.osdw_decode if wide else dec.osdl_decode)(y, args.order, index=idx, count=count, label_bits=labels, counts=cc)
             torch.cuda.synchronize()
             fer_conv = (nc[3] + cc.cpu().tolist()[1]) / B
             print(f"  order-{args.order} conventional scan on the same failures: FER {fer_conv:.3e} ({cc.cpu().tolist()[1]} still wrong, "
@@ -207,6 +210,9 @@ def main(argv=None):
     if fs and wide:
         legs[1] = ("osdw_fs_kernel", lambda: dec.osdw_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out))
         legs.append(("osdw_search_kernel", lambda: dec.osdw_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=outc)))
+    elif fs and long_:
+        legs[1] = ("osdl_fs_kernel", lambda: dec.osdl_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out))
+        legs.append(("osdl_search_kernel", lambda: dec.osdl_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=outc)))
     elif fs:
         legs[1] = ("osdx_fs_kernel", lambda: dec.osdx_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=out))
         if dec.osdw_supported:                           # both families serve the code: osdw_fs_kernel on the same frames
@@ -240,6 +246,11 @@ def main(argv=None):
         out2 = dec.osd_search(y, perm2, par2, p, index=idx, count=count)
         legs += [("osd_front_kernel", lambda: dec.osd_front(y, index=idx, count=count, out=(perm2, par2, ns2))),
                  ("osd_search_kernel(table)", lambda: dec.osd_search(y, perm2, par2, p, index=idx, count=count, out=out2))]
+    if fs and not long_ and dec.osdl_supported:            # an older family serves the code: osdl_fs_kernel on the same frames, alternating
+        outl = dec.osdl_fs_decode(y, fsp, index=idx, count=count)
+        for key in ("cw", "metric", "best", "ntep"):
+            assert torch.equal(outl[key][:nf], out[key][:nf]), key
+        legs_l = [("osdl_fs_kernel", lambda: dec.osdl_fs_search(y, outl["perm"], outl["parity"], fsp, index=idx, count=count, out=outl))]
     legs += legs_l
     if args.oracle > 0:
         import time

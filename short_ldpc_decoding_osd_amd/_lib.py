@@ -27,6 +27,7 @@ SYMBOLS = (
     "ldpc_osdw_supported", "ldpc_osdw_front", "ldpc_osdw_search", "ldpc_osdw_decode",
     "ldpc_osdw_fs_search", "ldpc_osdw_fs_decode", "ldpc_osdw_tep_eval", "ldpc_osdw_pb_search", "ldpc_osdw_pb_decode",
     "ldpc_osdl_supported", "ldpc_osdl_front", "ldpc_osdl_search", "ldpc_osdl_decode",
+    "ldpc_osdl_fs_search", "ldpc_osdl_fs_decode", "ldpc_osdl_tep_eval",
     "ldpc_hosd_pattern_teps", "ldpc_hosd_front", "ldpc_hosd_search", "ldpc_hosd_sliding",
     "ldpc_hosdx_supported", "ldpc_hosdx_front", "ldpc_hosdx_search", "ldpc_hosdx_sliding",
     "ldpc_hosdw_supported", "ldpc_hosdw_front", "ldpc_hosdw_search", "ldpc_hosdw_sliding", "ldpc_dia_cnn", "ldpc_dia_cnn_grad",
@@ -162,8 +163,8 @@ def load():
             f"ldpc_{fam}_pb_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
             f"ldpc_{fam}_pb_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         })
-    # the long / low-rate family has the front end and the conventional scan, under the signatures of the other two
-    for op in ("supported", "front", "search", "decode"):
+    # the long / low-rate family has all of these but PB-OSD, under the signatures of the other two
+    for op in ("supported", "front", "search", "decode", "fs_search", "fs_decode", "tep_eval"):
         sig[f"ldpc_osdl_{op}"] = sig[f"ldpc_osdx_{op}"]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError here = ABI/header drift, which must be loud

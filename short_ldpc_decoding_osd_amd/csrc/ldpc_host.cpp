@@ -352,6 +352,10 @@ int pack_osdl_tables(const ldpc_code &c, const OsdwTables &base, OsdlTables &t, 
         if ((total = tep_table(c.k, 3, sup.data(), nullptr)) < 0) return (int)total;
         host.tep.reserve((size_t)total);
         pack_supports(sup, host.tep);
+        host.tep_fs.reserve((size_t)total);
+        if (int rc = pack_fs_table(c.k, host.tep_fs, t.fs_off, t.fs_cnt)) return rc;
+    } else {
+        for (int w = 0; w < 4; ++w) { t.fs_off[w] = base.fs_off[w]; t.fs_cnt[w] = base.fs_cnt[w]; }
     }
     t.n = c.n; t.k = c.k;
     return LDPC_OK;

@@ -9,7 +9,7 @@
 //                                   d_parity follow from n and k inside the kernels
 //   front(t), search(t)             its front-end and scan kernels for the shape of the tables t (one kernel in the first two
 //                                   families, an instantiation per shape class in the third); the same argument lists in all
-//   fs, tep_eval                    its FS-OSD and one-TEP kernels (the first two families)
+//   fs(t), tep_eval(t)              its FS-OSD and one-TEP kernels, likewise
 // `who` is the name of the extern "C" entry point, for the error texts.
 // There is no library workspace: the decode entry points run their two launches through the caller's d_perm / d_parity, so the
 // calls hold no per-stream state, allocate nothing and are graph-capturable as they are.
@@ -84,11 +84,11 @@ int family_launch_search(const ldpc_ctx *ctx, const OsdFrames &fr, const typenam
 }
 
 template <class FAM>
-int family_launch_fs(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *p,
-                     const OsdScanOut &o, OsdCounting c, hipStream_t s)
+int family_launch_fs(const ldpc_ctx *ctx, const OsdFrames &fr, const typename FAM::perm_t *d_perm, const uint64_t *d_parity,
+                     const ldpc_osd_params *p, const OsdScanOut &o, OsdCounting c, hipStream_t s)
 {
     const auto &t = FAM::tables(ctx);
-    hipLaunchKernelGGL(FAM::fs, dim3(frame_grid(fr.F)), dim3(64), 0, s, fr.y, fr.index, fr.count, (long long)fr.F, t.n, t.k, d_perm,
+    hipLaunchKernelGGL(FAM::fs(t), dim3(frame_grid(fr.F)), dim3(64), 0, s, fr.y, fr.index, fr.count, (long long)fr.F, t.n, t.k, d_perm,
                        reinterpret_cast<const u64 *>(d_parity), t.d_tep_fs, fs_params(p, t.n, t.k, t.fs_off, t.fs_cnt),
                        reinterpret_cast<u64 *>(o.cw), o.metric, o.best, o.ntep, c.label, c.counts);
     LDPC_HIP(hipGetLastError());
@@ -127,20 +127,23 @@ int family_decode(ldpc_ctx *ctx, const OsdFrames &fr, int32_t order, typename FA
     return family_launch_search<FAM>(ctx, fr, d_perm, d_parity, order, o, c, (hipStream_t)stream);
 }
 
-// A scan that takes ldpc_osd_params (FS-OSD and PB-OSD in both families; each family launches its own PB kernel): what its entry points check and launch
+// A scan that takes ldpc_osd_params (FS-OSD in every family, PB-OSD in the first two; each family launches its own PB kernel):
+// what its entry points check and launch.  PERM: the family's perm_t.
+template <class PERM>
 struct OsdScan {
     int algo;
     const char *algo_name;
     bool aux_allowed;   // the scan writes params->d_aux
-    int (*launch)(const ldpc_ctx *, const OsdFrames &, const uint8_t *, const uint64_t *, const ldpc_osd_params *, const OsdScanOut &,
+    int (*launch)(const ldpc_ctx *, const OsdFrames &, const PERM *, const uint64_t *, const ldpc_osd_params *, const OsdScanOut &,
                   OsdCounting, hipStream_t);
 };
 template <class FAM>
-constexpr OsdScan fs_scan{LDPC_OSD_FS, "LDPC_OSD_FS", false, family_launch_fs<FAM>};
+constexpr OsdScan<typename FAM::perm_t> fs_scan{LDPC_OSD_FS, "LDPC_OSD_FS", false, family_launch_fs<FAM>};
 
 // the params of the entry points of `scan` for a code with k information bits: its algorithm, an order up to min(3, k), and
 // nothing that only ldpc_osd_search / ldpc_osd_decode serve
-inline int check_scan_params(int k, const ldpc_osd_params *p, const OsdScan &scan, const char *who)
+template <class PERM>
+int check_scan_params(int k, const ldpc_osd_params *p, const OsdScan<PERM> &scan, const char *who)
 {
     if (!p) return fail(LDPC_E_ARG, "%s: params is NULL", who);
     if (p->algo != scan.algo) return fail(LDPC_E_ARG, "%s: algo %d is not %s", who, p->algo, scan.algo_name);
@@ -153,8 +156,8 @@ inline int check_scan_params(int k, const ldpc_osd_params *p, const OsdScan &sca
 }
 
 template <class FAM>
-int family_scan_search(ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *params,
-                       const OsdScan &scan, const OsdScanOut &o, void *stream, const char *who)
+int family_scan_search(ldpc_ctx *ctx, const OsdFrames &fr, const typename FAM::perm_t *d_perm, const uint64_t *d_parity,
+                       const ldpc_osd_params *params, const OsdScan<typename FAM::perm_t> &scan, const OsdScanOut &o, void *stream, const char *who)
 {
     if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
     if (int rc = check_scan_params(FAM::tables(ctx).k, params, scan, who)) return rc;
@@ -164,8 +167,8 @@ int family_scan_search(ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm
 }
 
 template <class FAM>
-int family_scan_decode(ldpc_ctx *ctx, const OsdFrames &fr, const ldpc_osd_params *params, const OsdScan &scan, uint8_t *d_perm,
-                       uint64_t *d_parity, const OsdScanOut &o, OsdCounting c, void *stream, const char *who)
+int family_scan_decode(ldpc_ctx *ctx, const OsdFrames &fr, const ldpc_osd_params *params, const OsdScan<typename FAM::perm_t> &scan,
+                       typename FAM::perm_t *d_perm, uint64_t *d_parity, const OsdScanOut &o, OsdCounting c, void *stream, const char *who)
 {
     if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
     if (int rc = check_scan_params(FAM::tables(ctx).k, params, scan, who)) return rc;
@@ -176,14 +179,14 @@ int family_scan_decode(ldpc_ctx *ctx, const OsdFrames &fr, const ldpc_osd_params
 }
 
 template <class FAM>
-int family_tep_eval(ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const uint64_t *d_mask,
+int family_tep_eval(ldpc_ctx *ctx, const OsdFrames &fr, const typename FAM::perm_t *d_perm, const uint64_t *d_parity, const uint64_t *d_mask,
                     uint64_t *d_cw, float *d_metric, int32_t *d_hd, void *stream, const char *who)
 {
     if (int rc = family_open<FAM>(ctx, fr.F, who)) return rc;
     if (fr.F == 0) return LDPC_OK;
     if (int rc = first_null(who, {{"d_y", fr.y}, {"d_perm", d_perm}, {"d_parity", d_parity}, {"d_mask", d_mask}, {"d_cw", d_cw}})) return rc;
     const auto &t = FAM::tables(ctx);
-    hipLaunchKernelGGL(FAM::tep_eval, dim3(frame_grid(fr.F)), dim3(64), 0, (hipStream_t)stream, fr.y, fr.index, fr.count, (long long)fr.F,
+    hipLaunchKernelGGL(FAM::tep_eval(t), dim3(frame_grid(fr.F)), dim3(64), 0, (hipStream_t)stream, fr.y, fr.index, fr.count, (long long)fr.F,
                        t.n, t.k, d_perm, reinterpret_cast<const u64 *>(d_parity), reinterpret_cast<const u64 *>(d_mask),
                        reinterpret_cast<u64 *>(d_cw), d_metric, d_hd);
     LDPC_HIP(hipGetLastError());

@@ -65,27 +65,31 @@ struct OsdwTablesHost {
 int pack_osdw_tables(const ldpc_code &c, const OsdTables &base, OsdwTables &t, OsdwTablesHost &host);
 
 // The tables of the long / low-rate family (ldpc_osdl.hip): every code with n <= 384, 1 <= k <= 192 and 1 <= n - k <= 192.  A
-// member of its own in the context, as OsdwTables is; it holds the conventional scan's table only (no FS order, no PB constants).
+// member of its own in the context, as OsdwTables is; it holds the tables of the conventional scan and of FS-OSD (no PB constants).
 struct OsdlTables {
     int n = 0, k = 0;            // the shape the tables were built for; k = 0: no tables (ldpc_osdl_* report UNSUPPORTED)
     u64 *d_Gcols = nullptr;      // [n][W] column v of G as W = ceil(k / 64) words: bit r of word w = G[64 w + r][v]
     uchar4 *d_tep = nullptr;     // conventional order-3 TEP table of this k; where OsdwTables serves the code it IS OsdwTables::d_tep
-    bool own_tep = false;        // d_tep was allocated for this member and is freed with it
+    bool own_tep = false;        // d_tep and d_tep_fs were allocated for this member and are freed with it
     int64_t ntep[4] = {0, 0, 0, 0};
+    uchar4 *d_tep_fs = nullptr;  // FS-OSD visit order of this k, weight classes 1..min(3, k) back to back; where OsdwTables serves the code it IS OsdwTables::d_tep_fs
+    int fs_off[4] = {0, 0, 0, 0}, fs_cnt[4] = {0, 0, 0, 0};   // weight class w: offset / count inside d_tep_fs
 };
 
 struct OsdlTablesHost {
     std::vector<u64> Gcols;      // [n][W]
     std::vector<uchar4> tep;     // filled only where `base` has no table of this k (1 179 809 entries, 4.7 MB, at k = 192)
+    std::vector<uchar4> tep_fs;  // likewise (1 179 808 entries, 4.7 MB, at k = 192)
 };
 
-// For a code with n <= 384, 1 <= k <= 192, 1 <= n - k <= 192 and G = [k][n]: fills `host` and the shape and boundaries of `t`
-// (never a device pointer; t.own_tep tells whether host.tep was filled).  `base`: the OsdwTables already packed for the same
-// code.  Any other code leaves t.k = 0.  LDPC_OK, or the error of tep_table.  Pure host code (ldpc_host.cpp).
+// For a code with n <= 384, 1 <= k <= 192, 1 <= n - k <= 192 and G = [k][n]: fills `host` and the shape, boundaries, offsets and
+// counts of `t` (never a device pointer; t.own_tep tells whether host.tep and host.tep_fs were filled).  `base`: the OsdwTables
+// already packed for the same code.  Any other code leaves t.k = 0.  LDPC_OK, or the error of tep_table / tep_table_fs.  Pure
+// host code (ldpc_host.cpp).
 int pack_osdl_tables(const ldpc_code &c, const OsdwTables &base, OsdlTables &t, OsdlTablesHost &host);
 
-// The kernel argument of osd_fs_kernel / osdx_fs_kernel / osdw_fs_kernel (FsParams: ldpc_search.h) from the caller's parameters
-// and the shape, class offsets and class counts of the context's FS table (OsdTables or OsdwTables: fs_off / fs_cnt);
+// The kernel argument of osd_fs_kernel / osdx_fs_kernel / osdw_fs_kernel / osdl_fs_kernel (FsParams: ldpc_search.h) from the
+// caller's parameters and the shape, class offsets and class counts of the context's FS table (OsdTables, OsdwTables or OsdlTables: fs_off / fs_cnt);
 // beta_term = (float)((double)fs_beta * (double)(n - k)) (fs_testing.py:138).  Defined in ldpc_osd.hip.
 struct FsParams;
 FsParams fs_params(const ldpc_osd_params *p, int n, int k, const int (&fs_off)[4], const int (&fs_cnt)[4]);

@@ -1,35 +1,31 @@
 // OSD for longer and low-rate codes: the ldpc_osdl_* entry points.
 // For every code with n <= 384, 1 <= k <= 192 and 1 <= n - k <= 192: the front end and the conventional order-p scan (device
-// code: ldpc_osdl.h).  FS-OSD, PB-OSD, the one-TEP primitive and the one-call pipeline stay with the families of ldpc_osdx.hip /
-// ldpc_osdw.hip and with the (128,64) kernels.
-// The W-word G columns and the TEP table of k are the context's OsdlTables (ldpc_osd_tables.h), uploaded by ldpc_ctx_create.
+// code: ldpc_osdl.h).  FS-OSD and the one-TEP primitive of the family are in ldpc_osdl_fs.hip; PB-OSD and the one-call pipeline
+// stay with the families of ldpc_osdx.hip / ldpc_osdw.hip and with the (128,64) kernels.
+// The W-word G columns and the TEP tables of k are the context's OsdlTables (ldpc_osd_tables.h), uploaded by ldpc_ctx_create.
 // Validation, launches and the bodies of the entry points are those of ldpc_osd_family.h, shared with ldpc_osdx.hip and
-// ldpc_osdw.hip; this family's d_perm is uint16_t and its kernels are instantiations chosen by the shape.
-#include "ldpc_osdl.h"
-#include "ldpc_osd_family.h"
+// ldpc_osdw.hip; this family's d_perm is uint16_t and its kernels are instantiations chosen by the shape (ldpc_osdl_family.h).
+#include "ldpc_osdl_family.h"
 
 namespace ldpc {
 
-struct Osdl {
-    using perm_t = uint16_t;
-    static const OsdlTables &tables(const ldpc_ctx *ctx) { return ctx->osdl_tables; }
-    static constexpr const char *needs = "the long / low-rate OSD kernels need n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192";
-    // the front end for S = ceil(n / 64) rounded up to 2, 4 or 6 slots and W = ceil(k / 64) row words
-    template <int S>
-    static auto front_w(int W) { return W == 1 ? osdl_front_kernel<S, 1> : W == 2 ? osdl_front_kernel<S, 2> : osdl_front_kernel<S, 3>; }
-    static auto front(const OsdlTables &t)
-    {
-        const int S = (t.n + 63) / 64, W = (t.k + 63) / 64;
-        // (two slots hold k <= 127: W = 3 starts at four)
-        return S <= 2 ? (W == 1 ? osdl_front_kernel<2, 1> : osdl_front_kernel<2, 2>) : S <= 4 ? front_w<4>(W) : front_w<6>(W);
-    }
-    // the scan for Wp = ceil((n - k) / 64) words of discrepancy
-    static auto search(const OsdlTables &t)
-    {
-        const int Wp = (t.n - t.k + 63) / 64;
-        return Wp == 1 ? osdl_search_kernel<1> : Wp == 2 ? osdl_search_kernel<2> : osdl_search_kernel<3>;
-    }
-};
+// the front end for S = ceil(n / 64) rounded up to 2, 4 or 6 slots and W = ceil(k / 64) row words
+template <int S>
+static Osdl::front_fn osdl_front_w(int W) { return W == 1 ? osdl_front_kernel<S, 1> : W == 2 ? osdl_front_kernel<S, 2> : osdl_front_kernel<S, 3>; }
+
+Osdl::front_fn Osdl::front(const OsdlTables &t)
+{
+    const int S = (t.n + 63) / 64, W = (t.k + 63) / 64;
+    // (two slots hold k <= 127: W = 3 starts at four)
+    return S <= 2 ? (W == 1 ? osdl_front_kernel<2, 1> : osdl_front_kernel<2, 2>) : S <= 4 ? osdl_front_w<4>(W) : osdl_front_w<6>(W);
+}
+
+// the scan for Wp = ceil((n - k) / 64) words of discrepancy
+Osdl::search_fn Osdl::search(const OsdlTables &t)
+{
+    const int Wp = (t.n - t.k + 63) / 64;
+    return Wp == 1 ? osdl_search_kernel<1> : Wp == 2 ? osdl_search_kernel<2> : osdl_search_kernel<3>;
+}
 
 }  // namespace ldpc
 

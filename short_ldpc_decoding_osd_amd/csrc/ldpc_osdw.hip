@@ -19,8 +19,8 @@ struct Osdw {
     using perm_t = uint8_t;
     static constexpr auto front(const OsdwTables &) { return osdw_front_kernel; }
     static constexpr auto search(const OsdwTables &) { return osdw_search_kernel; }
-    static constexpr auto fs = osdw_fs_kernel;
-    static constexpr auto tep_eval = osdw_tep_eval_kernel;
+    static constexpr auto fs(const OsdwTables &) { return osdw_fs_kernel; }
+    static constexpr auto tep_eval(const OsdwTables &) { return osdw_tep_eval_kernel; }
 };
 
 static int osdw_launch_pb(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *p,
@@ -44,7 +44,7 @@ static int osdw_launch_pb(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
 }
-constexpr OsdScan osdw_pb_scan{LDPC_OSD_PB, "LDPC_OSD_PB", true, osdw_launch_pb};
+constexpr OsdScan<uint8_t> osdw_pb_scan{LDPC_OSD_PB, "LDPC_OSD_PB", true, osdw_launch_pb};
 
 }  // namespace ldpc
 

@@ -19,8 +19,8 @@ struct Osdx {
     using perm_t = uint8_t;
     static constexpr auto front(const OsdTables &) { return osdx_front_kernel; }
     static constexpr auto search(const OsdTables &) { return osdx_search_kernel; }
-    static constexpr auto fs = osdx_fs_kernel;
-    static constexpr auto tep_eval = osdx_tep_eval_kernel;
+    static constexpr auto fs(const OsdTables &) { return osdx_fs_kernel; }
+    static constexpr auto tep_eval(const OsdTables &) { return osdx_tep_eval_kernel; }
 };
 
 static int osdx_launch_pb(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *p,
@@ -39,7 +39,7 @@ static int osdx_launch_pb(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
 }
-constexpr OsdScan osdx_pb_scan{LDPC_OSD_PB, "LDPC_OSD_PB", true, osdx_launch_pb};
+constexpr OsdScan<uint8_t> osdx_pb_scan{LDPC_OSD_PB, "LDPC_OSD_PB", true, osdx_launch_pb};
 
 }  // namespace ldpc
 

@@ -88,13 +88,13 @@ class Decoder:
     _OSD_MASK_TAIL = {"osd": (), "osdx": (), "osdw": (2,)}
 
     def _osd_layout(self, fam):
-        """(dtype of ``perm``, shape tail of ``perm``, shape tail of ``parity``) of the family on this code.  ``osdl``: perm
-        [*, 64 ceil(n/64)] int16 (the library's u16), parity [*, 64 ceil(k/64)] int64 with one word per row, or
-        [*, 64 ceil(k/64), ceil((n-k)/64)] with more."""
+        """(dtype of ``perm``, shape tail of ``perm``, shape tail of ``parity``, shape tail of a ``tep_eval`` mask) of the family
+        on this code.  ``osdl``: perm [*, 64 ceil(n/64)] int16 (the library's u16), parity [*, 64 ceil(k/64)] int64 with one
+        word per row, or [*, 64 ceil(k/64), ceil((n-k)/64)] with more, mask [*, ceil(k/64)]."""
         if fam != "osdl":
-            return torch.uint8, (128,), (self._OSD_PARITY_WORDS[fam],)
-        rows, wp = 64 * ((self.k + 63) // 64), (self.n - self.k + 63) // 64
-        return torch.int16, (64 * self.words,), ((rows,) if wp == 1 else (rows, wp))
+            return torch.uint8, (128,), (self._OSD_PARITY_WORDS[fam],), self._OSD_MASK_TAIL[fam]
+        w, wp = (self.k + 63) // 64, (self.n - self.k + 63) // 64
+        return torch.int16, (64 * self.words,), ((64 * w,) if wp == 1 else (64 * w, wp)), (w,)
 
     def _osd_call(self, fam, op, *args):
         """``ldpc_<fam>_<op>(ctx, *args, stream)``, checked."""
@@ -104,7 +104,7 @@ class Decoder:
     def _osd_front_results(self, fam, y, perm, parity, F=None):
         """The checks of the calls that take front-end results (perm and parity in the layouts of ``_osd_layout``).  Returns F."""
         self._chk(y, torch.float32, (self.n,), "y")
-        pdt, ptail, qtail = self._osd_layout(fam)
+        pdt, ptail, qtail, _ = self._osd_layout(fam)
         self._chk(perm, pdt, ptail, "perm")
         self._chk(parity, torch.int64, qtail, "parity")
         return perm.shape[0] if F is None else F
@@ -115,7 +115,7 @@ class Decoder:
         if out is not None:
             perm, parity, ns = out
         else:
-            pdt, ptail, qtail = self._osd_layout(fam)
+            pdt, ptail, qtail, _ = self._osd_layout(fam)
             perm = self.empty((F,) + ptail, pdt)
             parity = self.empty((F,) + qtail, torch.int64)
             ns = self.empty((F,), torch.int32)
@@ -125,7 +125,7 @@ class Decoder:
     def _osd_tep_eval(self, fam, y, perm, parity, mask, index, count):
         """``<fam>_tep_eval``.  The kernel reads a mask row for every frame, so a shorter mask is refused here."""
         F = self._osd_front_results(fam, y, perm, parity)
-        self._chk(mask, torch.int64, self._OSD_MASK_TAIL[fam], "mask")
+        self._chk(mask, torch.int64, self._osd_layout(fam)[3], "mask")
         if mask.shape[0] < F:
             raise ValueError(f"mask: {mask.shape[0]} rows for {F} frames")
         out = dict(cw=self.empty((F, self.words), torch.int64), metric=self.empty((F,), torch.float32), hd=self.empty((F,), torch.int32))
@@ -146,7 +146,7 @@ class Decoder:
         """``<fam>_<op>`` for the ``*decode`` calls: front end + scan through ``perm`` / ``parity``, which are checked when
         given, allocated when not, and returned in the dict.  F by the rule of ``_osd_frames``; ``arg`` as in ``_osd_search``."""
         F = self._osd_frames(y, index, F)
-        pdt, ptail, qtail = self._osd_layout(fam)
+        pdt, ptail, qtail, _ = self._osd_layout(fam)
         perm = self.empty((F,) + ptail, pdt) if perm is None else self._chk(perm, pdt, ptail, "perm")
         parity = self.empty((F,) + qtail, torch.int64) if parity is None else self._chk(parity, torch.int64, qtail, "parity")
         out = self._osd_outputs(out, F)
@@ -491,6 +491,23 @@ class Decoder:
         order-``order`` search, two launches through ``perm`` / ``parity`` in the layouts of ``osdl_front`` (allocated when
         not given; returned in the dict); ``label_bits`` / ``counts`` as there."""
         return self._osd_decode("osdl", "decode", y, int(order), index, count, F, perm, parity, label_bits, counts, out)
+
+    def osdl_fs_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
+        """``osdx_fs_search`` for every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192, on the results of
+        ``osdl_front`` (its layouts)."""
+        return self._osd_search("osdl", "fs_search", y, perm, parity, C.byref(params), index, count, F, out)
+
+    def osdl_fs_decode(self, y, params, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
+                       out=None):
+        """``osdx_fs_decode`` for every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192: ``osdl_decode`` with the
+        search of ``osdl_fs_search``; ``perm`` / ``parity`` in the layouts of ``osdl_front``, ``label_bits`` / ``counts`` as there."""
+        return self._osd_decode("osdl", "fs_decode", y, C.byref(params), index, count, F, perm, parity, label_bits, counts, out)
+
+    def osdl_tep_eval(self, y, perm, parity, mask, index=None, count=None):
+        """``osdx_tep_eval`` for every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192, on the results of ``osdl_front``.
+        mask [F, ceil(k/64)] int64: bit p of word w flips primed MRB position 64 w + p; bits at or beyond k are ignored.
+        Returns dict(cw[F,words] int64 original bit order, metric[F] f32, hd[F] i32)."""
+        return self._osd_tep_eval("osdl", y, perm, parity, mask, index, count)
 
     def osdx_fs_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
         """FS-OSD on front-end results of any supported shape.  ``params``: ``osd_params(order, _lib.OSD_FS, fs_beta=...,
