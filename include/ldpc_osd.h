@@ -92,6 +92,12 @@ int64_t ldpc_tep_table(int32_t k, int32_t order, uint8_t *supports, int64_t *bou
  * supports: [C(k,weight)][3] uint8 ascending positions, 0xFF padded (NULL = only the count).   */
 int64_t ldpc_tep_table_fs(int32_t k, int32_t weight, uint8_t *supports);
 
+/* The code-only constants of ldpc_osdl_pb_search / _pb_decode for a code with 1 <= k <= 192 and 1 <= n-k <= 192, as
+ * ldpc_ctx_create uploads them (host only): table[0..192] = P[Binomial(n-k, 1/2) <= b] by the float64 pmf recurrence (zero
+ * beyond n-k), table[193..384] = (n-k-i) / (i+1), table[385..448] = (k-i) / (i+1), i < 64.  Returns the number of entries,
+ * 449 (table may be NULL), or LDPC_E_ARG for another shape.                                            */
+int64_t ldpc_osdl_pb_table(int32_t n, int32_t k, double *table);
+
 /* CRC-32C of a host buffer: the record checksum of the TFRecord files the reference's stages
  * exchange (Ldpc_128_testing/data_generating.py:16-26, read_TFdata.py:18-29).                   */
 uint32_t ldpc_crc32c(const void *data, uint64_t len);
@@ -557,9 +563,10 @@ int ldpc_osdw_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
 /* ---------------------------------------------------------------------------------------
  * OSD for longer and low-rate codes, i.e. every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192: the reference's
  * wimax-like (384,192) code and the codes with n <= 128 and n-k > 64, which the two families above refuse.  Served: the
- * front end, the conventional search (orders 0..3), FS-OSD (orders 0..min(3, k)) and one-TEP evaluation.  PB-OSD, the H-form
- * primitives and the one-call pipeline are not served for these shapes; codes with n > 384, k > 192 or n-k > 192 -- wimax
- * (1056,880) among them -- are refused by every OSD entry point.
+ * front end, the conventional search (orders 0..3), FS-OSD and PB-OSD (orders 0..min(3, k)) and one-TEP evaluation.  The
+ * H-form primitives, the staged PB routes, ldpc_pb_tuning, the LDPC_OSD_F_PB_* flags and the one-call pipeline
+ * are not served for these shapes; codes with n > 384, k > 192 or n-k > 192 -- wimax (1056,880) among them -- are refused
+ * by every OSD entry point.
  * The contract is that of ldpc_osdx_front / _search / _decode -- d_index / d_count read on the device and nothing written at
  * or beyond frame min(*d_count, F), ties of the sort to the lower index, the reference's pivot and exchange rule, the TEP
  * table of this code's k (orders 0..3, first minimum), the float order of the metric (flipped MRB weights ascending from
@@ -595,6 +602,20 @@ int ldpc_osdw_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
  *                          set bits of all Wp words of its parity discrepancy
  * The metric's float order is that of ldpc_osdl_search.  For a code that ldpc_osdx_* or ldpc_osdw_* also serves every output
  * equals that of their call of the same name bit for bit (d_mask: [F] beside ldpc_osdx_*, [F][2] beside ldpc_osdw_*).
+ * ldpc_osdl_pb_search / _pb_decode: the contract of ldpc_osdw_pb_search / _pb_decode, word for word, in the layouts of
+ * ldpc_osdl_front -- `params` read for algo (LDPC_OSD_PB), order (0..min(3, k)), snr_db and d_aux ([F][4] i32, nullable:
+ * {frontier comparisons, suc1, suc2, stop reason}); d_best the rank of the winner in visit order (0 = the all-zero TEP), d_ntep
+ * the number of TEPs visited; outputs nullable, each on its own; labels and counts as a pair or not at all; nothing written at
+ * or beyond frame min(*d_count, F); LDPC_E_ARG, naming the entry point and the offender, for a wrong algo, an order out of
+ * range, flags != 0, y_frames != 0 or a NULL in a required pointer; LDPC_E_UNSUPPORTED with the limits above and the code's
+ * (n,k); F == 0 is LDPC_OK; ldpc_osdl_pb_decode is ldpc_osdl_front plus the scan, two launches through the caller's d_perm /
+ * d_parity, no workspace, no per-stream state, nothing allocated, nothing synchronised (graph-capturable).  The search is the
+ * literal replay of pb_osd that ldpc_osdw_pb_search is (first minimum of the frontier by sum and insertion order, extended
+ * child before adjacent child, the deterministic exp and the float64 CDF recurrences), with the four per-frame chains over up
+ * to 192 positions, beta clamped to n-k and the success product ascending over all n-k parity positions; its constants
+ * (cdfH[193] of n-k, the binomial ratios of n-k and k) are uploaded by ldpc_ctx_create.  For a code that ldpc_osdx_* or
+ * ldpc_osdw_* also serves every output, d_aux included, equals that of their call of the same name bit for bit; the older
+ * families stay the ones to call for their shapes.
  * ------------------------------------------------------------------------------------- */
 int ldpc_osdl_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
 int ldpc_osdl_front(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
@@ -616,6 +637,13 @@ int ldpc_osdl_fs_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
 int ldpc_osdl_tep_eval(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
                        const uint16_t *d_perm, const uint64_t *d_parity, const uint64_t *d_mask, uint64_t *d_cw,
                        float *d_metric, int32_t *d_hd, void *stream);
+int ldpc_osdl_pb_search(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const uint16_t *d_perm, const uint64_t *d_parity, const ldpc_osd_params *params, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, void *stream);
+int ldpc_osdl_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                        const ldpc_osd_params *params, uint16_t *d_perm, uint64_t *d_parity, uint64_t *d_cw,
+                        float *d_metric, int32_t *d_best, int32_t *d_ntep, const uint64_t *d_label_bits,
+                        int64_t *d_counts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * H-form OSD primitives for the DL-OSD stage (n = 128, m = k = 64, full-rank H; other shapes: ldpc_hosdx_* below):

@@ -32,9 +32,12 @@ A code that neither older family serves and ldpc_osdl_* does (n <= 384, k <= 192
 tests/golden/wimaxlike_N384_K192_P16_set0.alist, or any code with n <= 128 and n-k > 64) runs the conventional search through
 ldpc_osdl_decode, osdl_front_kernel and osdl_search_kernel timed like the other legs.  --osd fs runs ldpc_osdl_fs_decode there:
 the line of TEPs per frame, the FER of the conventional scan of the same order on the same frames next to it, and osdl_fs_kernel
-timed next to osdl_search_kernel; --osd pb is not served there.  On a code that ldpc_osdw_* serves as well the conventional run
-also times the osdl kernels on the same frames, alternating; on a code an older family serves the --osd fs run asserts that
-ldpc_osdl_fs_decode gives the same outputs and times osdl_fs_kernel alternating with the older family's FS kernel.
+timed next to osdl_search_kernel.  --osd pb runs ldpc_osdl_pb_decode there: the line of TEPs per frame next to N_max and the
+stop shares, osdl_pb_kernel timed next to osdl_search_kernel of the same order and, with --tau-e, osdl_fs_kernel on the same
+frames.  On a code that ldpc_osdw_* serves as well the conventional run also times the osdl kernels on the same frames,
+alternating; on a code an older family serves the --osd fs run asserts that ldpc_osdl_fs_decode gives the same outputs and
+times osdl_fs_kernel alternating with the older family's FS kernel, and the --osd pb run does the same with
+ldpc_osdl_pb_decode and osdl_pb_kernel.
 --oracle N times the C oracle's front end (oracle/c_oracle.osd_front, one core) on the first N failures and prints its frames/s.
 --gen hip draws the frames with the library's counter-based generator (Decoder.gen_frames: frames 0 .. --frames - 1 of the set
 --seed, one launch) instead of the torch ops; the JSON line says which.
@@ -119,8 +122,6 @@ def main(argv=None):
     long_ = dec.osdl_supported and not dec.osdx_supported and not dec.osdw_supported     # n > 128 or n-k > 64: the long / low-rate family
     if not dec.osdx_supported and not dec.osdw_supported and not dec.osdl_supported:
         raise SystemExit(f"osdx_fer: the OSD kernels serve n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192; this code is ({dec.n},{dec.k})")
-    if long_ and pb:
-        raise SystemExit(f"osdx_fer: --osd pb serves n <= 128 and 1 <= n-k <= 64; ({dec.n},{dec.k}) has the conventional search and FS-OSD only")
     B = args.frames
     y, labels = dec.gen_frames(B, seed=args.seed, snr_db=args.snr) if args.gen == "hip" else make_frames(dec, B, args.seed, args.snr)
     res = dec.nms(y, args.T, args.alpha)
@@ -137,7 +138,7 @@ def main(argv=None):
     elif pb:
         aux = torch.zeros((idx.shape[0], 4), dtype=torch.int32, device=dec.device)
         pbp = dec.osd_params(args.order, _lib.OSD_PB, snr_db=args.snr, aux=aux)
-        pb_decode = dec.osdw_pb_decode if wide else dec.osdx_pb_decode
+        pb_decode = dec.osdw_pb_decode if wide else dec.osdl_pb_decode if long_ else dec.osdx_pb_decode
         out = pb_decode(y, pbp, index=idx, count=count, label_bits=labels, counts=counts)
     elif wide:
         out = dec.osdw_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
@@ -229,6 +230,14 @@ def main(argv=None):
             fsp = dec.osd_params(args.order, _lib.OSD_FS, fs_beta=args.beta, fs_tau_e=args.tau_e, fs_tau_psc=args.tau_psc)
             outf = dec.osdw_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count)
             legs.append(("osdw_fs_kernel", lambda: dec.osdw_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=outf)))
+    elif pb and long_:
+        legs[1] = ("osdl_pb_kernel", lambda: dec.osdl_pb_search(y, out["perm"], out["parity"], pbp, index=idx, count=count, out=out))
+        outc = dec.osdl_search(y, out["perm"], out["parity"], args.order, index=idx, count=count)
+        legs.append(("osdl_search_kernel", lambda: dec.osdl_search(y, out["perm"], out["parity"], args.order, index=idx, count=count, out=outc)))
+        if args.tau_e is not None:                       # FS-OSD of the same order on the same frames
+            fsp = dec.osd_params(args.order, _lib.OSD_FS, fs_beta=args.beta, fs_tau_e=args.tau_e, fs_tau_psc=args.tau_psc)
+            outf = dec.osdl_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count)
+            legs.append(("osdl_fs_kernel", lambda: dec.osdl_fs_search(y, out["perm"], out["parity"], fsp, index=idx, count=count, out=outf)))
     elif pb:
         legs[1] = ("osdx_pb_kernel", lambda: dec.osdx_pb_search(y, out["perm"], out["parity"], pbp, index=idx, count=count, out=out))
         if dec.osdw_supported:                           # both families serve the code: osdw_pb_kernel on the same frames
@@ -251,6 +260,15 @@ def main(argv=None):
         for key in ("cw", "metric", "best", "ntep"):
             assert torch.equal(outl[key][:nf], out[key][:nf]), key
         legs_l = [("osdl_fs_kernel", lambda: dec.osdl_fs_search(y, outl["perm"], outl["parity"], fsp, index=idx, count=count, out=outl))]
+    if pb and not long_ and dec.osdl_supported:            # an older family serves the code: osdl_pb_kernel on the same frames, alternating
+        auxl = torch.zeros_like(aux)
+        pbl = dec.osd_params(args.order, _lib.OSD_PB, snr_db=args.snr, aux=auxl)
+        outl = dec.osdl_pb_decode(y, pbl, index=idx, count=count)
+        torch.cuda.synchronize()
+        for key in ("cw", "metric", "best", "ntep"):
+            assert torch.equal(outl[key][:nf], out[key][:nf]), key
+        assert torch.equal(auxl[:nf], aux[:nf]), "aux"
+        legs_l = [("osdl_pb_kernel", lambda: dec.osdl_pb_search(y, outl["perm"], outl["parity"], pbl, index=idx, count=count, out=outl))]
     legs += legs_l
     if args.oracle > 0:
         import time

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("LDPC_OSD_LIB") or os.path.join(_HERE, "libldpcosd.so"
 SYMBOLS = (
     "ldpc_last_error", "ldpc_abi_version",
     "ldpc_code_from_alist", "ldpc_code_from_dense", "ldpc_code_destroy", "ldpc_code_dims",
-    "ldpc_code_get_H", "ldpc_code_get_G", "ldpc_gf2elim_host", "ldpc_tep_table", "ldpc_tep_table_fs", "ldpc_crc32c",
+    "ldpc_code_get_H", "ldpc_code_get_G", "ldpc_gf2elim_host", "ldpc_tep_table", "ldpc_tep_table_fs", "ldpc_osdl_pb_table", "ldpc_crc32c",
     "ldpc_ctx_create", "ldpc_ctx_destroy", "ldpc_ctx_nms_kernel", "ldpc_ctx_get_pb_tuning", "ldpc_ctx_set_pb_tuning",
     "ldpc_nms_decode", "ldpc_nms_traj_rows", "ldpc_nms_train_grad", "ldpc_eval_counts", "ldpc_compact", "ldpc_pack_bits", "ldpc_unpack_bits",
     "ldpc_gen_frames",
@@ -27,7 +27,7 @@ SYMBOLS = (
     "ldpc_osdw_supported", "ldpc_osdw_front", "ldpc_osdw_search", "ldpc_osdw_decode",
     "ldpc_osdw_fs_search", "ldpc_osdw_fs_decode", "ldpc_osdw_tep_eval", "ldpc_osdw_pb_search", "ldpc_osdw_pb_decode",
     "ldpc_osdl_supported", "ldpc_osdl_front", "ldpc_osdl_search", "ldpc_osdl_decode",
-    "ldpc_osdl_fs_search", "ldpc_osdl_fs_decode", "ldpc_osdl_tep_eval",
+    "ldpc_osdl_fs_search", "ldpc_osdl_fs_decode", "ldpc_osdl_tep_eval", "ldpc_osdl_pb_search", "ldpc_osdl_pb_decode",
     "ldpc_hosd_pattern_teps", "ldpc_hosd_front", "ldpc_hosd_search", "ldpc_hosd_sliding",
     "ldpc_hosdx_supported", "ldpc_hosdx_front", "ldpc_hosdx_search", "ldpc_hosdx_sliding",
     "ldpc_hosdw_supported", "ldpc_hosdw_front", "ldpc_hosdw_search", "ldpc_hosdw_sliding", "ldpc_dia_cnn", "ldpc_dia_cnn_grad",
@@ -109,6 +109,7 @@ def load():
         "ldpc_gf2elim_host": (C.c_int, [pi32, i32, i32, pi32, pi32, pi32]),
         "ldpc_tep_table": (i64, [i32, i32, C.POINTER(C.c_uint8), pi64]),
         "ldpc_tep_table_fs": (i64, [i32, i32, C.POINTER(C.c_uint8)]),
+        "ldpc_osdl_pb_table": (i64, [i32, i32, C.POINTER(C.c_double)]),
         "ldpc_crc32c": (C.c_uint32, [vp, C.c_uint64]),
         "ldpc_ctx_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
         "ldpc_ctx_destroy": (None, [vp]),
@@ -163,8 +164,8 @@ def load():
             f"ldpc_{fam}_pb_search": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, C.POINTER(OsdParams), vp, vp, vp, vp, vp]),
             f"ldpc_{fam}_pb_decode": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(OsdParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         })
-    # the long / low-rate family has all of these but PB-OSD, under the signatures of the other two
-    for op in ("supported", "front", "search", "decode", "fs_search", "fs_decode", "tep_eval"):
+    # the long / low-rate family has all of these, under the signatures of the other two
+    for op in ("supported", "front", "search", "decode", "fs_search", "fs_decode", "tep_eval", "pb_search", "pb_decode"):
         sig[f"ldpc_osdl_{op}"] = sig[f"ldpc_osdx_{op}"]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError here = ABI/header drift, which must be loud

@@ -63,13 +63,14 @@ int ldpc_ctx_create(const ldpc_code *code, int32_t device, ldpc_ctx **out)
                                        (rc = upload(host.pb, &w.d_pb)))) break;
             if (w.k && !w.own_tep) { w.d_tep = ctx->osd_tables.d_tep; w.d_tep_fs = ctx->osd_tables.d_tep_fs; w.d_pb = ctx->osd_tables.d_pb; }
         }
-        {   // the tables of the long / low-rate family (ldpc_osdl.hip, ldpc_osdl_fs.hip); the TEP tables of a code the high-rate family serves are the ones above
+        {   // the tables of the long / low-rate family (ldpc_osdl.hip, ldpc_osdl_fs.hip, ldpc_osdl_pb.hip); the TEP tables of a code the high-rate family serves are the ones above
             OsdlTables &l = ctx->osdl_tables;
             OsdlTablesHost host;
             if ((rc = pack_osdl_tables(ctx->code, ctx->osdw_tables, l, host))) break;
             if (l.k && (rc = upload(host.Gcols, &l.d_Gcols))) break;
             if (l.k && l.own_tep && ((rc = upload(host.tep, &l.d_tep)) || (rc = upload(host.tep_fs, &l.d_tep_fs)))) break;
             if (l.k && !l.own_tep) { l.d_tep = ctx->osdw_tables.d_tep; l.d_tep_fs = ctx->osdw_tables.d_tep_fs; }
+            if (l.k && (rc = upload(host.pb, &l.d_pb))) break;
         }
         if ((rc = probe_dpp(&ctx->dpp_ror_up, &ctx->dpp_wave_rol_dir))) break;
         // event pool of ldpc_pipeline_run's timing slots: created (and recorded once: the first record of an
@@ -109,7 +110,7 @@ void ldpc_ctx_destroy(ldpc_ctx *ctx)
     if (ctx->osdw_tables.own_tep) {
         (void)hipFree(ctx->osdw_tables.d_tep); (void)hipFree(ctx->osdw_tables.d_tep_fs); (void)hipFree(ctx->osdw_tables.d_pb);
     }
-    (void)hipFree(ctx->osdl_tables.d_Gcols);
+    (void)hipFree(ctx->osdl_tables.d_Gcols); (void)hipFree(ctx->osdl_tables.d_pb);
     if (ctx->osdl_tables.own_tep) { (void)hipFree(ctx->osdl_tables.d_tep); (void)hipFree(ctx->osdl_tables.d_tep_fs); }
     (void)hipFree(ctx->d_chk_ptr); (void)hipFree(ctx->d_chk_var);
     (void)hipFree(ctx->d_var_ptr); (void)hipFree(ctx->d_var_edge);

@@ -284,6 +284,25 @@ static void pack_pb_table(int n, int k, std::vector<double> &pb)
     for (int i = 0; i < m; ++i) { tt = tt * coef_m[i] * (0.5 / 0.5); acc = acc + tt; cdf[i + 1] = acc; }
 }
 
+void pack_osdl_pb_table(int n, int k, std::vector<double> &pb)
+{
+    const int m = n - k;
+    pb.assign(kPblTabSize, 0.0);
+    double *cdf = pb.data() + kPblCdfH, *coef_m = pb.data() + kPblCoefM, *coef_k = pb.data() + kPblCoefK;
+    for (int i = 0; i < m; ++i) coef_m[i] = (double)(m - i) / (double)(i + 1);
+    for (int i = 0; i < k && i < 64; ++i) coef_k[i] = (double)(k - i) / (double)(i + 1);
+    int top = 0;
+    while ((m >> (top + 1)) != 0) ++top;
+    double tt = 0.5;
+    for (int b = top - 1; b >= 0; --b) {
+        tt = tt * tt;
+        if ((m >> b) & 1) tt = tt * 0.5;
+    }
+    double acc = tt;
+    cdf[0] = acc;
+    for (int i = 0; i < m; ++i) { tt = tt * coef_m[i] * (0.5 / 0.5); acc = acc + tt; cdf[i + 1] = acc; }
+}
+
 int pack_osd_tables(const ldpc_code &c, OsdTables &t, OsdTablesHost &host)
 {
     t = OsdTables();
@@ -357,6 +376,7 @@ int pack_osdl_tables(const ldpc_code &c, const OsdwTables &base, OsdlTables &t, 
     } else {
         for (int w = 0; w < 4; ++w) { t.fs_off[w] = base.fs_off[w]; t.fs_cnt[w] = base.fs_cnt[w]; }
     }
+    pack_osdl_pb_table(c.n, c.k, host.pb);
     t.n = c.n; t.k = c.k;
     return LDPC_OK;
 }
@@ -521,6 +541,17 @@ uint32_t ldpc_crc32c(const void *data, uint64_t len)
 }
 
 int64_t ldpc_tep_table_fs(int32_t k, int32_t weight, uint8_t *supports) { return tep_table_fs(k, weight, supports); }
+
+int64_t ldpc_osdl_pb_table(int32_t n, int32_t k, double *table)
+{
+    if (k < 1 || k > 192 || n - k < 1 || n - k > 192) return fail(LDPC_E_ARG, "ldpc_osdl_pb_table: (n=%d, k=%d) outside 1 <= k <= 192 and 1 <= n-k <= 192", n, k);
+    if (table) {
+        std::vector<double> pb;
+        pack_osdl_pb_table(n, k, pb);
+        std::copy(pb.begin(), pb.end(), table);
+    }
+    return kPblTabSize;
+}
 
 int64_t ldpc_hosd_pattern_teps(int32_t nseg, const int32_t *bounds, const int32_t *pattern, uint8_t *teps)
 {

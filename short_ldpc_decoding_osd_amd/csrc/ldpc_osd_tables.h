@@ -65,7 +65,11 @@ struct OsdwTablesHost {
 int pack_osdw_tables(const ldpc_code &c, const OsdTables &base, OsdwTables &t, OsdwTablesHost &host);
 
 // The tables of the long / low-rate family (ldpc_osdl.hip): every code with n <= 384, 1 <= k <= 192 and 1 <= n - k <= 192.  A
-// member of its own in the context, as OsdwTables is; it holds the tables of the conventional scan and of FS-OSD (no PB constants).
+// member of its own in the context, as OsdwTables is; it holds the tables of the conventional scan and of FS-OSD and the PB constants.
+// The PB table of this family (float64, m = n - k <= 192): cdfH[193] = P[Bin(m, 1/2) <= b] (zero beyond m), then the ratios of
+// consecutive binomial coefficients (m - i) / (i + 1), 192 entries (zero beyond m - 1), and (k - i) / (i + 1), the first 64
+// (zero beyond k - 1; the kernel reads the entries i < order <= 3).  The kPbx* layout of the older families (ldpc_pbx.h) is another.
+constexpr int kPblCdfH = 0, kPblCoefM = 193, kPblCoefK = 385, kPblTabSize = 449;
 struct OsdlTables {
     int n = 0, k = 0;            // the shape the tables were built for; k = 0: no tables (ldpc_osdl_* report UNSUPPORTED)
     u64 *d_Gcols = nullptr;      // [n][W] column v of G as W = ceil(k / 64) words: bit r of word w = G[64 w + r][v]
@@ -74,12 +78,14 @@ struct OsdlTables {
     int64_t ntep[4] = {0, 0, 0, 0};
     uchar4 *d_tep_fs = nullptr;  // FS-OSD visit order of this k, weight classes 1..min(3, k) back to back; where OsdwTables serves the code it IS OsdwTables::d_tep_fs
     int fs_off[4] = {0, 0, 0, 0}, fs_cnt[4] = {0, 0, 0, 0};   // weight class w: offset / count inside d_tep_fs
+    double *d_pb = nullptr;      // PB-OSD (ldpc_osdl_pb.h), the kPbl* layout; always this member's own
 };
 
 struct OsdlTablesHost {
     std::vector<u64> Gcols;      // [n][W]
     std::vector<uchar4> tep;     // filled only where `base` has no table of this k (1 179 809 entries, 4.7 MB, at k = 192)
     std::vector<uchar4> tep_fs;  // likewise (1 179 808 entries, 4.7 MB, at k = 192)
+    std::vector<double> pb;      // [kPblTabSize], for every code the family serves
 };
 
 // For a code with n <= 384, 1 <= k <= 192, 1 <= n - k <= 192 and G = [k][n]: fills `host` and the shape, boundaries, offsets and
@@ -87,6 +93,10 @@ struct OsdlTablesHost {
 // already packed for the same code.  Any other code leaves t.k = 0.  LDPC_OK, or the error of tep_table / tep_table_fs.  Pure
 // host code (ldpc_host.cpp).
 int pack_osdl_tables(const ldpc_code &c, const OsdwTables &base, OsdlTables &t, OsdlTablesHost &host);
+
+// The PB table of the long / low-rate family for 1 <= k <= 192 and 1 <= m = n - k <= 192 (the kPbl* layout above): cdfH by the
+// float64 pmf recurrence of pack_pb_table -- q^m by left-to-right square-and-multiply, ratio p / q = 1.  Pure host code.
+void pack_osdl_pb_table(int n, int k, std::vector<double> &pb);
 
 // The kernel argument of osd_fs_kernel / osdx_fs_kernel / osdw_fs_kernel / osdl_fs_kernel (FsParams: ldpc_search.h) from the
 // caller's parameters and the shape, class offsets and class counts of the context's FS table (OsdTables, OsdwTables or OsdlTables: fs_off / fs_cnt);

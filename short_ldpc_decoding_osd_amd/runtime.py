@@ -503,6 +503,18 @@ class Decoder:
         search of ``osdl_fs_search``; ``perm`` / ``parity`` in the layouts of ``osdl_front``, ``label_bits`` / ``counts`` as there."""
         return self._osd_decode("osdl", "fs_decode", y, C.byref(params), index, count, F, perm, parity, label_bits, counts, out)
 
+    def osdl_pb_search(self, y, perm, parity, params, index=None, count=None, F=None, out=None):
+        """``osdx_pb_search`` for every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192, on the results of
+        ``osdl_front`` (its layouts).  ``params`` (``osd_params(order, _lib.OSD_PB, snr_db=..., aux=...)``, order
+        0..min(3, k)) and the returned dict as there."""
+        return self._osd_search("osdl", "pb_search", y, perm, parity, C.byref(params), index, count, F, out)
+
+    def osdl_pb_decode(self, y, params, index=None, count=None, F=None, perm=None, parity=None, label_bits=None, counts=None,
+                       out=None):
+        """``osdx_pb_decode`` for every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192: ``osdl_decode`` with the
+        search of ``osdl_pb_search``; ``perm`` / ``parity`` in the layouts of ``osdl_front``, ``label_bits`` / ``counts`` as there."""
+        return self._osd_decode("osdl", "pb_decode", y, C.byref(params), index, count, F, perm, parity, label_bits, counts, out)
+
     def osdl_tep_eval(self, y, perm, parity, mask, index=None, count=None):
         """``osdx_tep_eval`` for every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192, on the results of ``osdl_front``.
         mask [F, ceil(k/64)] int64: bit p of word w flips primed MRB position 64 w + p; bits at or beyond k are ignored.
