@@ -570,7 +570,7 @@ def pb_osd_frame(yp, labelp, Gp, order, snr_db):
         w1 = F32(np.exp(F32(c4 * rs)) * spl)                            # tep_prob :441-445
         w2 = F32(F32(1) - w1)
         bt = np.floor(F32(F32(w_dmin - rs) / lrb_mean))                 # beta_acquire :399-405
-        beta = 0 if not bt > 0 else (64 if bt > 64 else int(bt))
+        beta = 0 if not bt > 0 else (n - k if bt > n - k else int(bt))   # :404 min(tmp, n - k)
         bs = F32(0)
         bs = F32(bs + w1 * F32(stats.binom.cdf(beta, n - k, float(p1))))
         bs = F32(bs + w2 * F32(stats.binom.cdf(beta, n - k, 0.5)))

@@ -143,12 +143,10 @@ def pack(P, rows):
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def pair(k, n, name, mode, form="sorted", frames=FRAMES, seed=0):
-    """The (perm, P') pair as written, the same P' for every frame -> dict(k, n, name, mode, form, G = [I | P'], y [F, n] in
-    ORIGINAL bit order, cw = the labels in original order, perm [F, 128] u8 (0 beyond n), parity64 [F, 64] u64 (None for k > 64),
-    parity128 [F, 128] u64, Gps = [I | P'] per frame, yp = y in primed order).  Cached: shared, read-only.
-    ``extreme`` draws frames // 6 frames at 2.0 dB and returns their six extremes."""
+def draw(k, n, name, mode, form="sorted", frames=FRAMES, seed=0):
+    """The frames of a pair before any device layout (shared with tests/osdl_shapes.py) -> (G = [I | P'], y [F, n] in ORIGINAL
+    bit order, cw = the labels in original order, p [F, n] int64 = original bit at primed position q, yp = y in primed order,
+    cwp).  ``extreme`` draws frames // 6 frames at 2.0 dB and returns their six extremes."""
     assert form in FORMS and mode in MODES + ("extreme",)
     G = systematic(k, n, name)
     rng = np.random.default_rng(_seed(k, n, name, STRUCTURES) * 11 + seed + 3 * (MODES + ("extreme",)).index(mode)
@@ -165,23 +163,34 @@ def pair(k, n, name, mode, form="sorted", frames=FRAMES, seed=0):
         if mode == "grid":
             yp = to_grid(yp)
     F = len(yp)
-    perm = np.zeros((F, 128), np.uint8)
+    p = np.empty((F, n), np.int64)
     if form == "sorted":
         mag = -np.sort(-np.abs(yp), axis=1)
         yp = np.where(np.signbit(yp), -mag, mag).astype(F32)
-        perm[:, :n] = np.arange(n)
+        p[:] = np.arange(n)
     else:
         for f in range(F):
-            perm[f, :n] = rng.permutation(n)
-    p = perm[:, :n].astype(np.int64)
+            p[f] = rng.permutation(n)
     y = np.empty_like(yp)
     cw = np.empty_like(cwp)
     np.put_along_axis(y, p, yp, axis=1)                      # y[f, perm[f, q]] = y'[f, q]
     np.put_along_axis(cw, p, cwp, axis=1)
+    return G, np.ascontiguousarray(y, dtype=F32), cw, p, np.ascontiguousarray(yp, dtype=F32), cwp
+
+
+@functools.lru_cache(maxsize=None)
+def pair(k, n, name, mode, form="sorted", frames=FRAMES, seed=0):
+    """The (perm, P') pair as written, the same P' for every frame -> dict(k, n, name, mode, form, G = [I | P'], y [F, n] in
+    ORIGINAL bit order, cw = the labels in original order, perm [F, 128] u8 (0 beyond n), parity64 [F, 64] u64 (None for k > 64),
+    parity128 [F, 128] u64, Gps = [I | P'] per frame, yp = y in primed order).  Cached: shared, read-only.
+    ``extreme`` draws frames // 6 frames at 2.0 dB and returns their six extremes."""
+    G, y, cw, p, yp, cwp = draw(k, n, name, mode, form, frames, seed)
+    F = len(y)
+    perm = np.zeros((F, 128), np.uint8)
+    perm[:, :n] = p
     P = np.tile(parity(k, n, name), (F, 1, 1))
-    return _freeze(dict(k=k, n=n, name=name, mode=mode, form=form, G=G, y=np.ascontiguousarray(y, dtype=F32), cw=cw, perm=perm,
-                        parity64=pack(P, 64) if k <= 64 else None, parity128=pack(P, 128), Gps=[G] * F,
-                        yp=np.ascontiguousarray(yp, dtype=F32), cwp=cwp))
+    return _freeze(dict(k=k, n=n, name=name, mode=mode, form=form, G=G, y=y, cw=cw, perm=perm,
+                        parity64=pack(P, 64) if k <= 64 else None, parity128=pack(P, 128), Gps=[G] * F, yp=yp, cwp=cwp))
 
 
 def front_of(c):
@@ -214,7 +223,7 @@ def tep_masks(c, rng):
     of P' only and one over a group of equal non-zero rows (0 where the pair has none), as _masks of
     tests/test_gpu_osd_generators.py: a list of 7 lists of F ints."""
     k, F = c["k"], len(c["y"])
-    rows = [int(r) for r in c["parity128"][0, :k]]
+    rows = [int.from_bytes(np.packbits(r.astype(np.uint8), bitorder="little").tobytes(), "little") for r in c["G"][:, k:]]
     zero = sum(1 << p for p in range(k) if rows[p] == 0)
     groups = {}
     for p, r in enumerate(rows):
