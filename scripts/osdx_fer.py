@@ -38,6 +38,8 @@ frames.  On a code that ldpc_osdw_* serves as well the conventional run also tim
 alternating; on a code an older family serves the --osd fs run asserts that ldpc_osdl_fs_decode gives the same outputs and
 times osdl_fs_kernel alternating with the older family's FS kernel, and the --osd pb run does the same with
 ldpc_osdl_pb_decode and osdl_pb_kernel.
+The conventional run also times the one-TEP kernel (osdx_ / osdw_ / osdl_tep_eval_kernel) of every family it runs, on the same
+front-end results: every frame evaluates the TEP that flips MRB positions 0 and k - 1.
 --oracle N times the C oracle's front end (oracle/c_oracle.osd_front, one core) on the first N failures and prints its frames/s.
 --gen hip draws the frames with the library's counter-based generator (Decoder.gen_frames: frames 0 .. --frames - 1 of the set
 --seed, one launch) instead of the torch ops; the JSON line says which.
@@ -55,7 +57,7 @@ import numpy as np   # noqa: E402
 import torch         # noqa: E402
 
 from short_ldpc_decoding_osd_amd import Code, _lib              # noqa: E402
-from short_ldpc_decoding_osd_amd.runtime import Decoder         # noqa: E402
+from short_ldpc_decoding_osd_amd.runtime import Decoder, _ptr   # noqa: E402
 
 
 def make_frames(dec, B, seed, snr_db):
@@ -270,6 +272,25 @@ def main(argv=None):
         assert torch.equal(auxl[:nf], aux[:nf]), "aux"
         legs_l = [("osdl_pb_kernel", lambda: dec.osdl_pb_search(y, outl["perm"], outl["parity"], pbl, index=idx, count=count, out=outl))]
     legs += legs_l
+    if not fs and not pb:                                # the one-TEP kernel of every family in the run: each frame flips MRB positions 0 and k - 1
+        def tep_mask(words):
+            m = np.zeros((idx.shape[0], words), np.uint64)
+            for p in {0, dec.k - 1}:
+                m[:, p // 64] |= np.uint64(1) << np.uint64(p % 64)
+            return torch.from_numpy(m.view(np.int64)).to(dec.device)
+        fronts = {"osdl" if long_ else "osdw" if wide else "osdx": (out["perm"], out["parity"])}
+        if not wide and not long_ and dec.osdw_supported:
+            fronts["osdw"] = (outw["perm"], outw["parity"])
+        if legs_l:
+            fronts["osdl"] = (outl["perm"], outl["parity"])
+        for fam, (fperm, fparity) in fronts.items():
+            mask = tep_mask({"osdx": 1, "osdw": 2, "osdl": (dec.k + 63) // 64}[fam])
+            mask = mask[:, 0].contiguous() if fam == "osdx" else mask
+            res = getattr(dec, fam + "_tep_eval")(y, fperm, fparity, mask, index=idx, count=count)
+            targs = tuple(_ptr(t) for t in (y, idx, count)) + (idx.shape[0],) + tuple(
+                _ptr(t) for t in (fperm, fparity, mask, res["cw"], res["metric"], res["hd"]))
+            # (Decoder.*_tep_eval allocates its outputs on every call; the timed leg calls the library function on those of one call)
+            legs.append((fam + "_tep_eval_kernel", lambda fam=fam, targs=targs: dec._osd_call(fam, "tep_eval", *targs)))
     if args.oracle > 0:
         import time
         from oracle import c_oracle

@@ -9,6 +9,7 @@
 // indexed at run time, so the columns stay in registers (no scratch; profiles/osdl/README.md).  The host routes a code to S
 // rounded up to 2, 4 or 6 (an idle slot carries zero columns) and to its own W and Wp.
 // The metric (tep_cost_bounded, lut_byte) and the wave helpers of ldpc_search.h / ldpc_wave.h are used unchanged.
+// osdl_prepare / osdl_finish are the per-frame prologue and epilogue every search on such front-end results shares.
 #pragma once
 
 #include "ldpc_search.h"
@@ -271,17 +272,10 @@ __global__ __launch_bounds__(64) void osdl_front_kernel(const float *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------
-// conventional order-p search over the reference's TEP table for THIS k (the scan of osdw_search_kernel with up to 192 MRB
-// positions and a discrepancy of WP = ceil((n - k) / 64) words)
+// LDS of the searches: up to 192 MRB positions and a discrepancy of WP = ceil((n - k) / 64) words
 //   SearchLLds: w[0..k-1] = |y'| of the MRB, w[192..192+n-k-1] = |y'| of the parity part, zero elsewhere; the 8 WP byte LUTs
 //   hold the sums of np_oracle._weighted_distance_k (bytes of eight positions from primed position k, each ascending from
 //   0.0f: a padded position adds 0.0f, which changes no bit of a sum >= 0).
-//   perm_in [F][64 ceil(n/64)] u16 and parity_in [F][64 ceil(k/64)][WP] u64 as the front end writes them; an entry of perm_in at
-//   or beyond n is read as 0 (the caller's error: nothing is read or written outside the buffers).
-//   cw_out [F][words] u64, words = ceil(n / 64); label [*][words] addressed through `index`.
-//   counts[3] += {frames, frames_wrong, teps_total} (with label; teps_total only with ntep_out): one atomic per counter and
-//   wavefront, after its last frame.
-// The first minimum wins, +inf included: when every cost is +inf the winner is the first TEP of the table, as np.argmin has it.
 // ---------------------------------------------------------------------------------------
 template <int WP>
 struct __attribute__((aligned(16))) SearchLLds {
@@ -291,10 +285,94 @@ struct __attribute__((aligned(16))) SearchLLds {
     u64 cw[kOsdlN / 64];          // codeword being assembled in original bit order
 };
 
-// whether the TEP flips primed MRB position p
-__device__ __forceinline__ bool tepl_flips(uchar4 s, int p)
+template <int WP>
+struct __attribute__((aligned(16))) SearchLLdsLean {   // SearchLLds without the byte LUTs (at WP = 3: 7.6 KiB instead of 31.6)
+    u64 P[kOsdlK][WP];
+    float w[kOsdlK + 64 * WP];
+    u64 cw[kOsdlN / 64];
+};
+
+// ---------------------------------------------------------------------------------------
+// per-frame prologue and epilogue of every search on this family's front-end results (osdw_prepare / osdw_finish of ldpc_osdw.h
+// with three MRB slots per lane and WP parity words).  Idle lanes stay out of the hard-decision ballots -- their y = 0 would
+// count as a hard 1 --, rows of P' are masked to n - k columns, and w[] and P[] are zero beyond the live positions.
+//   LDS: SearchLLds<WP> (LUTS = true: the 8 WP byte LUTs over w[192..] are built) or SearchLLdsLean<WP> (LUTS = false).
+//   perm_in [F][64 ceil(n/64)] u16 and parity_in [F][64 ceil(k/64)][WP] u64 as osdl_front_kernel writes them; an entry of
+//   perm_in at or beyond n is read as 0 (the caller's error: nothing is read or written outside the buffers).
+// ---------------------------------------------------------------------------------------
+template <int WP>
+struct OsdlFrame {
+    u64 hm[3], hp[WP], d0[WP];   // hard decisions (y' > 0 ? 0 : 1) of MRB positions 64 s + lane / the parity part, order-0 discrepancy
+    int oM[3], oP[WP];           // original bit of primed positions 64 s + lane / k + 64 q + lane
+};
+
+template <int WP, bool LUTS, class LDS>
+__device__ __forceinline__ OsdlFrame<WP> osdl_prepare(LDS &L, const float *__restrict__ y, long long src, const unsigned short *__restrict__ perm_in,
+                                                     const u64 *__restrict__ parity_in, long long f, int n, int k, int lane)
 {
-    return (s.w > 0 && s.x == p) || (s.w > 1 && s.y == p) || (s.w > 2 && s.z == p);
+    OsdlFrame<WP> S;
+    const int m = n - k;
+    const int words = (n + 63) >> 6, Wk = (k + 63) >> 6;
+    const unsigned short *perm = perm_in + f * words * 64;
+    u64 colmask[WP];
+#pragma unroll
+    for (int q = 0; q < WP; ++q) colmask[q] = m >= 64 * (q + 1) ? ~0ull : (m > 64 * q ? ((1ull << (m - 64 * q)) - 1ull) : 0ull);
+#pragma unroll
+    for (int q = 0; q < WP; ++q) S.d0[q] = 0ull;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {                           // primed MRB position 64 s + lane
+        const int p = 64 * s + lane;
+        const bool live = p < k;
+        const int o = live ? perm[p] : 0;
+        S.oM[s] = o < n ? o : 0;
+        const float yv = live ? y[src * n + S.oM[s]] : 0.0f;
+        L.w[p] = __builtin_fabsf(yv);
+        S.hm[s] = __ballot(live && !(yv > 0.0f));           // idle lanes stay out: y = 0 is a hard 1
+#pragma unroll
+        for (int q = 0; q < WP; ++q) {
+            const u64 row = live ? (parity_in[((f * Wk * 64) + p) * WP + q] & colmask[q]) : 0ull;
+            L.P[p][q] = row;
+            S.d0[q] ^= ((S.hm[s] >> lane) & 1) ? row : 0ull;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < WP; ++q) {                          // primed parity position k + 64 q + lane
+        const int p = 64 * q + lane;
+        const bool live = p < m;
+        const int o = live ? perm[k + p] : 0;
+        S.oP[q] = o < n ? o : 0;
+        const float yv = live ? y[src * n + S.oP[q]] : 0.0f;
+        L.w[kOsdlK + p] = __builtin_fabsf(yv);
+        S.hp[q] = __ballot(live && !(yv > 0.0f));
+    }
+    if (lane < kOsdlN / 64) L.cw[lane] = 0;
+    wave_fence();
+#pragma unroll
+    for (int q = 0; q < WP; ++q) {
+        if constexpr (LUTS) build_byte_luts<8>(&L.lut[8 * q], &L.w[kOsdlK + 64 * q], lane);
+        S.d0[q] = wave_xor64(S.d0[q]) ^ S.hp[q];            // d0 = (u0 . P') ^ h_parity
+    }
+    wave_fence();
+    return S;
+}
+
+// candidate (flip[s]: whether it flips MRB position 64 s + lane, D = parity discrepancy) -> codeword in ORIGINAL bit order,
+// ceil(n / 64) words; L.cw holds it afterwards (the callers compare it with the label before their closing wave_fence)
+template <int WP, class LDS>
+__device__ __forceinline__ void osdl_finish(LDS &L, const OsdlFrame<WP> &S, const bool (&flip)[3], const u64 (&D)[WP], long long f, int n, int k,
+                                            int lane, u64 *__restrict__ cw_out)
+{
+    const int m = n - k, words = (n + 63) >> 6;
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+        if (64 * s + lane < k && ((((S.hm[s] >> lane) & 1) != 0) != flip[s])) atomicOr(&L.cw[S.oM[s] >> 6], 1ull << (S.oM[s] & 63));
+#pragma unroll
+    for (int q = 0; q < WP; ++q) {
+        const u64 par_bits = D[q] ^ S.hp[q];
+        if (64 * q + lane < m && ((par_bits >> lane) & 1)) atomicOr(&L.cw[S.oP[q] >> 6], 1ull << (S.oP[q] & 63));
+    }
+    wave_fence();
+    if (lane < words) cw_out[f * words + lane] = L.cw[lane];
 }
 
 // tep_cost_bounded (ldpc_search.h) over WP words of discrepancy: word 0 as there (exit after its two most reliable bytes), then
@@ -316,6 +394,33 @@ __device__ __forceinline__ bool tepl_cost_bounded(const SearchLLds<WP> &L, float
     return true;
 }
 
+// one TEP (ascending support s.x < s.y < s.z, weight s.w) -> parity discrepancy, MRB weight sum (tepw_apply with WP words)
+template <int WP>
+__device__ __forceinline__ void tepl_apply(const SearchLLds<WP> &L, uchar4 s, const u64 (&d0)[WP], u64 (&D)[WP], float &mrb)
+{
+    mrb = 0.0f;
+#pragma unroll
+    for (int q = 0; q < WP; ++q) D[q] = d0[q];
+    if (s.w > 0) { mrb = L.w[s.x];
+#pragma unroll
+        for (int q = 0; q < WP; ++q) D[q] ^= L.P[s.x][q]; }
+    if (s.w > 1) { mrb = mrb + L.w[s.y];
+#pragma unroll
+        for (int q = 0; q < WP; ++q) D[q] ^= L.P[s.y][q]; }
+    if (s.w > 2) { mrb = mrb + L.w[s.z];
+#pragma unroll
+        for (int q = 0; q < WP; ++q) D[q] ^= L.P[s.z][q]; }
+}
+
+// ---------------------------------------------------------------------------------------
+// conventional order-p search over the reference's TEP table for THIS k (the scan of osdw_search_kernel with up to 192 MRB
+// positions and a discrepancy of WP words), on osdl_prepare / osdl_finish
+//   cw_out [F][words] u64, words = ceil(n / 64); label [*][words] addressed through `index`.
+//   counts[3] += {frames, frames_wrong, teps_total} (with label; teps_total only with ntep_out): one atomic per counter and
+//   wavefront, after its last frame.
+// The first minimum wins, +inf included: when every cost is +inf the winner is the first TEP of the table, as np.argmin has it
+// (the two older families return "no candidate" there: best = 0x7FFFFFFF, nothing flipped).
+// ---------------------------------------------------------------------------------------
 template <int WP>
 __global__ __launch_bounds__(64) void osdl_search_kernel(const float *__restrict__ y, const int *__restrict__ index, const int *__restrict__ count,
         long long F, int n, int k, const unsigned short *__restrict__ perm_in, const u64 *__restrict__ parity_in,
@@ -324,56 +429,13 @@ __global__ __launch_bounds__(64) void osdl_search_kernel(const float *__restrict
 {
     __shared__ SearchLLds<WP> L;   // one wavefront per workgroup: compile-time LDS base for the LUT reads
     const int lane = threadIdx.x;
-    const int m = n - k;
-    const int words = (n + 63) >> 6, Wk = (k + 63) >> 6;
-    u64 colmask[WP];
-#pragma unroll
-    for (int q = 0; q < WP; ++q) colmask[q] = m >= 64 * (q + 1) ? ~0ull : (m > 64 * q ? ((1ull << (m - 64 * q)) - 1ull) : 0ull);
+    const int words = (n + 63) >> 6;
     const long long nframes = frame_count(count, F);
     unsigned long long seen = 0, wrong = 0, nteps = 0;
 
     for (long long f = blockIdx.x; f < nframes; f += gridDim.x) {
         const long long src = index ? index[f] : f;
-        const unsigned short *perm = perm_in + f * words * 64;
-        // ---- primed-order values, rows of P', hard decisions, byte LUTs, the order-0 discrepancy ----
-        int oM[3], oP[WP];
-        u64 hm[3], hp[WP], d0[WP];
-#pragma unroll
-        for (int q = 0; q < WP; ++q) d0[q] = 0ull;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {                           // primed MRB position 64 s + lane
-            const int p = 64 * s + lane;
-            const bool live = p < k;
-            const int o = live ? perm[p] : 0;
-            oM[s] = o < n ? o : 0;
-            const float yv = live ? y[src * n + oM[s]] : 0.0f;
-            L.w[p] = __builtin_fabsf(yv);
-            hm[s] = __ballot(live && !(yv > 0.0f));             // idle lanes stay out: y = 0 is a hard 1
-#pragma unroll
-            for (int q = 0; q < WP; ++q) {
-                const u64 row = live ? (parity_in[((f * Wk * 64) + p) * WP + q] & colmask[q]) : 0ull;
-                L.P[p][q] = row;
-                d0[q] ^= ((hm[s] >> lane) & 1) ? row : 0ull;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < WP; ++q) {                          // primed parity position k + 64 q + lane
-            const int p = 64 * q + lane;
-            const bool live = p < m;
-            const int o = live ? perm[k + p] : 0;
-            oP[q] = o < n ? o : 0;
-            const float yv = live ? y[src * n + oP[q]] : 0.0f;
-            L.w[kOsdlK + p] = __builtin_fabsf(yv);
-            hp[q] = __ballot(live && !(yv > 0.0f));
-        }
-        if (lane < kOsdlN / 64) L.cw[lane] = 0;
-        wave_fence();
-#pragma unroll
-        for (int q = 0; q < WP; ++q) {
-            build_byte_luts<8>(&L.lut[8 * q], &L.w[kOsdlK + 64 * q], lane);
-            d0[q] = wave_xor64(d0[q]) ^ hp[q];                  // d0 = (u0 . P') ^ h_parity
-        }
-        wave_fence();
+        const OsdlFrame<WP> S = osdl_prepare<WP, true>(L, y, src, perm_in, parity_in, f, n, k, lane);
         // ---- scan the TEP table, one TEP per lane per round; the first minimum wins ------------------
         float best = __builtin_inff();
         int bestt = 0x7FFFFFFF;
@@ -385,20 +447,9 @@ __global__ __launch_bounds__(64) void osdl_search_kernel(const float *__restrict
         for (int t0 = 0; t0 < ntep; t0 += 64, ++trip) {
             const int t = t0 + lane;
             if (t < ntep) {
-                const uchar4 s = teps[t];
                 u64 D[WP];
-                float mrb = 0.0f, c;
-#pragma unroll
-                for (int q = 0; q < WP; ++q) D[q] = d0[q];
-                if (s.w > 0) { mrb = L.w[s.x];
-#pragma unroll
-                    for (int q = 0; q < WP; ++q) D[q] ^= L.P[s.x][q]; }
-                if (s.w > 1) { mrb = mrb + L.w[s.y];
-#pragma unroll
-                    for (int q = 0; q < WP; ++q) D[q] ^= L.P[s.y][q]; }
-                if (s.w > 2) { mrb = mrb + L.w[s.z];
-#pragma unroll
-                    for (int q = 0; q < WP; ++q) D[q] ^= L.P[s.z][q]; }
+                float mrb, c;
+                tepl_apply<WP>(L, teps[t], S.d0, D, mrb);
                 // (c == best: only while the lane holds no candidate yet -- t ascends in a lane -- i.e. for a first cost of +inf)
                 if (tepl_cost_bounded<WP>(L, mrb, D, bound, c) && (c < best || (c == best && t < bestt))) {
                     best = c; bestt = t;
@@ -418,25 +469,10 @@ __global__ __launch_bounds__(64) void osdl_search_kernel(const float *__restrict
         uchar4 win;   // (no lane found a candidate -- every cost a NaN --: bestt is no index, nothing is flipped)
         win.x = win.y = win.z = win.w = 0;
         if (bestt < ntep) win = teps[bestt];
-        // ---- candidate -> codeword in ORIGINAL bit order, ceil(n / 64) words ---------------------
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            const int p = 64 * s + lane;
-            if (p < k && ((((hm[s] >> lane) & 1) != 0) != tepl_flips(win, p))) atomicOr(&L.cw[oM[s] >> 6], 1ull << (oM[s] & 63));
-        }
-#pragma unroll
-        for (int q = 0; q < WP; ++q) {
-            const u64 par_bits = bestD[q] ^ hp[q];
-            if (64 * q + lane < m && ((par_bits >> lane) & 1)) atomicOr(&L.cw[oP[q] >> 6], 1ull << (oP[q] & 63));
-        }
-        wave_fence();
-        if (lane < words) cw_out[f * words + lane] = L.cw[lane];
+        const bool flip[3] = {tep_flips(win, lane), tep_flips(win, 64 + lane), tep_flips(win, 128 + lane)};
+        osdl_finish<WP>(L, S, flip, bestD, f, n, k, lane, cw_out);
         store_results(f, lane, best, bestt, ntep, metric_out, best_out, ntep_out);
-        if (label) {
-            bool bad = false;
-            for (int w = 0; w < words; ++w) bad |= L.cw[w] != label[src * words + w];
-            seen += 1; wrong += bad; nteps += ntep_out ? (unsigned long long)ntep : 0ull;
-        }
+        if (label) { seen += 1; wrong += cw_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
         wave_fence();
     }
     if (label && lane == 0 && seen) {

@@ -14,116 +14,13 @@
 
 namespace ldpc {
 
-template <int WP>
-struct __attribute__((aligned(16))) SearchLLdsLean {   // SearchLLds without the byte LUTs (at WP = 3: 7.6 KiB instead of 31.6)
-    u64 P[kOsdlK][WP];
-    float w[kOsdlK + 64 * WP];
-    u64 cw[kOsdlN / 64];
-};
-
 // ---------------------------------------------------------------------------------------
-// per-frame prologue and epilogue of the FS scan and the one-TEP kernel (osdw_prepare / osdw_finish of ldpc_osdw_fs.h with three
-// MRB slots per lane and WP parity words).  They are the prologue and epilogue of osdl_search_kernel (ldpc_osdl.h) word for
-// word, as a COPY, for the reason ldpc_osdw_fs.h records: that kernel's register counts are the ones its measurements were
-// taken with (profiles/osdl/README.md), so it keeps its own text.  Idle lanes stay out of the hard-decision ballots -- their
-// y = 0 would count as a hard 1 --, rows of P' are masked to n - k columns, and w[] and P[] are zero beyond the live positions.
-//   LDS: SearchLLds<WP> (LUTS = true: the 8 WP byte LUTs over w[192..] are built) or SearchLLdsLean<WP> (LUTS = false).
-//   perm_in [F][64 ceil(n/64)] u16 and parity_in [F][64 ceil(k/64)][WP] u64 as osdl_front_kernel writes them; an entry of
-//   perm_in at or beyond n is read as 0 (the caller's error: nothing is read or written outside the buffers).
+// The per-frame prologue and epilogue are osdl_prepare / osdl_finish (ldpc_osdl.h), shared with osdl_search_kernel and the PB
+// kernel.  The FS scan itself stays a text per family: written as one body over traits for the three families, with the same
+// round loop, the launch of this kernel measured 1.8 % and 2.0 % above this text in two
+// alternating sessions at WP = 2 (a (200,100) code, 159 TEPs per frame; 1.9 % at WP = 3 in one), about ten times the spread of
+// this text's own runs, and the cause was not found (profiles/osd_scan_shared/README.md): the three FS kernels stay three texts.
 // ---------------------------------------------------------------------------------------
-template <int WP>
-struct OsdlFrame {
-    u64 hm[3], hp[WP], d0[WP];   // hard decisions (y' > 0 ? 0 : 1) of MRB positions 64 s + lane / the parity part, order-0 discrepancy
-    int oM[3], oP[WP];           // original bit of primed positions 64 s + lane / k + 64 q + lane
-};
-
-template <int WP, bool LUTS, class LDS>
-__device__ __forceinline__ OsdlFrame<WP> osdl_prepare(LDS &L, const float *__restrict__ y, long long src, const unsigned short *__restrict__ perm_in,
-                                                     const u64 *__restrict__ parity_in, long long f, int n, int k, int lane)
-{
-    OsdlFrame<WP> S;
-    const int m = n - k;
-    const int words = (n + 63) >> 6, Wk = (k + 63) >> 6;
-    const unsigned short *perm = perm_in + f * words * 64;
-    u64 colmask[WP];
-#pragma unroll
-    for (int q = 0; q < WP; ++q) colmask[q] = m >= 64 * (q + 1) ? ~0ull : (m > 64 * q ? ((1ull << (m - 64 * q)) - 1ull) : 0ull);
-#pragma unroll
-    for (int q = 0; q < WP; ++q) S.d0[q] = 0ull;
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {                           // primed MRB position 64 s + lane
-        const int p = 64 * s + lane;
-        const bool live = p < k;
-        const int o = live ? perm[p] : 0;
-        S.oM[s] = o < n ? o : 0;
-        const float yv = live ? y[src * n + S.oM[s]] : 0.0f;
-        L.w[p] = __builtin_fabsf(yv);
-        S.hm[s] = __ballot(live && !(yv > 0.0f));           // idle lanes stay out: y = 0 is a hard 1
-#pragma unroll
-        for (int q = 0; q < WP; ++q) {
-            const u64 row = live ? (parity_in[((f * Wk * 64) + p) * WP + q] & colmask[q]) : 0ull;
-            L.P[p][q] = row;
-            S.d0[q] ^= ((S.hm[s] >> lane) & 1) ? row : 0ull;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < WP; ++q) {                          // primed parity position k + 64 q + lane
-        const int p = 64 * q + lane;
-        const bool live = p < m;
-        const int o = live ? perm[k + p] : 0;
-        S.oP[q] = o < n ? o : 0;
-        const float yv = live ? y[src * n + S.oP[q]] : 0.0f;
-        L.w[kOsdlK + p] = __builtin_fabsf(yv);
-        S.hp[q] = __ballot(live && !(yv > 0.0f));
-    }
-    if (lane < kOsdlN / 64) L.cw[lane] = 0;
-    wave_fence();
-#pragma unroll
-    for (int q = 0; q < WP; ++q) {
-        if constexpr (LUTS) build_byte_luts<8>(&L.lut[8 * q], &L.w[kOsdlK + 64 * q], lane);
-        S.d0[q] = wave_xor64(S.d0[q]) ^ S.hp[q];            // d0 = (u0 . P') ^ h_parity
-    }
-    wave_fence();
-    return S;
-}
-
-// candidate (flip[s]: whether it flips MRB position 64 s + lane, D = parity discrepancy) -> codeword in ORIGINAL bit order,
-// ceil(n / 64) words; L.cw holds it afterwards (the callers compare it with the label before their closing wave_fence)
-template <int WP, class LDS>
-__device__ __forceinline__ void osdl_finish(LDS &L, const OsdlFrame<WP> &S, const bool (&flip)[3], const u64 (&D)[WP], long long f, int n, int k,
-                                            int lane, u64 *__restrict__ cw_out)
-{
-    const int m = n - k, words = (n + 63) >> 6;
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-        if (64 * s + lane < k && ((((S.hm[s] >> lane) & 1) != 0) != flip[s])) atomicOr(&L.cw[S.oM[s] >> 6], 1ull << (S.oM[s] & 63));
-#pragma unroll
-    for (int q = 0; q < WP; ++q) {
-        const u64 par_bits = D[q] ^ S.hp[q];
-        if (64 * q + lane < m && ((par_bits >> lane) & 1)) atomicOr(&L.cw[S.oP[q] >> 6], 1ull << (S.oP[q] & 63));
-    }
-    wave_fence();
-    if (lane < words) cw_out[f * words + lane] = L.cw[lane];
-}
-
-// one TEP (ascending support s.x < s.y < s.z, weight s.w) -> parity discrepancy, MRB weight sum (tepw_apply with WP words)
-template <int WP>
-__device__ __forceinline__ void tepl_apply(const SearchLLds<WP> &L, uchar4 s, const u64 (&d0)[WP], u64 (&D)[WP], float &mrb)
-{
-    mrb = 0.0f;
-#pragma unroll
-    for (int q = 0; q < WP; ++q) D[q] = d0[q];
-    if (s.w > 0) { mrb = L.w[s.x];
-#pragma unroll
-        for (int q = 0; q < WP; ++q) D[q] ^= L.P[s.x][q]; }
-    if (s.w > 1) { mrb = mrb + L.w[s.y];
-#pragma unroll
-        for (int q = 0; q < WP; ++q) D[q] ^= L.P[s.y][q]; }
-    if (s.w > 2) { mrb = mrb + L.w[s.z];
-#pragma unroll
-        for (int q = 0; q < WP; ++q) D[q] ^= L.P[s.z][q]; }
-}
-
 // the whole metric: tepl_cost_bounded under a bound nothing exceeds
 template <int WP>
 __device__ __forceinline__ float tepl_cost(const SearchLLds<WP> &L, float mrb, const u64 (&D)[WP])
@@ -220,7 +117,7 @@ __global__ __launch_bounds__(64) void osdl_fs_kernel(const float *__restrict__ y
         bool flip[3];
         u64 winD[WP];
 #pragma unroll
-        for (int s = 0; s < 3; ++s) flip[s] = tepl_flips(win, 64 * s + lane);
+        for (int s = 0; s < 3; ++s) flip[s] = tep_flips(win, 64 * s + lane);
 #pragma unroll
         for (int q = 0; q < WP; ++q) winD[q] = use_hit ? hitD[q] : bestD[q];
         osdl_finish<WP>(L, S, flip, winD, f, n, k, lane, cw_out);

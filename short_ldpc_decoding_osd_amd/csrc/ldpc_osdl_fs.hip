@@ -1,7 +1,7 @@
 // OSD for longer and low-rate codes: the ldpc_osdl_fs_* and ldpc_osdl_tep_eval entry points.
 // For every code with n <= 384, 1 <= k <= 192 and 1 <= n - k <= 192: FS-OSD and the one-TEP primitive (device code:
 // ldpc_osdl_fs.h) on the front-end results of ldpc_osdl_front (ldpc_osdl.hip), which ldpc_osdl_fs_decode launches through
-// Osdl::front.  A translation unit of its own: ldpc_osdl.hip keeps the code object its register counts were measured on.
+// Osdl::front.  A translation unit of its own, so that ldpc_osdl.hip stays the code object of the front end and the conventional scan.
 // The FS visit-order table of k is in the context's OsdlTables (ldpc_osd_tables.h).  Validation, launches and the bodies of the
 // entry points are those of ldpc_osd_family.h, shared with ldpc_osdx.hip and ldpc_osdw.hip.
 #include "ldpc_osdl_fs.h"

@@ -3,7 +3,7 @@
 // frontier by (sum, insertion order), append the extended and then the adjacent child, the promising rule, the cost, the success
 // rule, the same bookkeeping of cmp, suc1, suc2, stop and ntep -- for k up to 192 and m = n - k up to 192: on SearchLLdsLean<WP>
 // (192 rows of P' of WP = ceil(m / 64) words, 192 + 64 WP weights, no byte LUTs), with osdl_prepare / osdl_finish
-// (ldpc_osdl_fs.h) as prologue and epilogue, one frame per wavefront.  The float conventions are those of
+// (ldpc_osdl.h) as prologue and epilogue, one frame per wavefront.  The float conventions are those of
 // oracle/ldpc_oracle.c orc_pb_osd with 64 replaced by k (MRB) and m (parity part).
 //
 // The frontier is the one of osdw_pb_kernel: a run owns a fixed slot of LDS, the slot number is the run's prefix and the slot
@@ -45,7 +45,7 @@
 #pragma once
 
 #include "ldpc_osd_tables.h"
-#include "ldpc_osdl_fs.h"
+#include "ldpc_osdl.h"
 #include "ldpc_pb_expf.h"
 #include "ldpc_pbx.h"
 

@@ -8,7 +8,8 @@
 // so the scan is the one of ldpc_osdx.h with 128 rows of P' and two words of MRB hard decisions.
 // The helpers of ldpc_wave.h and the metric of ldpc_search.h (tep_cost, tep_cost_bounded: templates on the LDS type, they read
 // only its byte LUTs) are used unchanged.  tep_apply and wave_argmin carry a one-word flip mask, which 127 MRB positions do not
-// fit: their counterparts without the mask are here (tepw_apply, tepw_flips, five lines of arg-min in the scan).
+// fit: their counterparts without the mask are here (tepw_apply, five lines of arg-min in the scan) and in ldpc_search.h
+// (tep_flips).
 #pragma once
 
 #include "ldpc_search.h"
@@ -208,12 +209,6 @@ __device__ __forceinline__ void tepw_apply(const SearchWLds &L, uchar4 s, u64 d0
     if (s.w > 2) { D ^= L.P[s.z]; mrb = mrb + L.w[s.z]; }
 }
 
-// whether the TEP flips primed MRB position p
-__device__ __forceinline__ bool tepw_flips(uchar4 s, int p)
-{
-    return (s.w > 0 && s.x == p) || (s.w > 1 && s.y == p) || (s.w > 2 && s.z == p);
-}
-
 __global__ __launch_bounds__(64) void osdw_search_kernel(const float *__restrict__ y, const int *__restrict__ index, const int *__restrict__ count,
         long long F, int n, int k, const unsigned char *__restrict__ perm_in, const u64 *__restrict__ parity_in,
         const uchar4 *__restrict__ teps, int ntep, u64 *__restrict__ cw_out, float *__restrict__ metric_out, int *__restrict__ best_out,
@@ -276,8 +271,8 @@ __global__ __launch_bounds__(64) void osdw_search_kernel(const float *__restrict
         if (bestt < ntep) win = teps[bestt];
         // ---- candidate -> codeword in ORIGINAL bit order, ceil(n / 64) words ---------------------
         const u64 par_bits = bestD ^ hp;
-        if (liveA && ((((hmA >> lane) & 1) != 0) != tepw_flips(win, lane))) atomicOr(&L.cw[oA >> 6], 1ull << (oA & 63));
-        if (liveB && ((((hmB >> lane) & 1) != 0) != tepw_flips(win, 64 + lane))) atomicOr(&L.cw[oB >> 6], 1ull << (oB & 63));
+        if (liveA && ((((hmA >> lane) & 1) != 0) != tep_flips(win, lane))) atomicOr(&L.cw[oA >> 6], 1ull << (oA & 63));
+        if (liveB && ((((hmB >> lane) & 1) != 0) != tep_flips(win, 64 + lane))) atomicOr(&L.cw[oB >> 6], 1ull << (oB & 63));
         if (liveP && ((par_bits >> lane) & 1)) atomicOr(&L.cw[oP >> 6], 1ull << (oP & 63));
         wave_fence();
         if (lane < words) cw_out[f * words + lane] = L.cw[lane];

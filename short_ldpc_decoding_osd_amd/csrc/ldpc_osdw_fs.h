@@ -23,9 +23,10 @@ struct __attribute__((aligned(16))) SearchWLdsLean {   // the same without the b
 // per-frame prologue and epilogue of the FS scan and the one-TEP kernel (osdx_prepare / osdx_finish of ldpc_osdx.h with two MRB
 // slots per lane).  They are the prologue and epilogue of osdw_search_kernel (ldpc_osdw.h) word for word, as a COPY: with that
 // kernel built on these helpers the compiler allocated it 59 vector registers instead of the 61 its measurements were taken
-// with, so it keeps its own text and its own code object.  Idle lanes (lane >= k, 64 + lane >= k, lane >= n - k) stay out of the
-// hard-decision ballots -- their y = 0 would count as a hard 1 --, rows of P' are masked to n - k columns, and w[] is zero
-// beyond the live positions.
+// with and, the scan loop the same instructions, the launch measured 0.8 % and 0.5 % above this text on CCSDS (128,64) in two
+// alternating sessions, above the spread of this text's own runs (profiles/osd_scan_shared/README.md): it keeps its own text.
+// Idle lanes (lane >= k, 64 + lane >= k, lane >= n - k) stay out of the hard-decision ballots -- their y = 0 would count as a
+// hard 1 --, rows of P' are masked to n - k columns, and w[] is zero beyond the live positions.
 //   LDS: SearchWLds (LUTS = true: the eight byte LUTs over w[128..] are built) or SearchWLdsLean (LUTS = false).
 // ---------------------------------------------------------------------------------------
 struct OsdwFrame {
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(64) void osdw_fs_kernel(const float *__restrict__ y
         uchar4 win;   // rank 0 -- the all-zero TEP, also of a frame where nothing was found -- flips nothing
         win.x = win.y = win.z = win.w = 0;
         if (pos >= 0) win = teps_fs[pos];
-        osdw_finish(L, S, tepw_flips(win, lane), tepw_flips(win, 64 + lane), use_hit ? hitD : bestD, f, words, lane, cw_out);
+        osdw_finish(L, S, tep_flips(win, lane), tep_flips(win, 64 + lane), use_hit ? hitD : bestD, f, words, lane, cw_out);
         store_results(f, lane, use_hit ? hitc : best, use_hit ? hitidx : bestidx, ntep, metric_out, best_out, ntep_out);
         if (label) { seen += 1; wrong += cw_wrong(L, label, src, words); nteps += ntep_out ? (unsigned long long)ntep : 0ull; }
         wave_fence();

@@ -192,6 +192,12 @@ __device__ __forceinline__ void tep_apply(const SearchLds &L, uchar4 s, u64 d0, 
     if (s.w > 2) { D ^= L.P[s.z]; E |= 1ull << s.z; mrb = mrb + L.w[s.z]; }
 }
 
+// whether the TEP flips primed MRB position p (the families that remember a winner as its table entry, not as a flip mask)
+__device__ __forceinline__ bool tep_flips(uchar4 s, int p)
+{
+    return (s.w > 0 && s.x == p) || (s.w > 1 && s.y == p) || (s.w > 2 && s.z == p);
+}
+
 // wave arg-min on (cost, index): every lane returns the winner
 __device__ __forceinline__ void wave_argmin(float &best, int &bestt, u64 &bestD, u64 &bestE, int lane)
 {

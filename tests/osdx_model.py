@@ -37,6 +37,12 @@ def frames(name, snr, B, seed):
     return np_oracle.make_frames(graph(name)[1], snr, B, np.random.default_rng(seed))
 
 
+def saturated_frames(G):
+    """Two frames with every |y| = 3.0e38 and signs no codeword has: any two disagreements overflow the metric to +inf."""
+    s = np.random.default_rng(38).integers(0, 2, (2, np.asarray(G).shape[1]))
+    return np.where(s, -3.0e38, 3.0e38).astype(np.float32)
+
+
 def _pack_rows(bits):
     """[r, c <= 64] 0/1 -> [r] uint64, bit c of row r."""
     bits = np.asarray(bits, dtype=np.uint8)

@@ -122,6 +122,25 @@ def test_front_end_awkward_inputs(name):
     assert_front(got, osdx_model.front_oracle(G, y), dec.n, dec.k)
 
 
+def test_scan_without_a_finite_cost_flips_nothing():
+    """Order 1 on frames whose every cost is +inf: the scan holds no candidate -- best = 0x7FFFFFFF, the metric +inf and no MRB
+    flip: the codeword words are the hard decisions.  (ldpc_osdl_search takes the first TEP there: tests/test_gpu_osdl.py.)"""
+    dec = decoder("short")
+    G = osdx_model.graph("short")[1]
+    y = osdx_model.saturated_frames(G)
+    with np.errstate(over="ignore"):
+        ref = osdx_model.scan_oracle(G, y, 1)
+    assert np.isposinf(ref["metric"]).all() and (ref["ties"] == ref["ntep"]).all()    # premise: every cost is +inf
+    assert not ref["best"].any()                                 # (np.argmin names the first TEP there; these kernels name none)
+    hard = pack_np((y < 0).astype(np.uint8))                     # nothing flipped, no discrepancy taken over: the hard decisions of y
+    for out in (dec.osdx_decode(to_dev(y, dec), 1), dec.osdx_search(to_dev(y, dec), *dec.osdx_front(to_dev(y, dec))[:2], 1)):
+        torch.cuda.synchronize()
+        assert np.array_equal(words_np(out["cw"]), hard)
+        assert np.isposinf(out["metric"].cpu().numpy()).all()
+        assert (out["best"].cpu().numpy() == 0x7FFFFFFF).all()
+        assert np.array_equal(out["ntep"].cpu().numpy(), ref["ntep"])
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 3, 4: the scan
 # ---------------------------------------------------------------------------------------------------------------------
