@@ -28,7 +28,19 @@ SIGS = {
                           "soft_margin", "fcn_weights", "n_weights", "group", "d_label_bits", "d_deep_limit", "d_global_min",
                           "d_truth", "d_success", "d_cw", "d_metric", "d_best", "d_teps_evaluated"),
 }
-_SCALARS = {"B": 0, "F": 0, "T": 0, "w_in": 1.0, "w_out": 1.0, "kernel": 0, "nblk": 0, "win": 0, "soft_margin": 0.0,
+# the G-form families (any shape, high rate, long / low rate) share their signatures
+_FRONT_RESULTS = ("d_y", "d_index", "d_count", "F", "d_perm", "d_parity")
+_SCAN_OUT = ("d_cw", "d_metric", "d_best", "d_ntep")
+_DECODE_TAIL = ("d_perm", "d_parity") + _SCAN_OUT + ("d_label_bits", "d_counts")
+for _fam in ("osdx", "osdw", "osdl"):
+    SIGS[f"ldpc_{_fam}_front"] = SIGS["ldpc_osd_front"]
+    SIGS[f"ldpc_{_fam}_search"] = _FRONT_RESULTS + ("order",) + _SCAN_OUT
+    SIGS[f"ldpc_{_fam}_decode"] = ("d_y", "d_index", "d_count", "F", "order") + _DECODE_TAIL
+    SIGS[f"ldpc_{_fam}_tep_eval"] = SIGS["ldpc_osd_tep_eval"]
+    for _algo in ("fs", "pb"):
+        SIGS[f"ldpc_{_fam}_{_algo}_search"] = _FRONT_RESULTS + ("params",) + _SCAN_OUT
+        SIGS[f"ldpc_{_fam}_{_algo}_decode"] = ("d_y", "d_index", "d_count", "F", "params") + _DECODE_TAIL
+_SCALARS = {"B": 0, "F": 0, "T": 0, "order": 0, "w_in": 1.0, "w_out": 1.0, "kernel": 0, "nblk": 0, "win": 0, "soft_margin": 0.0,
             "n_weights": 0, "group": 0}
 
 
@@ -73,7 +85,8 @@ def alpha_array(alpha, T):
 
 
 # ---- sentinels: a value no kernel writes, per dtype
-SENT = {torch.int64: 0x5A5A5A5A5A5A5A5A, torch.float32: -7.0, torch.int32: -7, torch.uint8: 0xEE}
+SENT = {torch.int64: 0x5A5A5A5A5A5A5A5A, torch.float32: -7.0, torch.int32: -7, torch.uint8: 0xEE,
+        torch.int16: 0x6EEE}
 
 
 def sentinel(dec, shape, dtype):

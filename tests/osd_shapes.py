@@ -33,6 +33,7 @@ import functools
 import numpy as np
 
 from oracle import np_oracle
+from tests import osd_family as OF
 from tests import osd_generators, osdw_model, osdx_model
 
 F32 = np.float32
@@ -139,7 +140,7 @@ def pack(P, rows):
     F, k, _ = P.shape
     out = np.zeros((F, rows), np.uint64)
     for f in range(F):
-        out[f, :k] = osdx_model._pack_rows(P[f])
+        out[f, :k] = OF.pack_rows(P[f], 1)[:, 0]
     return out
 
 

@@ -1,11 +1,12 @@
 """Test helper: the inputs of the FS-OSD and one-TEP tests of the long / low-rate family (ldpc_osdl_fs_search / _fs_decode /
 _tep_eval).  The CPU oracle is tests/osdx_fs_model.py, which serves any (k, n) as it is; here are the codes, frames and
-parameter sets, the front-end results in the osdl layouts (perm [F, 64 S] u16, parity [F, 64 W, Wp] u64), ``planted`` in those
-layouts and W-word masks.  tests/test_osdl_fs_host.py asserts the coverage of these inputs without a GPU."""
+parameter sets and the awkward frames; ``planted`` and ``split_masks`` bind the shared constructions to the osdl layouts
+(perm [F, 64 S] u16, parity [F, 64 W, Wp] u64, W-word masks).  tests/test_osdl_fs_host.py asserts the coverage of these inputs without a GPU."""
 import functools
 
 import numpy as np
 
+from tests import osd_family as OF
 from tests import osdl_model
 from tests import osdx_fs_model as M
 
@@ -70,30 +71,20 @@ def span(support):
 
 
 def spans(name):
-    """-> (winner spans, stopping-candidate spans): the set of span() values over the reference-quirk winners (rank > 0) and over
-    the tau_e stopping candidates of every frame and parameter set of ``name``."""
-    _, _, _, b, order, sets, _ = parity_case(name)
-    win, stop = set(), set()
-    for s in sets:
-        for scan in b.scans:
-            r = scan.fs(order, *s)
-            if r["ref"][0]:
-                win.add(span(r["ref"][0]))
-            if r["hit"] is not None and r["hit"][0]:
-                stop.add(span(r["hit"][0]))
-    return win, stop
+    """osdx_fs_model.spans over the parity case of ``name`` with this module's span()."""
+    return M.spans(parity_case(name), span)
 
 
 def split_masks(masks, W):
     """Python-int masks (bit p = flip MRB position p < 64 W) -> [F, W] u64 in the layout of ldpc_osdl_tep_eval."""
-    return np.array([[(int(m) >> (64 * w)) & ((1 << 64) - 1) for w in range(W)] for m in masks], dtype=np.uint64).reshape(len(masks), W)
+    return OF.OSDL.split_masks(masks, 64 * W)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # a planted stop
 # ---------------------------------------------------------------------------------------------------------------------
 PLANTED_SHAPES = {3: ((40, 140), (70, 200)), 2: ((130, 321), (192, 384))}       # weight class -> (k, n)
-PLANTED_TAU_E = {3: 3.5, 2: 2.5}
+PLANTED_TAU_E = M.PLANTED_TAU_E
 PLANTED = [(k, n, w, which) for w in (3, 2) for (k, n) in PLANTED_SHAPES[w] for which in ("first", "middle", "last")]
 # Beside those twelve, at (192,384): the support {63, 64}, once as the tau_e stop and once -- under a tau_e nothing meets -- as
 # the winner of the full scan.  The natural frames of wl384 have no winner and no stopping candidate across positions 63 / 64
@@ -102,48 +93,12 @@ ACROSS = [(192, 384, 2, "across", 2.5), (192, 384, 2, "across", 0.5)]
 PLANTED_CODE = {(130, 321): "s321_130", (192, 384): "wl384"}                    # the contexts of the planted cases
 
 
-def classes_before(k, weight):
-    """The TEPs visited before weight class ``weight``: the all-zero TEP and the lighter classes."""
-    return 1 + (k if weight > 1 else 0) + (k * (k - 1) // 2 if weight > 2 else 0)
+classes_before = M.classes_before
 
 
-@functools.lru_cache(maxsize=None)
 def planted(k, n, weight, which, tau_e=None, seed=5):
-    """osdx_fs_model.planted in the osdl layouts, for weight class 2 or 3: caller-made front-end results with a tau_e stop
-    (3.5 in class 3, 2.5 in class 2) planted at a chosen rank of the class -- "first" (a rank of its first round), "middle",
-    "last" (the last, partial round), or "across" (the support {63, 64} of class 2; ``tau_e`` then as given).  Identity
-    permutation, random rows of P' (large mutual distance), y' whose hard decisions make d0 the sum of the support's rows of
-    P': that TEP then has HD = weight and, as the model confirms, nothing before it has HD <= weight.  tau_psc = n: every
-    candidate is eligible, so the reference-quirk answer is a search result.
-    -> dict(y [1, n], perm [1, 64 S] u16, parity [1, 64 W, Wp] u64, batch, support, rank, at, params (order, beta, tau_e, tau_psc))."""
-    m = n - k
-    sup = M.class_supports(k, weight)
-    cnt = len(sup)
-    assert cnt % 64, "the last round must be partial"
-    rank = M.fs_rank(k, (63, 64)) if which == "across" else {"first": 37, "middle": (cnt // 128) * 64 + 21,
-                                                             "last": (cnt // 64) * 64 + (cnt % 64) // 2}[which]
-    support = tuple(int(x) for x in sup[rank])
-    rng = np.random.default_rng(seed)
-    P = rng.integers(0, 2, (k, m), dtype=np.int64)
-    Gp = np.concatenate([np.eye(k, dtype=np.int64), P], axis=1)
-    u0 = rng.integers(0, 2, k, dtype=np.int64)
-    hp = (u0.dot(P) + P[list(support)].sum(axis=0)) % 2        # d0 = (u0 . P') ^ hp = the sum of the support's rows
-    mag = np.concatenate([np.linspace(0.5, 0.05, k), rng.uniform(0.6, 1.5, m)]).astype(F32)
-    y = (np.where(np.concatenate([u0, hp]) == 1, -1.0, 1.0) * mag).astype(F32)[None, :]
-    perm, parity = osdl_model.pack_front(np.arange(n), Gp)
-    return dict(y=y, perm=perm[None], parity=parity[None], batch=M.Batch(y, perm[None], [Gp]), support=support, rank=rank,
-                at=classes_before(k, weight) + rank,
-                params=(weight, 0.0, PLANTED_TAU_E[weight] if tau_e is None else tau_e, float(n)))
+    """osdx_fs_model.planted_stop in the osdl layouts (perm [1, 64 S] u16, parity [1, 64 W, Wp] u64), tau_psc = n."""
+    return M.planted_stop(OF.OSDL, k, n, weight, which, tau_e, seed=seed)
 
 
-@functools.lru_cache(maxsize=None)
-def planted_graph(k, n):
-    """(H, G) of a code of shape (k, n) to hold the context of a planted case (the search never reads G; the caller brings
-    the front-end results): the family's own code of that shape, else H = [A | I] as osdl_model builds its synthetic codes."""
-    if (k, n) in PLANTED_CODE:
-        return osdl_model.graph(PLANTED_CODE[(k, n)])
-    from oracle import np_oracle
-    H = osdl_model._h_systematic(n, k)
-    G = np_oracle.generator_from_H(H)
-    assert G.shape == (k, n)
-    return H, G
+planted_graph = OF.shape_graph       # (k, n) -> (H, G) of the context of a planted case

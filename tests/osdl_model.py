@@ -1,11 +1,12 @@
-"""Test helper: the codes, the layouts and the CPU oracles of the long / low-rate OSD entry points (ldpc_osdl_*: n <= 384,
+"""Test helper: the codes, frames and constructed inputs of the long / low-rate OSD entry points (ldpc_osdl_*: n <= 384,
 1 <= k <= 192, 1 <= n-k <= 192).
 
-  codes          wl384: the reference's wimax-like (384,192) code (tests/golden/); six synthetic codes from H = [A | I_m] with
-                 seeded random columns of A, built as osdw_model._synthetic builds its own; the cross-checks ccsds, ldpc_96_48,
-                 array_121_80 and s128_96, which ldpc_osdx_* or ldpc_osdw_* serve as well; four refused shapes
+  codes          wl384: the reference's wimax-like (384,192) code (tests/golden/); six synthetic codes of
+                 osd_family.h_systematic (H = [A | I_m]); the cross-checks ccsds, ldpc_96_48, array_121_80 and s128_96, which
+                 ldpc_osdx_* or ldpc_osdw_* serve as well; four refused shapes.  make_code / graph resolve every name of the
+                 three families' model modules
   layouts        S = ceil(n/64), W = ceil(k/64), Wp = ceil((n-k)/64): perm [F, 64 S] u16, parity [F, 64 W, Wp] u64
-  front_oracle   the C oracle's general orc_osd_front, frame by frame, packed into those layouts
+                 (osd_family.OSDL; pack_front / unpack_front / front_oracle are its bindings)
   scan oracle    osdx_model.scan_oracle takes a ``front`` tuple and uses only its perm and Gps: it serves any shape as it is
   constructed    reliability orders that make the front end take the paths natural frames leave out (premises: test_osdl_host)
 """
@@ -16,6 +17,7 @@ import numpy as np
 
 from oracle import c_oracle, np_oracle
 from tests import nms_graphs, osd_adversary, osdw_model, osdx_model
+from tests import osd_family as OF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WL384 = os.path.join(ROOT, "tests", "golden", "wimaxlike_N384_K192_P16_set0.alist")
@@ -28,16 +30,6 @@ SERVED = NEW + CROSS
 LIMITS = (384, 192, 192)                                                    # n, k, n - k
 
 
-def _h_systematic(n, k, colw=3):
-    """H = [A | I_m] from default_rng(5), column c of A gets min(m, colw) ones (osdw_model._synthetic's construction)."""
-    rng = np.random.default_rng(5)
-    m = n - k
-    A = np.zeros((m, k), np.int64)
-    for c in range(k):
-        A[rng.choice(m, size=min(m, colw), replace=False), c] = 1
-    return np.concatenate([A, np.eye(m, dtype=np.int64)], axis=1)
-
-
 @functools.lru_cache(maxsize=None)
 def graph(name):
     """-> (H, G) int64 of ``name``."""
@@ -46,10 +38,7 @@ def graph(name):
         return c.H, c.G
     if name in SYNTH or name in REFUSED:
         n, k = (SYNTH.get(name) or REFUSED[name])
-        H = _h_systematic(n, k)
-        G = np_oracle.generator_from_H(H)
-        assert G.shape == (k, n)
-        return H, G
+        return OF.h_systematic(n, k)
     if name == "wimax_1056":
         return nms_graphs.graph(name)
     return osdw_model.graph(name) if name in osdw_model.CODES else osdx_model.graph(name)
@@ -81,54 +70,9 @@ def frames(name, snr, B, seed):
 
 
 # ------------------------------------------------------------------------------------------------ layouts
-def pack_rows(bits, words):
-    """[r, c <= 64 words] 0/1 -> [r, words] uint64: bit c % 64 of word c // 64."""
-    bits = np.asarray(bits, dtype=np.uint8)
-    pad = np.zeros((bits.shape[0], 64 * words - bits.shape[1]), np.uint8)
-    return np.packbits(np.concatenate([bits, pad], axis=1), axis=1, bitorder="little").view(np.uint64).reshape(bits.shape[0], words)
-
-
-def unpack_rows(words, cols):
-    """The inverse of pack_rows: [r, words] uint64 -> [r, cols] 0/1."""
-    words = np.ascontiguousarray(words, dtype=np.uint64)
-    return np.unpackbits(words.view(np.uint8).reshape(words.shape[0], -1), axis=1, bitorder="little")[:, :cols]
-
-
-def pack_front(perm, Gp):
-    """One frame's (perm [n], [I | P'] [k, n]) -> (perm [64 S] u16, parity [64 W, Wp] u64), zero in the padding."""
-    k, n = Gp.shape
-    S, W, Wp = (n + 63) // 64, (k + 63) // 64, (n - k + 63) // 64
-    p = np.zeros(64 * S, np.uint16)
-    p[:n] = perm
-    q = np.zeros((64 * W, Wp), np.uint64)
-    q[:k] = pack_rows(Gp[:, k:], Wp)
-    return p, q
-
-
-def unpack_front(p, q, n, k):
-    """The inverse of pack_front -> (perm [n], P' [k, n-k])."""
-    return np.asarray(p[:n], dtype=np.int64), unpack_rows(np.asarray(q)[:k], n - k)
-
-
-def front_oracle(G, y, swaps=False):
-    """-> (perm [F, 64 S] u16, parity [F, 64 W, Wp] u64, nswaps [F] i32, Gp list) in the layouts of ldpc_osdl_front.
-    ``swaps``: a fifth member, the recorded exchanges [(a, b), ...] per frame."""
-    G = np.asarray(G)
-    k, n = G.shape
-    y = np.asarray(y, dtype=np.float32)
-    S, W, Wp = (n + 63) // 64, (k + 63) // 64, (n - k + 63) // 64
-    perm = np.zeros((len(y), 64 * S), np.uint16)
-    parity = np.zeros((len(y), 64 * W, Wp), np.uint64)
-    ns = np.zeros(len(y), np.int32)
-    Gps, sws = [], []
-    for f, row in enumerate(y):
-        p, Gp, sw = c_oracle.osd_front(G, row)
-        assert np.array_equal(Gp[:, :k], np.eye(k, dtype=np.int32))
-        perm[f], parity[f] = pack_front(p, Gp)
-        ns[f] = len(sw)
-        Gps.append(Gp.astype(np.int64))
-        sws.append(list(sw))
-    return (perm, parity, ns, Gps, sws) if swaps else (perm, parity, ns, Gps)
+pack_rows, unpack_rows = OF.pack_rows, OF.unpack_rows
+pack_front, unpack_front = OF.OSDL.pack_front, OF.OSDL.unpack_front
+front_oracle = functools.partial(OF.front_oracle, fam=OF.OSDL)       # (G, y, swaps=False) -> perm [F, 64 S] u16, parity [F, 64 W, Wp] u64, ...
 
 
 def scan_oracle(G, y, order, front):
@@ -136,22 +80,6 @@ def scan_oracle(G, y, order, front):
     its float32 sums to +inf on purpose: NumPy's warning about it is switched off.)"""
     with np.errstate(over="ignore"):
         return osdx_model.scan_oracle(G, y, order, front[:4])
-
-
-def self_check(name, order=1, frames_=2, seed=5):
-    """osdx_model.self_check at any order: the two front-end oracles agree and the vectorised scan costs equal
-    np_oracle.convention_osd's, bit for bit."""
-    G = graph(name)[1]
-    y, cw = frames(name, 1.5, frames_, seed)
-    for row, lab in zip(y, cw):
-        yp, labp, Gp, perm, _ = np_oracle.swapped_info(row, lab, G)
-        ref = np_oracle.convention_osd(yp, labp, Gp, order)
-        cost, cand = osdx_model.scan_frame(yp, Gp, order)
-        assert np.array_equal(cost.view(np.uint32), ref["costs"].view(np.uint32))
-        assert int(np.argmin(cost)) == ref["best_index"] and np.array_equal(cand[ref["best_index"]], ref["codeword"])
-        p_c, Gp_c, _ = c_oracle.osd_front(G, row)
-        assert np.array_equal(p_c, perm) and np.array_equal(Gp_c, Gp)
-    return True
 
 
 # ------------------------------------------------------------------------------------------------ inputs

@@ -1,17 +1,12 @@
-"""Test helper: the CPU model of PB-OSD for any (k, n) with n - k <= 192, in the device layouts of ldpc_osdl_pb_search /
-_pb_decode, and the inputs of tests/test_gpu_osdl_pb.py (tests/test_osdl_pb_host.py asserts their premises without a GPU).
-
-The model is tests/osdx_pb_model._pb_frame with 8 ceil(m / 64) byte tables in place of 8 (m = n - k): the parity discrepancy is
-an integer of m bits, the metric adds the byte sums of word 0, then of word 1, then of word 2 to the reliability sum, each
-byte's set positions ascending from 0.0f.  det_expf, binom_cdf and the tags are that module's.  Where m <= 64 the two models
-are the same arithmetic, and ``pb`` here equals ``osdx_pb_model.pb`` exactly (asserted on the host).
+"""Test helper: the inputs of tests/test_gpu_osdl_pb.py in the osdl layouts (tests/test_osdl_pb_host.py asserts their premises
+without a GPU): natural and quantised frames, loud and quiet noiseless frames per slot tier, equal magnitudes.  The CPU model is
+tests/osdx_pb_model.py (``pb``), which serves any (k, n); this module owns no arithmetic.
 """
 import functools
-import heapq
-import math
 
 import numpy as np
 
+from tests import osd_family as OF
 from tests import osdl_model
 from tests import osdx_pb_model as M
 
@@ -19,139 +14,7 @@ F32 = np.float32
 det_expf, binom_cdf, quantise, tag_counts, frontier_bound = M.det_expf, M.binom_cdf, M.quantise, M.tag_counts, M.frontier_bound
 
 
-def _bits_int(bits):
-    return int.from_bytes(np.packbits(np.asarray(bits, dtype=np.uint8), bitorder="little").tobytes(), "little")
-
-
-def pb_frame(yp, Gp, order, snr_db):
-    """One frame in the primed domain -> dict(support, cand [n], metric, best, ntep, aux (cmp, suc1, suc2, stop), tags, peak)."""
-    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
-        return _pb_frame(np.asarray(yp, dtype=F32), np.asarray(Gp, dtype=np.int64), order, snr_db)
-
-
-def _pb_frame(yp, Gp, order, snr_db):
-    k, n = Gp.shape
-    m = n - k
-    nb = 8 * ((m + 63) // 64)
-    w = np.abs(yp)
-    hard = np.where(yp > 0, 0, 1).astype(np.int64)
-    P = [_bits_int(Gp[r, k:]) for r in range(k)]
-    d0 = _bits_int(hard[k:])
-    for r in range(k):
-        if hard[r]:
-            d0 ^= P[r]
-    # byte tables of the parity part: each byte's set positions ascending from 0.0f (a position beyond n adds nothing)
-    wp = np.zeros(8 * nb, F32)
-    wp[:m] = w[k:]
-    lut = np.zeros((nb, 256), F32)
-    for b in range(nb):
-        for t in range(8):
-            lut[b, 1 << t:2 << t] = lut[b, 0:1 << t] + wp[8 * b + t]
-
-    def cost(mrb, D):
-        acc = F32(mrb)
-        for b in range(nb):
-            acc = F32(acc + lut[b, (D >> (8 * b)) & 0xFF])
-        return acc
-
-    c4 = F32(-4.0 * (1.0 / math.pow(10.0, float(F32(snr_db)) / 10.0)))
-    q = [F32(F32(1.0) / F32(F32(1.0) + det_expf(-F32(c4 * w[p])))) for p in range(n)]
-    acc, accw = F32(0), F32(0)
-    for p in range(k, n):
-        acc = F32(acc + q[p])
-        accw = F32(accw + w[p])
-    p1, lrb_mean = F32(acc / F32(m)), F32(accw / F32(m))
-    acc, spl = F32(0), F32(1)
-    for p in range(k):
-        acc = F32(acc + q[p])
-        spl = F32(spl * F32(F32(1.0) - q[p]))
-    pt = F32(acc / F32(k))
-    cdfA, cdfH = binom_cdf(m, float(p1)), binom_cdf(m, 0.5)
-    niu = binom_cdf(k, float(pt))[order]
-    nmax = sum(math.comb(k, i) for i in range(order + 1))
-    p_t_suc, p_t_pro = 0.99 * niu, 0.002 * math.sqrt((1.0 - niu) / float(nmax))
-
-    best, best_sup, best_D, best_idx = cost(F32(0), d0), (), d0, 0
-    ntep, stop, cmp_, suc1, suc2, peak = nmax, 0, 0, 0, 0, 0
-    tags = set()
-    heap = [(float(w[k - 1]), 0, (k - 1,))] if order > 0 else []
-    seq = 1
-    for j in range(nmax - 1):
-        peak = max(peak, len(heap))
-        cmp_ += 1 if len(heap) == 1 else 2
-        s, _, sup = heapq.heappop(heap)
-        if heap and heap[0][0] == s:
-            tags.add("tie")
-        rs = F32(s)
-        last, wt = sup[-1], len(sup)
-        if last < k - 1 and wt < order:
-            heapq.heappush(heap, (float(F32(rs + w[k - 1])), seq, sup + (k - 1,)))
-            seq += 1
-        if (last - sup[-2] > 1) if wt > 1 else (last - 1 >= 0):
-            child = sup[:-1] + (last - 1,)
-            a = w[child[0]]
-            for p in child[1:]:
-                a = F32(a + w[p])
-            heapq.heappush(heap, (float(a), seq, child))
-            seq += 1
-        w1 = F32(det_expf(F32(c4 * rs)) * spl)
-        w2 = F32(F32(1.0) - w1)
-        bt = np.floor(F32(F32(best - rs) / lrb_mean))
-        beta = (int(bt) if bt < F32(m) else m) if bt > 0 else 0
-        bs = F32(F32(0.0) + F32(w1 * F32(cdfA[beta])))
-        bs = F32(bs + F32(w2 * F32(cdfH[beta])))
-        if float(bs) < p_t_pro:
-            stop, ntep = 1, j + 1
-            break
-        D = d0
-        for p in sup:
-            D ^= P[p]
-        c = cost(rs, D)
-        suc1 += 1
-        if c < best:
-            best, best_sup, best_D, best_idx = c, sup, D, j + 1
-            suc2 += 1
-            if j + 1 >= 64:
-                tags.add("late_improvement")
-            prod = F32(1.0)
-            for p in range(m):
-                prod = F32(prod * (F32(F32(2.0) * q[k + p]) if (D >> p) & 1 else F32(F32(2.0) * F32(F32(1.0) - q[k + p]))))
-            p_suc = F32(F32(1.0) / F32(F32(1.0) + F32(F32(F32(F32(1.0) - w1) / w1) / prod)))
-            if p_suc > F32(p_t_suc):
-                stop, ntep = 2, j + 1
-                break
-    tags.add(f"stop{stop}")
-    if best_idx:
-        tags.add("improved")
-    assert peak <= frontier_bound(k), (peak, k)
-    cand = hard.copy()
-    for p in best_sup:
-        cand[p] ^= 1
-    for c in range(m):
-        cand[k + c] = hard[k + c] ^ ((best_D >> c) & 1)
-    return dict(support=best_sup, cand=cand, metric=best, best=best_idx, ntep=ntep, aux=(cmp_, suc1, suc2, stop), tags=tags,
-                peak=peak)
-
-
-def pb(y, perm, Gps, order, snr_db):
-    """Frames y [F, n] in original order with front-end results (perm [F, >= n], Gps: [I | P'] per frame) -> dict of arrays in
-    the layouts of ldpc_osdl_pb_search: cw [F, words] u64, metric [F] f32, best / ntep [F] i32, aux [F, 4] i32, and tags (a
-    list of sets), peak [F], supports (a list of tuples)."""
-    y = np.asarray(y, dtype=F32)
-    k, n = np.asarray(Gps[0]).shape
-    F = len(y)
-    bits = np.zeros((F, n), np.uint8)
-    out = dict(metric=np.zeros(F, F32), best=np.zeros(F, np.int32), ntep=np.zeros(F, np.int32), aux=np.zeros((F, 4), np.int32),
-               tags=[], peak=np.zeros(F, np.int64), supports=[])
-    for f in range(F):
-        p = np.asarray(perm[f][:n]).astype(np.int64)
-        r = pb_frame(y[f][p], Gps[f], order, snr_db)
-        bits[f, p] = r["cand"]
-        out["metric"][f], out["best"][f], out["ntep"][f], out["aux"][f], out["peak"][f] = r["metric"], r["best"], r["ntep"], r["aux"], r["peak"]
-        out["tags"].append(r["tags"])
-        out["supports"].append(r["support"])
-    out["cw"] = M._pack(bits)
-    return out
+pb, pb_frame = M.pb, M.pb_frame
 
 
 def span(sup):
@@ -166,28 +29,15 @@ def span(sup):
 TIER_SLOTS = (2048, 4096, 8064, 18368)
 
 
-def slots3(k):
-    return k + (k - 1) * (k - 2) // 2
-
-
-def tier(k):
-    return min(t for t in TIER_SLOTS if slots3(k) <= t)
+slots3, tier = M.slots3, functools.partial(M.tier, slots=TIER_SLOTS)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# codes: the named ones of osdl_model, or a shape (k, n): H = [A | I] of osdl_model._h_systematic
+# codes: the named ones of osdl_model, or a shape (k, n): osd_family.shape_graph
 # ---------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
 def graph(code):
     """-> (H, G) of a name of osdl_model or of a shape (k, n)."""
-    if isinstance(code, tuple):
-        from oracle import np_oracle
-        k, n = code
-        H = osdl_model._h_systematic(n, k)
-        G = np_oracle.generator_from_H(H)
-        assert G.shape == (k, n)
-        return H, G
-    return osdl_model.graph(code)
+    return OF.shape_graph(*code) if isinstance(code, tuple) else osdl_model.graph(code)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -249,25 +99,6 @@ def in_turn(code, order, loud=2, quiet=2):
 EQUAL = ((100, 200, 2, 1, 2), (100, 200, 2, 2, 2), (150, 321, 2, 1, 1), (150, 321, 2, 2, 1), (70, 200, 3, 1, 1))   # (k, n, order, levels, frames)
 
 
-@functools.lru_cache(maxsize=None)
 def equal_magnitudes(k, n, order, levels, F, seed=11):
-    """osdx_pb_model.equal_magnitudes in the osdl layouts: identity permutation, random P', |y'| equal over the MRB (levels = 1)
-    or of two distinct values (levels = 2), so that the sums of one weight tie and the visit order is the insertion order.
-    -> dict(y [F, n], perm, parity, order, snr_db, model)."""
-    m = n - k
-    rng = np.random.default_rng(seed)
-    ys, Gps, perms, pars = [], [], [], []
-    for f in range(F):
-        Pm = rng.integers(0, 2, (k, m), dtype=np.int64)
-        Gp = np.concatenate([np.eye(k, dtype=np.int64), Pm], axis=1)
-        p, q = osdl_model.pack_front(np.arange(n), Gp)
-        Gps.append(Gp), perms.append(p), pars.append(q)
-        mrb = np.full(k, 0.75, F32)
-        if levels == 2:
-            mrb[rng.random(k) < 0.5] = F32(0.5)
-        mag = np.concatenate([mrb, rng.uniform(0.3, 1.2, m).astype(F32)]).astype(F32)
-        sign = np.where(rng.integers(0, 2, n) == 1, F32(-1), F32(1))
-        ys.append(mag * sign)
-    y = np.ascontiguousarray(np.stack(ys), dtype=F32)
-    perm, parity = np.stack(perms), np.stack(pars)
-    return dict(y=y, perm=perm, parity=parity, order=order, snr_db=1.0, model=pb(y, perm, Gps, order, 1.0))
+    """osdx_pb_model.equal_magnitudes_in in the osdl layouts."""
+    return M.equal_magnitudes_in(OF.OSDL, k, n, order, levels, F, seed)

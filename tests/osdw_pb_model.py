@@ -1,13 +1,14 @@
 """Test helper: the inputs of the PB-OSD tests of the high-rate family (ldpc_osdw_pb_search / _pb_decode).  The CPU model is
 tests/osdx_pb_model.py, which serves any k as it is; here are the codes, frames and parameter sets, the front-end results in the
-osdw layouts (parity [F,128]), the wide variants of ``equal_magnitudes`` and ``in_turn``, the shape edges and the largest
-frontier.  tests/test_osdw_pb_host.py asserts the coverage of these inputs without a GPU."""
+osdw layouts (parity [F,128]), ``equal_magnitudes`` bound to those layouts, this family's ``in_turn`` frames, the shape edges
+and the largest frontier.  tests/test_osdw_pb_host.py asserts the coverage of these inputs without a GPU."""
 import functools
 
 import numpy as np
 
 from tests import osd_shapes as S
-from tests import osdw_fs_model, osdw_model, osdx_model
+from tests import osd_family as OF
+from tests import osdw_fs_model, osdw_model
 from tests import osdx_pb_model as M
 
 F32 = np.float32
@@ -29,12 +30,7 @@ EVERY_TAG = ("stop0", "stop1", "stop2", "improved", "tie", "late_improvement")
 TIER_SLOTS = (2048, 4096, 8064)
 
 
-def slots3(k):
-    return k + (k - 1) * (k - 2) // 2
-
-
-def tier(k):
-    return min(t for t in TIER_SLOTS if slots3(k) <= t)
+slots3, tier = M.slots3, functools.partial(M.tier, slots=TIER_SLOTS)
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,29 +92,9 @@ def order3_frame(k, n, snr_db):
 EQUAL = ((80, 121, 2, 1, 3), (80, 121, 2, 2, 3), (67, 100, 3, 1, 1))      # (k, n, order, levels, frames)
 
 
-@functools.lru_cache(maxsize=None)
 def equal_magnitudes(k, n, order, levels, F, seed=11):
-    """osdx_pb_model.equal_magnitudes with two-word parity: identity permutation, random P', |y'| equal over the MRB (levels = 1)
-    or of two distinct values (levels = 2), so that the sums of one weight tie and the visit order is the insertion order.
-    -> dict(y [F, n], perm, parity [F, 128], order, snr_db, model)."""
-    m = n - k
-    rng = np.random.default_rng(seed)
-    ys, Gps = [], []
-    perm = np.zeros((F, 128), np.uint8)
-    perm[:, :n] = np.arange(n)
-    parity = np.zeros((F, 128), np.uint64)
-    for f in range(F):
-        Pm = rng.integers(0, 2, (k, m), dtype=np.int64)
-        Gps.append(np.concatenate([np.eye(k, dtype=np.int64), Pm], axis=1))
-        parity[f, :k] = osdx_model._pack_rows(Pm)
-        mrb = np.full(k, 0.75, F32)
-        if levels == 2:
-            mrb[rng.random(k) < 0.5] = F32(0.5)
-        mag = np.concatenate([mrb, rng.uniform(0.3, 1.2, m).astype(F32)]).astype(F32)
-        sign = np.where(rng.integers(0, 2, n) == 1, F32(-1), F32(1))
-        ys.append(mag * sign)
-    y = np.ascontiguousarray(np.stack(ys), dtype=F32)
-    return dict(y=y, perm=perm, parity=parity, order=order, snr_db=1.0, model=pb(y, perm, Gps, order, 1.0))
+    """osdx_pb_model.equal_magnitudes_in with two-word parity [F, 128]."""
+    return M.equal_magnitudes_in(OF.OSDW, k, n, order, levels, F, seed)
 
 
 # ---------------------------------------------------------------------------------------------------------- frames in turn

@@ -1,5 +1,6 @@
-"""Test helper: a vectorised CPU oracle of FS-OSD (fs_osd, FS_OSD/fs_testing.py:129-161) for any (k, n), in the style of
-osdx_model.scan_oracle and in the device layouts of ldpc_osdx_fs_search / _decode.
+"""Test helper: the one vectorised CPU oracle of FS-OSD (fs_osd, FS_OSD/fs_testing.py:129-161) for any (k, n) -- every G-form
+family's reference, in the style of osdx_model.scan_oracle -- with the planted stop (``planted_stop``) and the span survey
+(``spans``) in any family's layouts, and the inputs of the any-shape family's FS tests (ldpc_osdx_fs_search / _decode).
 
 Per weight class the candidates, their Hamming distances and their costs (osdx_model.costs_vectorised: the float32 additions of
 np_oracle._weighted_distance_k in the same order) are arrays over the class's TEPs in visit order.  They depend on the frame
@@ -24,6 +25,7 @@ import functools
 import numpy as np
 
 from oracle import np_oracle
+from tests import osd_family as OF
 from tests import osdx_model
 
 F32 = np.float32
@@ -224,32 +226,62 @@ def parity_case(name, order3=False):
     return y, cw, front, b, order, sets, [b.fs(order, *s) for s in sets]
 
 
+PLANTED_TAU_E = {3: 3.5, 2: 2.5}
+
+
+def classes_before(k, weight):
+    """The TEPs visited before weight class ``weight``: the all-zero TEP and the lighter classes."""
+    return 1 + (k if weight > 1 else 0) + (k * (k - 1) // 2 if weight > 2 else 0)
+
+
 @functools.lru_cache(maxsize=None)
-def planted(k, n, which, seed=5):
-    """Test 2: caller-made front-end results with a tau_e = 3.5 stop planted at a chosen rank of weight class 3.
-    Identity permutation, random rows of P' (large mutual distance), y' whose hard decisions make d0 = P'[a] ^ P'[b] ^ P'[c]:
-    the TEP {a, b, c} then has HD 3 and, as the model confirms, nothing before it has HD <= 3.  ``which``: "first" (its rank
-    in the first round of the class), "middle", or "last" (the last, partial round).
-    -> dict(y [1, n], perm [1, 128] u8, parity [1, 64] u64, batch, support, rank, params (order, beta, tau_e, tau_psc))."""
+def planted_stop(fam, k, n, weight, which, tau_e=None, tau_psc=None, seed=5):
+    """Caller-made front-end results in the layouts of the family ``fam`` (osd_family) with a tau_e stop (3.5 in class 3, 2.5 in
+    class 2) planted at a chosen rank of weight class ``weight`` -- "first" (a rank of its first round), "middle", "last" (the
+    last, partial round), or "across" (the support {63, 64} of class 2; ``tau_e`` then as given).  Identity permutation, random
+    rows of P' (large mutual distance), y' whose hard decisions make d0 the sum of the support's rows of P': that TEP then has
+    HD = weight and, as the model confirms, nothing before it has HD <= weight.  ``tau_psc``: n when None (every candidate is
+    eligible, so the reference-quirk answer is a search result).
+    -> dict(y [1, n], perm, parity, batch, support, rank, at = the rank in the whole visit order,
+            params (order, beta, tau_e, tau_psc))."""
     m = n - k
-    sup3 = class_supports(k, 3)
-    cnt = len(sup3)
+    sup = class_supports(k, weight)
+    cnt = len(sup)
     assert cnt % 64, "the last round must be partial"
-    rank = {"first": 37, "middle": (cnt // 128) * 64 + 21, "last": (cnt // 64) * 64 + (cnt % 64) // 2}[which]
-    a, b, c = (int(x) for x in sup3[rank])
+    rank = fs_rank(k, (63, 64)) if which == "across" else {"first": 37, "middle": (cnt // 128) * 64 + 21,
+                                                           "last": (cnt // 64) * 64 + (cnt % 64) // 2}[which]
+    support = tuple(int(x) for x in sup[rank])
     rng = np.random.default_rng(seed)
     P = rng.integers(0, 2, (k, m), dtype=np.int64)
     Gp = np.concatenate([np.eye(k, dtype=np.int64), P], axis=1)
     u0 = rng.integers(0, 2, k, dtype=np.int64)
-    hp = (u0.dot(P) + P[a] + P[b] + P[c]) % 2                 # d0 = (u0 . P') ^ hp = P'[a] ^ P'[b] ^ P'[c]
+    hp = (u0.dot(P) + P[list(support)].sum(axis=0)) % 2        # d0 = (u0 . P') ^ hp = the sum of the support's rows
     mag = np.concatenate([np.linspace(0.5, 0.05, k), rng.uniform(0.6, 1.5, m)]).astype(F32)
     y = (np.where(np.concatenate([u0, hp]) == 1, -1.0, 1.0) * mag).astype(F32)[None, :]
-    perm = np.zeros((1, 128), np.uint8)
-    perm[0, :n] = np.arange(n)
-    parity = np.zeros((1, 64), np.uint64)
-    parity[0, :k] = osdx_model._pack_rows(P)
-    return dict(y=y, perm=perm, parity=parity, batch=Batch(y, perm, [Gp]), support=(a, b, c), rank=rank,
-                params=(3, 0.0, 3.5, 30.0))
+    perm, parity = fam.pack_front(np.arange(n), Gp)
+    return dict(y=y, perm=perm[None], parity=parity[None], batch=Batch(y, perm[None], [Gp]), support=support, rank=rank,
+                at=classes_before(k, weight) + rank,
+                params=(weight, 0.0, PLANTED_TAU_E[weight] if tau_e is None else tau_e, float(n) if tau_psc is None else tau_psc))
+
+
+def planted(k, n, which, seed=5):
+    """Test 2: planted_stop in class 3 (tau_e = 3.5, tau_psc = 30) in the osdx layouts: perm [1, 128] u8, parity [1, 64] u64."""
+    return planted_stop(OF.OSDX, k, n, 3, which, tau_psc=30.0, seed=seed)
+
+
+def spans(case, span):
+    """-> (winner spans, stopping-candidate spans): the set of span() values over the reference-quirk winners (rank > 0) and over
+    the tau_e stopping candidates of every frame and parameter set of a parity_case result."""
+    _, _, _, b, order, sets, _ = case
+    win, stop = set(), set()
+    for s in sets:
+        for scan in b.scans:
+            r = scan.fs(order, *s)
+            if r["ref"][0]:
+                win.add(span(r["ref"][0]))
+            if r["hit"] is not None and r["hit"][0]:
+                stop.add(span(r["hit"][0]))
+    return win, stop
 
 
 PLANTED = [(k, n, which) for (k, n) in ((17, 40), (60, 121)) for which in ("first", "middle", "last")]

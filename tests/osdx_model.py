@@ -1,9 +1,12 @@
-"""Test helper: CPU oracles of the any-shape OSD entry points (ldpc_osdx_*), in the device layouts.
+"""Test helper: the codes and frames of the any-shape OSD entry points (ldpc_osdx_*), and the scan oracle of every G-form
+family.
 
-  front_oracle   the C oracle's general orc_osd_front (oracle/ldpc_oracle.c), frame by frame
-  scan_oracle    front_oracle + np_oracle.tep_matrix(k, order) + a cost that runs np_oracle._weighted_distance_k's exact
-                 sequence of float32 additions, vectorised over the TEPs (loop over positions, arrays over candidates);
-                 ``self_check`` shows it equal to np_oracle.convention_osd's costs bit for bit
+  codes          ccsds and four members of tests/nms_graphs.py; frames; saturated_frames
+  front_oracle   osd_family.front_oracle bound to the osdx layouts
+  scan_oracle    a front_oracle result of any family + np_oracle.tep_matrix(k, order) + a cost that runs
+                 np_oracle._weighted_distance_k's exact sequence of float32 additions, vectorised over the TEPs (loop over
+                 positions, arrays over candidates); osd_family.self_check shows it equal to np_oracle.convention_osd's costs
+                 bit for bit
 """
 import functools
 import os
@@ -12,6 +15,7 @@ import numpy as np
 
 from oracle import c_oracle, np_oracle
 from tests import nms_graphs
+from tests import osd_family as OF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CCSDS = os.path.join(ROOT, "short_ldpc_decoding_osd_amd", "data", "CCSDS_ldpc_n128_k64.alist")
@@ -43,31 +47,7 @@ def saturated_frames(G):
     return np.where(s, -3.0e38, 3.0e38).astype(np.float32)
 
 
-def _pack_rows(bits):
-    """[r, c <= 64] 0/1 -> [r] uint64, bit c of row r."""
-    bits = np.asarray(bits, dtype=np.uint8)
-    pad = np.zeros((bits.shape[0], 64 - bits.shape[1]), np.uint8)
-    return np.packbits(np.concatenate([bits, pad], axis=1), axis=1, bitorder="little").view(np.uint64)[:, 0]
-
-
-def front_oracle(G, y):
-    """-> (perm [F,128] u8, parity [F,64] u64, nswaps [F] i32, Gp list) in the layouts of ldpc_osdx_front: entries beyond n,
-    rows beyond k and bits beyond n-k are zero."""
-    G = np.asarray(G)
-    k, n = G.shape
-    y = np.asarray(y, dtype=np.float32)
-    perm = np.zeros((len(y), 128), np.uint8)
-    parity = np.zeros((len(y), 64), np.uint64)
-    ns = np.zeros(len(y), np.int32)
-    Gps = []
-    for f, row in enumerate(y):
-        p, Gp, sw = c_oracle.osd_front(G, row)
-        assert np.array_equal(Gp[:, :k], np.eye(k, dtype=np.int32))
-        perm[f, :n] = p
-        parity[f, :k] = _pack_rows(Gp[:, k:])
-        ns[f] = len(sw)
-        Gps.append(Gp.astype(np.int64))
-    return perm, parity, ns, Gps
+front_oracle = functools.partial(OF.front_oracle, fam=OF.OSDX)       # (G, y) -> perm [F,128] u8, parity [F,64] u64, nswaps, Gp list
 
 
 @functools.lru_cache(maxsize=None)
@@ -128,19 +108,3 @@ def scan_oracle(G, y, order, front=None):
     pad = np.zeros((F, (-n) % 64), np.uint8)
     out["cw"] = np.packbits(np.concatenate([bits, pad], axis=1), axis=1, bitorder="little").view(np.uint64)
     return out
-
-
-def self_check(name, frames_=3, seed=5):
-    """The vectorised cost against np_oracle.convention_osd on a few order-1 frames, bit for bit."""
-    G = graph(name)[1]
-    k, n = G.shape
-    y, cw = frames(name, 1.5, frames_, seed)
-    for row, lab in zip(y, cw):
-        yp, labp, Gp, perm, _ = np_oracle.swapped_info(row, lab, G)
-        ref = np_oracle.convention_osd(yp, labp, Gp, 1)
-        cost, cand = scan_frame(yp, Gp, 1)
-        assert np.array_equal(cost.view(np.uint32), ref["costs"].view(np.uint32))
-        assert int(np.argmin(cost)) == ref["best_index"] and np.array_equal(cand[ref["best_index"]], ref["codeword"])
-        p_c, Gp_c, _ = c_oracle.osd_front(G, row)               # the two front-end oracles agree on the shape
-        assert np.array_equal(p_c, perm) and np.array_equal(Gp_c, Gp)
-    return True

@@ -1,5 +1,5 @@
-"""Test helper: a CPU model of PB-OSD (pb_osd, PB_OSD/pb_testing.py:100-149) for any (k, n), in the device layouts of
-ldpc_osdx_pb_search / _decode.
+"""Test helper: the one CPU model of PB-OSD (pb_osd, PB_OSD/pb_testing.py:100-149) for any (k, n) -- every G-form family's
+reference -- and the inputs of the any-shape family's PB tests (ldpc_osdx_pb_search / _decode).
 
 The model is oracle/ldpc_oracle.c orc_pb_osd's deterministic float conventions with 64 + 64 replaced by k + (n - k):
     q_p = 1 / (1 + det_expf(-(c4 |y'_p|))) in float32, c4 = (float)(-4 / 10^(snr_db / 10));
@@ -8,7 +8,8 @@ The model is oracle/ldpc_oracle.c orc_pb_osd's deterministic float conventions w
     binomial CDFs of (n - k, p1), (n - k, 1/2) and (k, pt) by the float64 pmf recurrence, q^N by left-to-right
     square-and-multiply (six squarings at N = 64);
     the frontier is a heap keyed by (sum, insertion sequence number): "first minimum in list order";
-    the metric is osdx_model.costs_vectorised's order of additions, taken from byte tables as the C oracle takes it.
+    the metric is osdx_model.costs_vectorised's order of additions, taken from byte tables as the C oracle takes it:
+    8 ceil(m / 64) tables (m = n - k), the byte sums of word 0, then of word 1, then of word 2 added to the reliability sum.
 Every float32 operation is rounded on its own (NumPy float32 scalars).
 
 Tags of a frame: stop0 / stop1 / stop2, improved (the winner is not the all-zero TEP), tie (a pop whose sum equalled another
@@ -20,6 +21,7 @@ import math
 
 import numpy as np
 
+from tests import osd_family as OF
 from tests import osdx_model
 
 F32 = np.float32
@@ -67,31 +69,36 @@ def frontier_bound(k):
 
 def pb_frame(yp, Gp, order, snr_db):
     """One frame in the primed domain -> dict(support, cand [n], metric, best, ntep, aux (cmp, suc1, suc2, stop), tags, peak)."""
-    with np.errstate(over="ignore", divide="ignore"):         # (a vanishing success product: p_suc = 0, as on the device)
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):   # (a vanishing success product: p_suc = 0, as on the device)
         return _pb_frame(np.asarray(yp, dtype=F32), np.asarray(Gp, dtype=np.int64), order, snr_db)
+
+
+def _bits_int(bits):
+    return int.from_bytes(np.packbits(np.asarray(bits, dtype=np.uint8), bitorder="little").tobytes(), "little")
 
 
 def _pb_frame(yp, Gp, order, snr_db):
     k, n = Gp.shape
     m = n - k
+    nb = 8 * ((m + 63) // 64)                                 # byte tables: 8 per word of the parity discrepancy
     w = np.abs(yp)
     hard = np.where(yp > 0, 0, 1).astype(np.int64)
-    P = [int(sum(int(Gp[r, k + c]) << c for c in range(m))) for r in range(k)]
-    d0 = int(sum(int(hard[k + c]) << c for c in range(m)))
+    P = [_bits_int(Gp[r, k:]) for r in range(k)]
+    d0 = _bits_int(hard[k:])
     for r in range(k):
         if hard[r]:
             d0 ^= P[r]
     # byte tables of the parity part: each byte's set positions ascending from 0.0f (a position beyond n adds nothing)
-    wp = np.zeros(64, F32)
+    wp = np.zeros(8 * nb, F32)
     wp[:m] = w[k:]
-    lut = np.zeros((8, 256), F32)
-    for b in range(8):
+    lut = np.zeros((nb, 256), F32)
+    for b in range(nb):
         for t in range(8):
             lut[b, 1 << t:2 << t] = lut[b, 0:1 << t] + wp[8 * b + t]
 
     def cost(mrb, D):
         acc = F32(mrb)
-        for b in range(8):
+        for b in range(nb):
             acc = F32(acc + lut[b, (D >> (8 * b)) & 0xFF])
         return acc
 
@@ -180,21 +187,22 @@ def _pack(bits):
 
 
 def pb(y, perm, Gps, order, snr_db):
-    """Frames y [F, n] in original order with front-end results (perm [F, 128] u8, Gps: [I | P'] per frame) -> dict of arrays
-    in the layouts of ldpc_osdx_pb_search: cw [F, words] u64, metric [F] f32, best / ntep [F] i32, aux [F, 4] i32, and
-    tags (a list of sets), peak [F]."""
+    """Frames y [F, n] in original order with front-end results (perm [F, >= n] of any family, Gps: [I | P'] per frame) -> dict
+    of arrays in the layouts of ldpc_osd?_pb_search: cw [F, words] u64, metric [F] f32, best / ntep [F] i32, aux [F, 4] i32,
+    and tags (a list of sets), peak [F], supports (a list of tuples)."""
     y = np.asarray(y, dtype=F32)
     k, n = np.asarray(Gps[0]).shape
     F = len(y)
     bits = np.zeros((F, n), np.uint8)
     out = dict(metric=np.zeros(F, F32), best=np.zeros(F, np.int32), ntep=np.zeros(F, np.int32), aux=np.zeros((F, 4), np.int32),
-               tags=[], peak=np.zeros(F, np.int64))
+               tags=[], peak=np.zeros(F, np.int64), supports=[])
     for f in range(F):
         p = np.asarray(perm[f][:n]).astype(np.int64)
         r = pb_frame(y[f][p], Gps[f], order, snr_db)
         bits[f, p] = r["cand"]
         out["metric"][f], out["best"][f], out["ntep"][f], out["aux"][f], out["peak"][f] = r["metric"], r["best"], r["ntep"], r["aux"], r["peak"]
         out["tags"].append(r["tags"])
+        out["supports"].append(r["support"])
     out["cw"] = _pack(bits)
     return out
 
@@ -251,23 +259,19 @@ def case(name, i):
 
 
 @functools.lru_cache(maxsize=None)
-def equal_magnitudes(name, order, levels, seed=11):
-    """Caller-made front-end results: identity permutation, random P', |y'| equal over the MRB (levels = 1) or of two distinct
-    values (levels = 2), so that the sums of one weight tie and the visit order is the insertion order.
-    -> dict(y [F, n], perm, parity, model) for a few frames with random hard decisions."""
-    G = osdx_model.graph(name)[1]
-    k, n = G.shape
+def equal_magnitudes_in(fam, k, n, order, levels, F, seed=11):
+    """Caller-made front-end results in the layouts of the family ``fam`` (osd_family): identity permutation, random P', |y'|
+    equal over the MRB (levels = 1) or of two distinct values (levels = 2), so that the sums of one weight tie and the visit
+    order is the insertion order.  -> dict(y [F, n], perm, parity, order, snr_db, model) for F frames with random hard
+    decisions."""
     m = n - k
     rng = np.random.default_rng(seed)
-    F = 3
-    ys, Gps = [], []
-    perm = np.zeros((F, 128), np.uint8)
-    perm[:, :n] = np.arange(n)
-    parity = np.zeros((F, 64), np.uint64)
+    ys, Gps, perms, pars = [], [], [], []
     for f in range(F):
         Pm = rng.integers(0, 2, (k, m), dtype=np.int64)
-        Gps.append(np.concatenate([np.eye(k, dtype=np.int64), Pm], axis=1))
-        parity[f, :k] = osdx_model._pack_rows(Pm)
+        Gp = np.concatenate([np.eye(k, dtype=np.int64), Pm], axis=1)
+        p, q = fam.pack_front(np.arange(n), Gp)
+        Gps.append(Gp), perms.append(p), pars.append(q)
         mrb = np.full(k, 0.75, F32)
         if levels == 2:
             mrb[rng.random(k) < 0.5] = F32(0.5)
@@ -275,7 +279,24 @@ def equal_magnitudes(name, order, levels, seed=11):
         sign = np.where(rng.integers(0, 2, n) == 1, F32(-1), F32(1))
         ys.append(mag * sign)
     y = np.ascontiguousarray(np.stack(ys), dtype=F32)
+    perm, parity = np.stack(perms), np.stack(pars)
     return dict(y=y, perm=perm, parity=parity, order=order, snr_db=1.0, model=pb(y, perm, Gps, order, 1.0))
+
+
+def equal_magnitudes(name, order, levels, seed=11):
+    """equal_magnitudes_in on the shape of ``name`` in the osdx layouts, three frames."""
+    k, n = osdx_model.graph(name)[1].shape
+    return equal_magnitudes_in(OF.OSDX, k, n, order, levels, 3, seed)
+
+
+def slots3(k):
+    """The frontier slots an order-3 search of k positions needs."""
+    return k + (k - 1) * (k - 2) // 2
+
+
+def tier(k, slots):
+    """The smallest slot tier of ``slots`` that holds slots3(k)."""
+    return min(t for t in slots if slots3(k) <= t)
 
 
 @functools.lru_cache(maxsize=None)

@@ -9,39 +9,35 @@ holds to the reference restatements and whose premises it asserts.  Integers com
   3  non-zero padding of perm and P': ignored by every search entry point
   4  structured codes (zero columns, repeated columns, a rank-one parity part of G) through the device front end and the decodes
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from short_ldpc_decoding_osd_amd import _lib
+from tests import osd_family as OF
 from tests import osd_shapes as S
 from tests import osdw_fs_model as W
 from tests import osdx_fs_model as M
 from tests import osdx_model, osdx_pb_model
 from tests.gpu_util import to_dev, words_np
+from tests.osd_family import fs_params, new_aux
 
 pytestmark = pytest.mark.gpu
 PAIR_CASES = [(k, n, name) for k, n in S.SHAPES for name in S.STRUCTURES]
 CODE_CASES = [(k, n, name) for k, n in S.CODE_SHAPES for name in S.CODE_STRUCTURES]
-_decoders, _REF = {}, {}
-_p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+_REF = {}
+
+
+def _graph(k, n, name):
+    return S.context_graph(k, n) if name is None else S.code(k, n, name)[:2]
 
 
 def decoder(k, n, name=None):
     """A context of the shape (a plain H = [A | I] code: the searches never read G), or of the structured code ``name``."""
-    key = (k, n, name)
-    if key not in _decoders:
-        from short_ldpc_decoding_osd_amd import Code
-        from short_ldpc_decoding_osd_amd.runtime import Decoder
-        H, G = S.context_graph(k, n) if name is None else S.code(k, n, name)[:2]
-        code = Code(H=H)
-        assert np.array_equal(code.G, G) and (code.k, code.check_matrix_column) == (k, n)
-        dec = Decoder(code)
-        assert dec.osdw_supported and dec.osdx_supported == (k <= 64)
-        _decoders[key] = dec
-    return _decoders[key]
+    dec = OF.decoder((k, n, name), _graph)
+    assert np.array_equal(dec.code.G, _graph(k, n, name)[1]) and (dec.code.k, dec.code.check_matrix_column) == (k, n)
+    assert dec.osdw_supported and dec.osdx_supported == (k <= 64)
+    return dec
 
 
 def ref(kind, c, *args):
@@ -72,33 +68,16 @@ def conv_frames(k, order, F):
     return min(F, 3) if (order == 2 and k >= 100) else F
 
 
-def u32(t):
-    return (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.ascontiguousarray(t)).view(np.uint32)
-
-
 def assert_scan(out, want, tag):
-    F = len(want["best"])
-    assert np.array_equal(words_np(out["cw"])[:F], want["cw"]), tag
-    assert np.array_equal(u32(out["metric"])[:F], u32(want["metric"])), tag
-    assert np.array_equal(out["best"].cpu().numpy()[:F], want["best"]), tag
-    assert np.array_equal(out["ntep"].cpu().numpy()[:F], want["ntep"]), tag
+    OF.assert_scan(out, want, len(want["best"]), tag)
 
 
 def assert_fs(out, want, quirk, tag):
-    key = "ref" if quirk else "hit"
-    assert_scan(out, dict(cw=want["cw_" + key], metric=want["metric_" + key], best=want["best_" + key], ntep=want["ntep"]), tag)
+    assert_scan(out, OF.fs_view(want, quirk), tag)
 
 
 def assert_same(a, b, tag, keys=("cw", "metric", "best", "ntep")):
-    for key in keys:
-        x, y = a[key], b[key]
-        if x.dtype == torch.float32:
-            x, y = x.view(torch.int32), y.view(torch.int32)
-        assert torch.equal(x, y), tag + (key,)
-
-
-def fs_params(dec, order, s, quirk):
-    return dec.osd_params(order, _lib.OSD_FS, fs_beta=s[0], fs_tau_e=s[1], fs_tau_psc=s[2], fs_reference_quirk=quirk)
+    OF.assert_same(a, b, keys, tag)
 
 
 def device_inputs(dec, c, padding=False):
@@ -131,7 +110,7 @@ def run_searches(dec, c, padding=False):
                     out["osdx_fs_search", s, quirk] = dec.osdx_fs_search(yd, perm, p64, p)
         if k <= 64:
             for snr in S.PB_SNRS:
-                aux = torch.full((F, 4), -9, dtype=torch.int32, device=dec.device)
+                aux = new_aux(dec, F)
                 r = dec.osdx_pb_search(yd, perm, p64, dec.osd_params(min(2, k), _lib.OSD_PB, snr_db=snr, aux=aux))
                 out["osdx_pb_search", snr] = dict(r, aux=aux)
     torch.cuda.synchronize()
@@ -143,10 +122,7 @@ def _check_conv(c, args, got, tag):
 
 
 def _check_tep(c, args, got, tag):
-    want = ref("tep", c, args[0])
-    assert np.array_equal(words_np(got["cw"]), want["cw"]), tag
-    assert np.array_equal(u32(got["metric"]), u32(want["metric"])), tag
-    assert np.array_equal(got["hd"].cpu().numpy(), want["hd"]), tag
+    OF.assert_outputs(got, ref("tep", c, args[0]), where=tag, keys=("cw", "metric", "hd"))
 
 
 def _check_fs(c, args, got, tag):
@@ -228,12 +204,9 @@ def test_padding_of_the_inputs_is_ignored(k, n):
 
 
 def _sentinels(dec, F):
-    return dict(cw=torch.full((F, dec.words), -1, dtype=torch.int64, device=dec.device),
-                metric=torch.full((F,), -5.0, dtype=torch.float32, device=dec.device),
-                best=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                ntep=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                hd=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                aux=torch.full((F, 4), -9, dtype=torch.int32, device=dec.device))
+    """The outputs of the search calls (no perm / parity: they are inputs here) and hd."""
+    b = OF.sentinels(dec, OF.OSDW, F, aux=True)
+    return dict({k: b[k] for k in SCAN_KEYS + ("aux",)}, hd=OF.A.sentinel(dec, (F,), torch.int32))
 
 
 @pytest.mark.parametrize("k,n", [(5, 12), (70, 87)])
@@ -248,11 +221,10 @@ def test_padding_through_raw_calls_with_sentinels(k, n):
     count = to_dev(np.array([done], np.int32), dec)
     s = S.fs_sets(k, n)[0]
     order = S.fs_order(k)
-    L, ctx, st = dec.L, dec._ctx, dec._stream()
+    wide, narrow = (dict(d_y=yd, d_count=count, F=F, d_perm=perm, d_parity=q) for q in (p128, p64))
     scan = SCAN_KEYS
     conv = ref("conv", c, 2, F)
-    r = ref("fs", c, *s)
-    fs = dict(cw=r["cw_ref"], metric=r["metric_ref"], best=r["best_ref"], ntep=r["ntep"])
+    fs = OF.fs_view(ref("fs", c, *s), 1)
     tep = ref("tep", c, 3)
     masks = ref("masks", c)[3]
     fsp, runs = fs_params(dec, order, s, 1), []
@@ -262,38 +234,24 @@ def test_padding_through_raw_calls_with_sentinels(k, n):
         assert call(b) == 0, (name, dec.L.ldpc_last_error())
         runs.append((name, b, {key: want[key] for key in keys}))
 
-    run("osdw_search", conv, scan, lambda b: L.ldpc_osdw_search(
-        ctx, _p(yd), None, _p(count), F, _p(perm), _p(p128), 2, _p(b["cw"]), _p(b["metric"]), _p(b["best"]), _p(b["ntep"]), st))
-    run("osdw_fs_search", fs, scan, lambda b: L.ldpc_osdw_fs_search(
-        ctx, _p(yd), None, _p(count), F, _p(perm), _p(p128), C.byref(fsp), _p(b["cw"]), _p(b["metric"]), _p(b["best"]),
-        _p(b["ntep"]), st))
     m2 = to_dev(W.split_masks(masks).view(np.int64), dec)
-    run("osdw_tep_eval", tep, ("cw", "metric", "hd"), lambda b: L.ldpc_osdw_tep_eval(
-        ctx, _p(yd), None, _p(count), F, _p(perm), _p(p128), _p(m2), _p(b["cw"]), _p(b["metric"]), _p(b["hd"]), st))
+    run("osdw_search", conv, scan, lambda b: OF.raw(dec, OF.OSDW, "search", b, order=2, **wide))
+    run("osdw_fs_search", fs, scan, lambda b: OF.raw(dec, OF.OSDW, "fs_search", b, params=fsp, **wide))
+    run("osdw_tep_eval", tep, ("cw", "metric", "hd"), lambda b: OF.raw(dec, OF.OSDW, "tep_eval", b, d_mask=m2, **wide))
     if k <= 64:
-        run("osdx_search", conv, scan, lambda b: L.ldpc_osdx_search(
-            ctx, _p(yd), None, _p(count), F, _p(perm), _p(p64), 2, _p(b["cw"]), _p(b["metric"]), _p(b["best"]), _p(b["ntep"]), st))
-        run("osdx_fs_search", fs, scan, lambda b: L.ldpc_osdx_fs_search(
-            ctx, _p(yd), None, _p(count), F, _p(perm), _p(p64), C.byref(fsp), _p(b["cw"]), _p(b["metric"]), _p(b["best"]),
-            _p(b["ntep"]), st))
         m1 = to_dev(np.array(masks, dtype=np.uint64).view(np.int64), dec)
-        run("osdx_tep_eval", tep, ("cw", "metric", "hd"), lambda b: L.ldpc_osdx_tep_eval(
-            ctx, _p(yd), None, _p(count), F, _p(perm), _p(p64), _p(m1), _p(b["cw"]), _p(b["metric"]), _p(b["hd"]), st))
+        run("osdx_search", conv, scan, lambda b: OF.raw(dec, OF.OSDX, "search", b, order=2, **narrow))
+        run("osdx_fs_search", fs, scan, lambda b: OF.raw(dec, OF.OSDX, "fs_search", b, params=fsp, **narrow))
+        run("osdx_tep_eval", tep, ("cw", "metric", "hd"), lambda b: OF.raw(dec, OF.OSDX, "tep_eval", b, d_mask=m1, **narrow))
 
         def pb_call(b):
-            pb = dec.osd_params(order, _lib.OSD_PB, snr_db=1.0, aux=b["aux"])
-            return L.ldpc_osdx_pb_search(ctx, _p(yd), None, _p(count), F, _p(perm), _p(p64), C.byref(pb), _p(b["cw"]),
-                                         _p(b["metric"]), _p(b["best"]), _p(b["ntep"]), st)
+            return OF.raw(dec, OF.OSDX, "pb_search", b, params=dec.osd_params(order, _lib.OSD_PB, snr_db=1.0, aux=b["aux"]), **narrow)
         run("osdx_pb_search", ref("pb", c, 1.0), scan + ("aux",), pb_call)
     torch.cuda.synchronize()
     clean = _sentinels(dec, F)
     assert len(runs) == (7 if k <= 64 else 3)
     for name, b, want in runs:
-        for key, w in want.items():
-            got = words_np(b[key]) if key == "cw" else b[key].cpu().numpy()
-            if key == "metric":
-                got, w = u32(got), u32(w)
-            assert np.array_equal(got[:done], w[:done]), (name, key)
+        OF.assert_outputs(b, want, slice(0, done), where=name, keys=tuple(want))
         for key in b:
             lo = done if key in want else 0                  # an output the call does not have stays untouched altogether
             assert torch.equal(b[key][lo:], clean[key][lo:]), (name, key)
@@ -351,9 +309,8 @@ def test_structured_codes_through_the_front_end(k, n, name, mode):
     F = len(y)
     assert F == S.CODE_FRAMES
     yd = to_dev(y, dec)
-    perm = torch.full((F, 128), 0xEE, dtype=torch.uint8, device=dec.device)
-    parity = torch.full((F, 128), -1, dtype=torch.int64, device=dec.device)
-    ns = torch.full((F,), -7, dtype=torch.int32, device=dec.device)
+    b = OF.sentinels(dec, OF.OSDW, F)
+    perm, parity, ns = b["perm"], b["parity"], OF.A.sentinel(dec, (F,), torch.int32)
     got = dec.osdw_front(yd, out=(perm, parity, ns))
     torch.cuda.synchronize()
     assert_front(got, front, n, k, 128)
@@ -387,7 +344,7 @@ def test_structured_codes_through_the_pb_decode(k, n, name, mode, snr):
     ys, sub = code_ref("sub", k, n, name, mode)
     assert len(ys) == S.CODE_FRAMES
     want = code_ref("pb", k, n, name, mode, snr)
-    aux = torch.full((len(ys), 4), -9, dtype=torch.int32, device=dec.device)
+    aux = new_aux(dec, len(ys))
     out = dec.osdx_pb_decode(to_dev(ys, dec), dec.osd_params(2, _lib.OSD_PB, snr_db=snr, aux=aux))
     torch.cuda.synchronize()
     assert_scan(out, want, (k, n, name, mode, "osdx_pb_decode", snr))

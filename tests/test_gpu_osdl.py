@@ -2,63 +2,39 @@
 bit-exact against the CPU oracles of tests/osdl_model.py on the reference's (384,192) code and six synthetic codes, and against
 ldpc_osdx_* / ldpc_osdw_* on four codes those families serve as well.  Floats compare by their bits.  The premises of the
 inputs (which paths of the elimination they take) are asserted on the CPU in tests/test_osdl_host.py."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from short_ldpc_decoding_osd_amd import _lib
-from tests import osdl_model, osdx_model
-from tests.gpu_util import pack_np, to_dev, words_np
+from tests import osd_family as OF
+from tests import osdl_model
+from tests.gpu_util import to_dev
+from tests.osd_family import assert_scan, decoder
 
 pytestmark = pytest.mark.gpu
-_decoders, _scan = {}, {}
+_scan = {}
 OUTS = ("perm", "parity", "cw", "metric", "best", "ntep")
-NEEDS = r"n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192"
-
-
-def decoder(name):
-    if name not in _decoders:
-        from short_ldpc_decoding_osd_amd.runtime import Decoder
-        _decoders[name] = Decoder(osdl_model.make_code(name))
-    return _decoders[name]
+FAM = OF.OSDL
 
 
 def layout(dec):
-    S, W, Wp = dec.words, (dec.k + 63) // 64, (dec.n - dec.k + 63) // 64
-    return (64 * S,), ((64 * W,) if Wp == 1 else (64 * W, Wp))
+    """Shape tails of perm and parity."""
+    return FAM.layout(dec.n, dec.k)[1:3]
 
 
-def filled(dec, F, value=7):
-    """Every buffer of a call, prefilled."""
-    ptail, qtail = layout(dec)
-    mk = lambda shape, dt: torch.full(shape, value, dtype=dt, device=dec.device)      # noqa: E731
-    return dict(perm=mk((F,) + ptail, torch.int16), parity=mk((F,) + qtail, torch.int64), cw=mk((F, dec.words), torch.int64),
-                metric=mk((F,), torch.float32), best=mk((F,), torch.int32), ntep=mk((F,), torch.int32))
-
-
-def front_np(perm, parity, dec):
-    """Device front-end results in the oracle's types: perm [F, 64 S] u16, parity [F, 64 W, Wp] u64."""
-    W, Wp = (dec.k + 63) // 64, (dec.n - dec.k + 63) // 64
-    return perm.cpu().numpy().view(np.uint16), words_np(parity).reshape(-1, 64 * W, Wp)
+def filled(dec, F):
+    """Every buffer of a call, prefilled with values no kernel writes."""
+    return OF.sentinels(dec, FAM, F)
 
 
 def assert_front(got, want, dec, rows=slice(None)):
-    """perm, parity (padding included: the oracle's arrays are zero there) and nswaps."""
-    perm, parity = front_np(got[0], got[1], dec)
-    assert np.array_equal(perm[rows], want[0][rows])
-    assert np.array_equal(parity[rows], want[1][rows])
-    if got[2] is not None:
-        assert np.array_equal(got[2].cpu().numpy()[rows], want[2][rows])
+    """(perm, parity, nswaps or None) of the frames ``rows`` against a front_oracle result."""
+    OF.assert_front(FAM, dec, got[0][rows], got[1][rows], want, None if got[2] is None else got[2][rows], rows)
 
 
-def assert_scan(out, ref, F=None):
-    sl = slice(0, F)
-    assert np.array_equal(words_np(out["cw"])[sl], ref["cw"][sl])
-    assert np.array_equal(out["metric"].cpu().numpy().view(np.uint32)[sl], ref["metric"].view(np.uint32)[sl])
-    assert np.array_equal(out["best"].cpu().numpy()[sl], ref["best"][sl])
-    assert np.array_equal(out["ntep"].cpu().numpy()[sl], ref["ntep"][sl])
+def _raw_decode(dec, *args, **kw):
+    return OF.raw_decode(dec, FAM, "decode", *args, **kw)
 
 
 def subset(front, rows):
@@ -113,18 +89,18 @@ def test_front_end_matches_oracle(name):
     if name in osdl_model.NEW:
         assert not dec.osdx_supported and not dec.osdw_supported
     F = len(y)
-    b = filled(dec, F, -1)
-    ns = torch.full((F,), -7, dtype=torch.int32, device=dec.device)
+    b = filled(dec, F)
+    ns = OF.A.sentinel(dec, (F,), torch.int32)
     got = dec.osdl_front(to_dev(y, dec), out=(b["perm"], b["parity"], ns))
     torch.cuda.synchronize()
     assert (tuple(got[0].shape[1:]), tuple(got[1].shape[1:])) == layout(dec)
-    perm = front_np(got[0], got[1], dec)[0]
+    perm = got[0].cpu().numpy().view(np.uint16)
     assert all(sorted(p[:dec.n]) == list(range(dec.n)) for p in perm.tolist())
     assert not perm[:, dec.n:].any()                                # the padded entries are written, as zero
     assert_front(got, want, dec)
     assert (want[2] >= 0).all()
     # without nswaps: the same perm and parity
-    again = dec.osdl_front(to_dev(y, dec), out=(filled(dec, F, -1)["perm"], filled(dec, F, -1)["parity"], None))
+    again = dec.osdl_front(to_dev(y, dec), out=(filled(dec, F)["perm"], filled(dec, F)["parity"], None))
     torch.cuda.synchronize()
     assert torch.equal(again[0], got[0]) and torch.equal(again[1], got[1])
 
@@ -185,13 +161,6 @@ def test_search_ignores_the_padding(name, order):
 # ---------------------------------------------------------------------------------------------------------------------
 # 4: decode, compaction and counts
 # ---------------------------------------------------------------------------------------------------------------------
-def _raw_decode(dec, yd, index, count, F, order, bufs, label=None, counts=None):
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-    return dec.L.ldpc_osdl_decode(dec._ctx, p(yd), p(index), p(count), F, order, p(bufs.get("perm")), p(bufs.get("parity")),
-                                  p(bufs.get("cw")), p(bufs.get("metric")), p(bufs.get("best")), p(bufs.get("ntep")),
-                                  p(label), p(counts), dec._stream())
-
-
 @pytest.fixture(scope="module")
 def listed():
     """s200_100: a shuffled subset of its front-end frames as the frame list, a device-side count below the list's length, and
@@ -205,8 +174,8 @@ def listed():
     assert not np.all(np.diff(idx) > 0)
     nf = 13
     _, front, ref = scan_case(name, 1, idx[:nf])
-    return dict(dec=dec, yd=to_dev(y, dec), labels=labels, index=to_dev(idx, dec), idx=idx, nf=nf, front=front, ref=ref,
-                count=to_dev(np.array([nf], np.int32), dec))
+    return dict(dec=dec, yd=to_dev(y, dec), labels=labels, label_rows=idx[:nf], index=to_dev(idx, dec), idx=idx, nf=nf, rows=np.arange(nf),
+                front=front, ref=ref, count=to_dev(np.array([nf], np.int32), dec), arg=lambda bufs: 1)
 
 
 def test_frame_list_and_device_count(listed):
@@ -220,32 +189,12 @@ def test_frame_list_and_device_count(listed):
         assert_scan(bufs, listed["ref"], done)
         assert_front((bufs["perm"], bufs["parity"], None), listed["front"], dec, slice(0, done))
         for k in OUTS:                                              # nothing at or beyond min(count, F)
-            assert bool((bufs[k][done:] == 7).all()), (cap, k)
+            assert OF.A.untouched(bufs[k], done), (cap, k)
 
 
 @pytest.mark.parametrize("off", ["none", "metric", "best", "ntep", "counts", "label"])
 def test_nullable_outputs_and_counters(listed, off):
-    dec, nf, ref = listed["dec"], listed["nf"], listed["ref"]
-    label = to_dev(pack_np(listed["labels"]).view(np.int64), dec)
-    bufs = filled(dec, nf)
-    counts = torch.tensor([5, 6, 7], dtype=torch.int64, device=dec.device)
-    if off in bufs:
-        bufs[off] = None
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], nf, 1, bufs,
-                       None if off == "label" else label, None if off == "counts" else counts) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(words_np(bufs["cw"]), ref["cw"])
-    if off != "metric":
-        assert np.array_equal(bufs["metric"].cpu().numpy().view(np.uint32), ref["metric"].view(np.uint32))
-    if off != "best":
-        assert np.array_equal(bufs["best"].cpu().numpy(), ref["best"])
-    if off != "ntep":
-        assert np.array_equal(bufs["ntep"].cpu().numpy(), ref["ntep"])
-    # the counters, recomputed on the host from cw, the labels of the listed frames and ntep
-    wrong = int(np.any(ref["cw"] != pack_np(listed["labels"][listed["idx"][:nf]]), axis=1).sum())
-    assert 0 < wrong < nf
-    want = [5, 6, 7] if off in ("counts", "label") else [5 + nf, 6 + wrong, 7 + (0 if off == "ntep" else int(ref["ntep"].sum()))]
-    assert counts.cpu().tolist() == want
+    OF.check_nullable(FAM, "decode", listed, off)
 
 
 def test_more_frames_than_workgroups():
@@ -299,19 +248,11 @@ def test_unsupported_shapes_are_refused(name):
     dec = decoder(name)
     assert not dec.osdl_supported and not dec.osdx_supported and not dec.osdw_supported
     assert (dec.n, dec.k) == {"wimax_1056": (1056, 880), "s385_193": (385, 193), "s384_193": (384, 193), "s384_191": (384, 191)}[name]
-    y, _ = osdl_model.frames(name, 2.0, 4, 1)
-    yd = to_dev(y, dec)
-    bufs = filled(dec, 4)
-    msg = rf"\(-5\).*{NEEDS}.*\({dec.n},{dec.k}\)"
-    with pytest.raises(_lib.LdpcError, match=msg):
-        dec.osdl_front(yd, out=(bufs["perm"], bufs["parity"], None))
-    with pytest.raises(_lib.LdpcError, match=msg):
-        dec.osdl_search(yd, bufs["perm"], bufs["parity"], 1, out=bufs)
-    with pytest.raises(_lib.LdpcError, match=msg):
-        dec.osdl_decode(yd, 1, perm=bufs["perm"], parity=bufs["parity"], out=bufs)
-    torch.cuda.synchronize()
-    for k in OUTS:
-        assert bool((bufs[k] == 7).all()), k
+    yd = to_dev(osdl_model.frames(name, 2.0, 4, 1)[0], dec)
+    OF.check_unsupported(FAM, dec, yd, {
+        "front": lambda b: dec.osdl_front(yd, out=(b["perm"], b["parity"], None)),
+        "search": lambda b: dec.osdl_search(yd, b["perm"], b["parity"], 1, out=b),
+        "decode": lambda b: dec.osdl_decode(yd, 1, perm=b["perm"], parity=b["parity"], out=b)})
 
 
 def test_bad_arguments_are_refused():
@@ -328,10 +269,8 @@ def test_bad_arguments_are_refused():
         assert f"ldpc_osdl_decode: d_{missing} is NULL".encode() in dec.L.ldpc_last_error()
     assert _raw_decode(dec, None, None, None, 4, 1, bufs) == -1
     assert b"ldpc_osdl_decode: d_y is NULL" in dec.L.ldpc_last_error()
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-    front = lambda y_, perm, parity: dec.L.ldpc_osdl_front(dec._ctx, p(y_), None, None, 4, p(perm), p(parity), None, dec._stream())   # noqa: E731
-    search = lambda y_, perm, parity, cw: dec.L.ldpc_osdl_search(dec._ctx, p(y_), None, None, 4, p(perm), p(parity), 1, p(cw), None,   # noqa: E731
-                                                                 None, None, dec._stream())
+    front = lambda y_, perm, parity: OF.raw(dec, FAM, "front", d_y=y_, F=4, d_perm=perm, d_parity=parity)   # noqa: E731
+    search = lambda y_, perm, parity, cw: OF.raw(dec, FAM, "search", d_y=y_, F=4, d_perm=perm, d_parity=parity, order=1, d_cw=cw)   # noqa: E731
     for call, args, who in ((front, (None, bufs["perm"], bufs["parity"]), "ldpc_osdl_front: d_y"),
                             (front, (yd, None, bufs["parity"]), "ldpc_osdl_front: d_perm"),
                             (front, (yd, bufs["perm"], None), "ldpc_osdl_front: d_parity"),
@@ -342,8 +281,8 @@ def test_bad_arguments_are_refused():
         assert call(*args) == -1
         assert f"{who} is NULL".encode() in dec.L.ldpc_last_error()
     assert _raw_decode(dec, yd, None, None, 0, 1, {}) == 0                 # F == 0: LDPC_OK, no launch
-    assert dec.L.ldpc_osdl_front(dec._ctx, None, None, None, 0, None, None, None, dec._stream()) == 0
-    assert dec.L.ldpc_osdl_search(dec._ctx, None, None, None, 0, None, None, 1, None, None, None, None, dec._stream()) == 0
+    assert OF.raw(dec, FAM, "front", F=0) == 0
+    assert OF.raw(dec, FAM, "search", F=0, order=1) == 0
     # the older families keep their refusal of this code
     with pytest.raises(_lib.LdpcError, match=r"\(-5\).*1 <= k <= 64 and 1 <= n-k <= 64.*\(100,20\)"):
         dec.osdx_decode(yd, 1)
@@ -351,7 +290,7 @@ def test_bad_arguments_are_refused():
         dec.osdw_decode(yd, 1)
     torch.cuda.synchronize()
     for k in OUTS:
-        assert bool((bufs[k] == 7).all()), k
+        assert OF.A.untouched(bufs[k]), k
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -3,98 +3,46 @@ n <= 384, 1 <= k <= 192, 1 <= n-k <= 192) -- bit-exact against the model of test
 code and the synthetic codes of tests/osdl_model.py, and against ldpc_osdx_fs_* / ldpc_osdw_fs_* / _tep_eval on four codes those
 families serve as well.  The inputs and the branches they reach are those tests/test_osdl_fs_host.py asserts on the CPU.  Floats
 compare by their bits."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from short_ldpc_decoding_osd_amd import _lib
+from tests import osd_family as OF
 from tests import osdl_fs_model as LF
 from tests import osdl_model
 from tests import osdx_fs_model as M
-from tests.gpu_util import pack_np, to_dev, words_np
+from tests.gpu_util import to_dev, words_np
+from tests.osd_family import assert_fs, assert_same, decoder, fs_params
 
 pytestmark = pytest.mark.gpu
 ALPHA0 = 0.669435
-NEEDS = r"n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192"
+FAM = OF.OSDL
 OUTS = ("perm", "parity", "cw", "metric", "best", "ntep")
-_decoders = {}
-
-
-def decoder(name):
-    if name not in _decoders:
-        from short_ldpc_decoding_osd_amd import Code
-        from short_ldpc_decoding_osd_amd.runtime import Decoder
-        code = Code(H=LF.planted_graph(*name)[0]) if isinstance(name, tuple) else osdl_model.make_code(name)   # (k, n): a planted case
-        _decoders[name] = Decoder(code)
-    return _decoders[name]
-
-
-def layout(dec):
-    """Shape tails of perm, parity and a tep_eval mask."""
-    S, W, Wp = dec.words, (dec.k + 63) // 64, (dec.n - dec.k + 63) // 64
-    return (64 * S,), ((64 * W,) if Wp == 1 else (64 * W, Wp)), (W,)
 
 
 def dev_front(perm, parity, dec):
-    """The oracle's perm [F, 64 S] u16 and parity [F, 64 W, Wp] u64 as the device tensors of the binding."""
-    return (to_dev(perm.view(np.int16), dec), to_dev(parity.view(np.int64).reshape((len(perm),) + layout(dec)[1]), dec))
-
-
-def fs_params(dec, order, s, quirk, **kw):
-    return dec.osd_params(order, _lib.OSD_FS, fs_beta=s[0], fs_tau_e=s[1], fs_tau_psc=s[2], fs_reference_quirk=quirk, **kw)
-
-
-def assert_fs(out, ref, quirk, sl=slice(None), where=""):
-    """Every output bit for bit: cw, metric as uint32, best, ntep."""
-    key = "ref" if quirk else "hit"
-    assert np.array_equal(words_np(out["cw"])[sl], ref["cw_" + key][sl]), where
-    assert np.array_equal(out["metric"].cpu().numpy().view(np.uint32)[sl], ref["metric_" + key].view(np.uint32)[sl]), where
-    assert np.array_equal(out["best"].cpu().numpy()[sl], ref["best_" + key][sl]), where
-    assert np.array_equal(out["ntep"].cpu().numpy()[sl], ref["ntep"][sl]), where
+    return OF.dev_front(perm, parity, dec, FAM)
 
 
 def assert_front(perm, parity, front, dec):
-    """perm and parity, padding included: the oracle's arrays are zero there."""
-    W, Wp = (dec.k + 63) // 64, (dec.n - dec.k + 63) // 64
-    assert np.array_equal(perm.cpu().numpy().view(np.uint16), front[0])
-    assert np.array_equal(words_np(parity).reshape(-1, 64 * W, Wp), front[1])
-
-
-def assert_same(got, want, keys, where=""):
-    for key in keys:
-        a, b = got[key], want[key]
-        if a.dtype == torch.float32:
-            a, b = a.view(torch.int32), b.view(torch.int32)
-        assert torch.equal(a, b), (where, key)
+    OF.assert_front(FAM, dec, perm, parity, front)
 
 
 def sentinels(dec, F):
-    ptail, qtail, _ = layout(dec)
-    mk = lambda shape, dt, v: torch.full(shape, v, dtype=dt, device=dec.device)      # noqa: E731
-    return dict(perm=mk((F,) + ptail, torch.int16, 0x6EEE), parity=mk((F,) + qtail, torch.int64, -1), cw=mk((F, dec.words), torch.int64, -1),
-                metric=mk((F,), torch.float32, -5.0), best=mk((F,), torch.int32, -9), ntep=mk((F,), torch.int32, -9))
+    return OF.sentinels(dec, FAM, F)
 
 
-_p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+def _raw_decode(dec, *args, **kw):
+    return OF.raw_decode(dec, FAM, "fs_decode", *args, **kw)
 
 
-def _raw_decode(dec, yd, index, count, F, params, bufs, label=None, counts=None):
-    return dec.L.ldpc_osdl_fs_decode(dec._ctx, _p(yd), _p(index), _p(count), F, C.byref(params) if params is not None else None,
-                                     _p(bufs.get("perm")), _p(bufs.get("parity")), _p(bufs.get("cw")), _p(bufs.get("metric")),
-                                     _p(bufs.get("best")), _p(bufs.get("ntep")), _p(label), _p(counts), dec._stream())
+def _raw_search(dec, *args):
+    return OF.raw_search(dec, FAM, "fs_search", *args)
 
 
-def _raw_search(dec, yd, F, params, bufs):
-    return dec.L.ldpc_osdl_fs_search(dec._ctx, _p(yd), None, None, F, _p(bufs.get("perm")), _p(bufs.get("parity")),
-                                     C.byref(params) if params is not None else None, _p(bufs.get("cw")), _p(bufs.get("metric")),
-                                     _p(bufs.get("best")), _p(bufs.get("ntep")), dec._stream())
-
-
-def _raw_tep_eval(dec, yd, F, perm, parity, mask, cw, metric, hd):
-    return dec.L.ldpc_osdl_tep_eval(dec._ctx, _p(yd), None, None, F, _p(perm), _p(parity), _p(mask), _p(cw), _p(metric), _p(hd),
-                                    dec._stream())
+def _raw_tep_eval(dec, *args):
+    return OF.raw_tep_eval(dec, FAM, *args)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -291,72 +239,34 @@ def listed():
     front = osdl_model.front_oracle(G, y[idx])
     ref = M.Batch(y[idx], front[0], front[3]).fs(2, *LISTED_SET)
     assert ref["hit"].any() and not ref["hit"].all()
-    return dict(dec=dec, y=y, yd=yd, labels=cw, index=index, count=count, nf=nf, idx=idx, ref=ref, front=front,
-                params=fs_params(dec, 2, LISTED_SET, 1))
+    p = fs_params(dec, 2, LISTED_SET, 1)
+    return dict(dec=dec, y=y, yd=yd, labels=cw, label_rows=idx, index=index, count=count, nf=nf, rows=np.arange(nf),
+                ref=OF.fs_view(ref, 1), front=front, arg=lambda bufs: p, distinct_ntep=3)
 
 
 @pytest.mark.parametrize("which", ["smaller", "equal", "larger"])
 def test_frame_list_and_device_count(listed, which):
-    dec, nf = listed["dec"], listed["nf"]
-    F = {"smaller": nf + 13, "equal": nf, "larger": nf - 9}[which]       # the device count against the capacity F
-    done = min(nf, F)
-    bufs = sentinels(dec, nf + 13)
-    clean = {k: v.clone() for k, v in bufs.items()}
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], F, listed["params"], bufs) == 0
-    torch.cuda.synchronize()
-    assert_fs(bufs, listed["ref"], 1, slice(0, done))
-    assert_front(bufs["perm"][:done], bufs["parity"][:done], (listed["front"][0][:done], listed["front"][1][:done]), dec)
-    for k in bufs:                                                       # nothing at or beyond min(count, F)
-        assert torch.equal(bufs[k][done:], clean[k][done:]), k
+    OF.check_frame_list(FAM, "fs_decode", listed, which)
 
 
 @pytest.mark.parametrize("off", ["none", "metric", "best", "ntep", "counts", "label"])
 def test_nullable_outputs_and_counters(listed, off):
-    dec, nf, ref = listed["dec"], listed["nf"], listed["ref"]
-    label = to_dev(pack_np(listed["labels"]).view(np.int64), dec)
-    bufs = sentinels(dec, nf)
-    counts = torch.tensor([5, 6, 7], dtype=torch.int64, device=dec.device)
-    if off in bufs:
-        bufs[off] = None
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], nf, listed["params"], bufs,
-                       None if off == "label" else label, None if off == "counts" else counts) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(words_np(bufs["cw"]), ref["cw_ref"])
-    if off != "metric":
-        assert np.array_equal(bufs["metric"].cpu().numpy().view(np.uint32), ref["metric_ref"].view(np.uint32))
-    if off != "best":
-        assert np.array_equal(bufs["best"].cpu().numpy(), ref["best_ref"])
-    if off != "ntep":
-        assert np.array_equal(bufs["ntep"].cpu().numpy(), ref["ntep"])
-    # the counters, recomputed on the host: teps_total is the sum of the per-frame ntep
-    wrong = int(np.any(ref["cw_ref"] != pack_np(listed["labels"][listed["idx"]]), axis=1).sum())
-    assert 0 < wrong < nf and len(set(ref["ntep"].tolist())) > 3
-    want = [5, 6, 7] if off in ("counts", "label") else [5 + nf, 6 + wrong, 7 + (0 if off == "ntep" else int(ref["ntep"].sum()))]
-    assert counts.cpu().tolist() == want
+    OF.check_nullable(FAM, "fs_decode", listed, off)
 
 
 def test_one_wavefront_decodes_several_frames_in_turn():
     """More frames than the grid's 65536 workgroups, s100_20 at order 2: wavefront b decodes frame b and then frame 65536 + b.
     The frames that share a wavefront are checked against the model, all of them against the same frames in split launches."""
-    name = "s100_20"
+    name, s = "s100_20", (0.02, 22.5, 80)
     dec = decoder(name)
     G = osdl_model.graph(name)[1]
-    extra, s = 300, (0.02, 22.5, 80)
-    F = 65536 + extra
-    y, _ = osdl_model.frames(name, 1.0, F, 31)
-    yd = to_dev(y, dec)
     p = fs_params(dec, 2, s, 1)
-    out = dec.osdl_fs_decode(yd, p)
-    head = dec.osdl_fs_decode(yd[:65536].contiguous(), p)
-    tail = dec.osdl_fs_decode(yd[65536:].contiguous(), p)
-    torch.cuda.synchronize()
-    for k in OUTS:
-        assert torch.equal(out[k][:65536], head[k]) and torch.equal(out[k][65536:], tail[k]), k
-    for sl in (slice(0, extra), slice(65536, F)):
-        front = osdl_model.front_oracle(G, y[sl])
-        ref = M.Batch(y[sl], front[0], front[3]).fs(2, *s)
-        assert len(set(ref["ntep"].tolist())) > 3            # premise: the frames of a wavefront differ in their scans
-        assert_fs({k: out[k][sl] for k in ("cw", "metric", "best", "ntep")}, ref, 1)
+
+    def model(ys):
+        front = osdl_model.front_oracle(G, ys)
+        return front, OF.fs_view(M.Batch(ys, front[0], front[3]).fs(2, *s), 1)
+    OF.check_frames_in_turn(FAM, dec, osdl_model.frames(name, 1.0, 65536 + 300, 31)[0], lambda yd: dec.osdl_fs_decode(yd, p), model,
+                            distinct_ntep=3)
 
 
 def test_fs_decode_is_graph_capturable():
@@ -388,23 +298,14 @@ def test_fs_decode_is_graph_capturable():
 @pytest.mark.parametrize("name", ["wimax_1056"] + list(osdl_model.REFUSED))
 def test_unsupported_shapes_are_refused(name):
     dec = decoder(name)
-    assert not dec.osdl_supported and not dec.osdx_supported and not dec.osdw_supported
-    y, _ = osdl_model.frames(name, 2.0, 4, 1)
-    yd = to_dev(y, dec)
-    bufs = sentinels(dec, 4)
-    clean = {k: v.clone() for k, v in bufs.items()}
+    assert not dec.osdx_supported and not dec.osdw_supported
+    yd = to_dev(osdl_model.frames(name, 2.0, 4, 1)[0], dec)
     p = fs_params(dec, 1, (0.1, 4.5, 30), 1)
-    mask = torch.zeros((4,) + layout(dec)[2], dtype=torch.int64, device=dec.device)
-    msg = rf"\(-5\).*{NEEDS}.*\({dec.n},{dec.k}\)"
-    with pytest.raises(_lib.LdpcError, match=r"ldpc_osdl_fs_search.*" + msg):
-        dec.osdl_fs_search(yd, bufs["perm"], bufs["parity"], p, out=bufs)
-    with pytest.raises(_lib.LdpcError, match=r"ldpc_osdl_fs_decode.*" + msg):
-        dec.osdl_fs_decode(yd, p, perm=bufs["perm"], parity=bufs["parity"], out=bufs)
-    with pytest.raises(_lib.LdpcError, match=r"ldpc_osdl_tep_eval.*" + msg):
-        dec.osdl_tep_eval(yd, bufs["perm"], bufs["parity"], mask)
-    torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    mask = torch.zeros((4,) + FAM.layout(dec.n, dec.k)[3], dtype=torch.int64, device=dec.device)
+    OF.check_unsupported(FAM, dec, yd, {
+        "fs_search": lambda b: dec.osdl_fs_search(yd, b["perm"], b["parity"], p, out=b),
+        "fs_decode": lambda b: dec.osdl_fs_decode(yd, p, perm=b["perm"], parity=b["parity"], out=b),
+        "tep_eval": lambda b: dec.osdl_tep_eval(yd, b["perm"], b["parity"], mask)})
 
 
 def test_bad_arguments_are_refused():
@@ -416,42 +317,10 @@ def test_bad_arguments_are_refused():
     clean = {k: v.clone() for k, v in bufs.items()}
     s = (0.1, 9.5, 60)
     good = fs_params(dec, 2, s, 1)
-    aux = torch.zeros((4, 4), dtype=torch.int32, device=dec.device)
     mask = torch.zeros((4, 2), dtype=torch.int64, device=dec.device)
-    bad = [(dec.osd_params(2, _lib.OSD_CONVENTIONAL), r"algo 0 is not LDPC_OSD_FS"),
-           (dec.osd_params(2, _lib.OSD_PB), r"algo 2 is not LDPC_OSD_FS"),
-           (fs_params(dec, 4, s, 1), r"order 4 outside 0\.\.3"),
-           (fs_params(dec, -1, s, 1), r"order -1 outside 0\.\.3"),
-           (fs_params(dec, 2, s, 1, table_scan=True), r"flags 0x1 are not served here"),
-           (fs_params(dec, 2, s, 1, aux=aux), r"d_aux is not served here"),
-           (fs_params(dec, 2, s, 1, y_frames=4), r"y_frames 4 is not served here")]
-    for p, why in bad:
-        with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdl_fs_decode: " + why):
-            dec.osdl_fs_decode(yd, p, perm=bufs["perm"], parity=bufs["parity"], out=bufs)
-        with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdl_fs_search: " + why):
-            dec.osdl_fs_search(yd, bufs["perm"], bufs["parity"], p, out=bufs)
-    for missing in ("cw", "perm", "parity"):
-        assert _raw_decode(dec, yd, None, None, 4, good, {**bufs, missing: None}) == -1
-        assert f"ldpc_osdl_fs_decode: d_{missing} is NULL".encode() in dec.L.ldpc_last_error()
-        assert _raw_search(dec, yd, 4, good, {**bufs, missing: None}) == -1
-        assert f"ldpc_osdl_fs_search: d_{missing} is NULL".encode() in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, None, None, None, 4, good, bufs) == -1 and b"ldpc_osdl_fs_decode: d_y is NULL" in dec.L.ldpc_last_error()
-    assert _raw_search(dec, None, 4, good, bufs) == -1 and b"ldpc_osdl_fs_search: d_y is NULL" in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, yd, None, None, 4, None, bufs) == -1 and b"ldpc_osdl_fs_decode: params is NULL" in dec.L.ldpc_last_error()
-    assert _raw_search(dec, yd, 4, None, bufs) == -1 and b"ldpc_osdl_fs_search: params is NULL" in dec.L.ldpc_last_error()
-    for missing in ("y", "perm", "parity", "mask", "cw"):
-        a = dict(y=yd, perm=bufs["perm"], parity=bufs["parity"], mask=mask, cw=bufs["cw"])
-        a[missing] = None
-        assert _raw_tep_eval(dec, a["y"], 4, a["perm"], a["parity"], a["mask"], a["cw"], None, None) == -1
-        assert f"ldpc_osdl_tep_eval: d_{missing} is NULL".encode() in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, yd, None, None, 0, good, {}) == 0              # F == 0: LDPC_OK, no launch
-    assert _raw_search(dec, yd, 0, good, {}) == 0
-    assert _raw_tep_eval(dec, None, 0, None, None, None, None, None, None) == 0
-    # a negative F and a missing context are LDPC_E_ARG
-    assert _raw_search(dec, yd, -1, good, bufs) == -1 and b"ldpc_osdl_fs_search: bad arguments" in dec.L.ldpc_last_error()
+    OF.check_bad_arguments(FAM, "fs", dec, yd, bufs, lambda order, **kw: fs_params(dec, order, s, 1, **kw), good, mask)
     torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    OF.assert_untouched(bufs, clean)
 
 
 def test_order_is_bounded_by_k():
@@ -469,8 +338,7 @@ def test_order_is_bounded_by_k():
     with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdl_fs_search: order 2 outside 0\.\.1"):
         dec.osdl_fs_search(yd, bufs["perm"], bufs["parity"], fs_params(dec, 2, s, 1), out=bufs)
     torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    OF.assert_untouched(bufs, clean)
     front = osdl_model.front_oracle(osdl_model.graph(name)[1], y)
     ref = M.Batch(y, front[0], front[3]).fs(1, *s)
     assert (ref["depth"] == 1).any() and len(set(ref["ntep"].tolist())) == 2

@@ -4,78 +4,41 @@ tests/osdl_model.py, on full scans and first-TEP stops that one wavefront decode
 just above each tier boundary, on tied reliability sums, and against ldpc_osdx_pb_* / ldpc_osdw_pb_* on the codes an older
 family serves as well.  The inputs and what they reach are those tests/test_osdl_pb_host.py asserts on the CPU.  Integers
 compare equal, floats by their bits."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from short_ldpc_decoding_osd_amd import _lib
+from tests import osd_family as OF
 from tests import osdl_model
 from tests import osdl_pb_model as LP
-from tests.gpu_util import pack_np, to_dev, words_np
+from tests.gpu_util import pack_np, to_dev
+from tests.osd_family import assert_pb, assert_same, decoder, new_aux, pb_params
 
 pytestmark = pytest.mark.gpu
-NEEDS = r"n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192"
+FAM = OF.OSDL
 KEYS = ("cw", "metric", "best", "ntep", "aux")
-_decoders = {}
-
-
-def decoder(code):
-    """A context of a named code of osdl_model, or of a shape (k, n) (osdl_pb_model.graph)."""
-    if code not in _decoders:
-        from short_ldpc_decoding_osd_amd import Code
-        from short_ldpc_decoding_osd_amd.runtime import Decoder
-        c = Code(H=LP.graph(code)[0]) if isinstance(code, tuple) else osdl_model.make_code(code)
-        _decoders[code] = Decoder(c)
-    return _decoders[code]
-
-
-def layout(dec):
-    """Shape tails of perm and parity."""
-    S, W, Wp = dec.words, (dec.k + 63) // 64, (dec.n - dec.k + 63) // 64
-    return (64 * S,), ((64 * W,) if Wp == 1 else (64 * W, Wp))
 
 
 def dev_front(perm, parity, dec):
-    """The oracle's perm [F, 64 S] u16 and parity [F, 64 W, Wp] u64 as the device tensors of the binding."""
-    return (to_dev(np.ascontiguousarray(perm).view(np.int16), dec),
-            to_dev(np.ascontiguousarray(parity).view(np.int64).reshape((len(perm),) + layout(dec)[1]), dec))
+    return OF.dev_front(perm, parity, dec, FAM)
 
-
-def new_aux(dec, F):
-    return torch.full((F, 4), -9, dtype=torch.int32, device=dec.device)
-
-
-def pb_params(dec, order, snr_db, aux=None, **kw):
-    return dec.osd_params(order, _lib.OSD_PB, snr_db=snr_db, aux=aux, **kw)
-
-
-def assert_pb(out, aux, ref, sl=slice(None), pick=None, where=""):
-    """Every output bit for bit: cw, metric as uint32, best, ntep and the four aux columns.  ``pick``: the model's frames that
-    the outputs hold, in order (a frame list)."""
-    pick = np.arange(len(ref["best"])) if pick is None else np.asarray(pick)
-    assert np.array_equal(words_np(out["cw"])[sl], ref["cw"][pick][sl]), where
-    assert np.array_equal(out["metric"].cpu().numpy().view(np.uint32)[sl], ref["metric"][pick].view(np.uint32)[sl]), where
-    assert np.array_equal(out["best"].cpu().numpy()[sl], ref["best"][pick][sl]), where
-    assert np.array_equal(out["ntep"].cpu().numpy()[sl], ref["ntep"][pick][sl]), where
-    if aux is not None:
-        assert np.array_equal(aux.cpu().numpy()[sl], ref["aux"][pick][sl]), where
 
 
 def assert_front(perm, parity, front, dec, pick=slice(None)):
-    """perm and parity, padding included: the oracle's arrays are zero there."""
-    W, Wp = (dec.k + 63) // 64, (dec.n - dec.k + 63) // 64
-    assert np.array_equal(perm.cpu().numpy().view(np.uint16), front[0][pick])
-    assert np.array_equal(words_np(parity).reshape(-1, 64 * W, Wp), front[1][pick])
+    OF.assert_front(FAM, dec, perm, parity, front, rows=pick)
 
 
-def assert_same(got, want, keys, where=""):
-    for key in keys:
-        a, b = got[key], want[key]
-        if a.dtype == torch.float32:
-            a, b = a.view(torch.int32), b.view(torch.int32)
-        assert torch.equal(a, b), (where, key)
+def sentinels(dec, F):
+    return OF.sentinels(dec, FAM, F, aux=True)
+
+
+def _raw_decode(dec, *args, **kw):
+    return OF.raw_decode(dec, FAM, "pb_decode", *args, **kw)
+
+
+def _raw_search(dec, *args):
+    return OF.raw_search(dec, FAM, "pb_search", *args)
 
 
 def check_against_model(dec, y, front, order, snr_db, ref, where=""):
@@ -210,28 +173,6 @@ def test_equals_the_older_family(name, order):
 # ---------------------------------------------------------------------------------------------------------------------
 # 6: frame lists, device-side counts, nullable outputs, counters
 # ---------------------------------------------------------------------------------------------------------------------
-def sentinels(dec, F):
-    ptail, qtail = layout(dec)
-    mk = lambda shape, dt, v: torch.full(shape, v, dtype=dt, device=dec.device)      # noqa: E731
-    return dict(perm=mk((F,) + ptail, torch.int16, 0x6EEE), parity=mk((F,) + qtail, torch.int64, -1), cw=mk((F, dec.words), torch.int64, -1),
-                metric=mk((F,), torch.float32, -5.0), best=mk((F,), torch.int32, -9), ntep=mk((F,), torch.int32, -9), aux=new_aux(dec, F))
-
-
-_p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-
-
-def _raw_decode(dec, yd, index, count, F, params, bufs, label=None, counts=None):
-    return dec.L.ldpc_osdl_pb_decode(dec._ctx, _p(yd), _p(index), _p(count), F, C.byref(params) if params is not None else None,
-                                     _p(bufs.get("perm")), _p(bufs.get("parity")), _p(bufs.get("cw")), _p(bufs.get("metric")),
-                                     _p(bufs.get("best")), _p(bufs.get("ntep")), _p(label), _p(counts), dec._stream())
-
-
-def _raw_search(dec, yd, F, params, bufs):
-    return dec.L.ldpc_osdl_pb_search(dec._ctx, _p(yd), None, None, F, _p(bufs.get("perm")), _p(bufs.get("parity")),
-                                     C.byref(params) if params is not None else None, _p(bufs.get("cw")), _p(bufs.get("metric")),
-                                     _p(bufs.get("best")), _p(bufs.get("ntep")), dec._stream())
-
-
 @pytest.fixture(scope="module")
 def listed():
     """wl384, the 12 frames of NATURAL[0] (order 2, both stop rules, three first-TEP stops): a list of 20 of them with repeats,
@@ -243,71 +184,25 @@ def listed():
     nf = len(idx)
     assert len(set(idx.tolist())) < nf and np.any(np.diff(idx) < 0)
     assert len(set(ref["aux"][idx, 3].tolist())) == 2 and len(set(ref["ntep"][idx].tolist())) > 3
-    return dict(dec=dec, yd=to_dev(y, dec), labels=cw, index=to_dev(idx, dec), count=to_dev(np.array([nf], np.int32), dec), nf=nf,
-                idx=idx, ref=ref, front=front, order=order, snr_db=snr_db)
+    return dict(dec=dec, yd=to_dev(y, dec), labels=cw, label_rows=idx, index=to_dev(idx, dec),
+                count=to_dev(np.array([nf], np.int32), dec), nf=nf, rows=idx, ref=ref, front=front, order=order, snr_db=snr_db,
+                arg=lambda bufs: pb_params(dec, order, snr_db, bufs["aux"]), some_wrong=False)
 
 
 @pytest.mark.parametrize("which", ["smaller", "equal", "larger"])
 def test_frame_list_and_device_count(listed, which):
-    dec, nf = listed["dec"], listed["nf"]
-    F = {"smaller": nf + 13, "equal": nf, "larger": nf - 9}[which]       # the device count against the capacity F
-    done = min(nf, F)
-    bufs = sentinels(dec, nf + 13)
-    clean = {k: v.clone() for k, v in bufs.items()}
-    params = pb_params(dec, listed["order"], listed["snr_db"], bufs["aux"])
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], F, params, bufs) == 0
-    torch.cuda.synchronize()
-    pick = np.concatenate([listed["idx"], np.zeros(13, np.int32)])       # (rows beyond `done` are not compared)
-    assert_pb(bufs, bufs["aux"], listed["ref"], slice(0, done), pick)
-    assert_front(bufs["perm"][:done], bufs["parity"][:done], listed["front"], dec, listed["idx"][:done])
-    for k in bufs:                                                       # nothing at or beyond min(count, F)
-        assert torch.equal(bufs[k][done:], clean[k][done:]), k
+    OF.check_frame_list(FAM, "pb_decode", listed, which)
 
 
 @pytest.mark.parametrize("off", ["none", "metric", "best", "ntep", "aux", "counts", "label", "metric+best+ntep+aux"])
 def test_nullable_outputs_and_counters(listed, off):
-    dec, nf, ref, idx = listed["dec"], listed["nf"], listed["ref"], listed["idx"]
-    label = to_dev(pack_np(listed["labels"]).view(np.int64), dec)
-    bufs = sentinels(dec, nf)
-    counts = torch.tensor([5, 6, 7], dtype=torch.int64, device=dec.device)
-    gone = off.split("+")
-    for key in gone:
-        if key in bufs:
-            bufs[key] = None
-    params = pb_params(dec, listed["order"], listed["snr_db"], bufs["aux"])
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], nf, params, bufs,
-                       None if off == "label" else label, None if off == "counts" else counts) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(words_np(bufs["cw"]), ref["cw"][idx])
-    if "metric" not in gone:
-        assert np.array_equal(bufs["metric"].cpu().numpy().view(np.uint32), ref["metric"][idx].view(np.uint32))
-    for key in ("best", "ntep", "aux"):
-        if key not in gone:
-            assert np.array_equal(bufs[key].cpu().numpy(), ref[key][idx]), key
-    # the counters, recomputed on the host: teps_total is the sum of the per-frame ntep and moves only with d_ntep
-    wrong = int(np.any(ref["cw"][idx] != pack_np(listed["labels"][idx]), axis=1).sum())
-    want = [5, 6, 7] if off in ("counts", "label") else [5 + nf, 6 + wrong, 7 + (0 if "ntep" in gone else int(ref["ntep"][idx].sum()))]
-    assert counts.cpu().tolist() == want
+    OF.check_nullable(FAM, "pb_decode", listed, off)
 
 
 @pytest.mark.parametrize("mask", range(1, 15))
 def test_every_subset_of_the_nullable_outputs_through_the_search(listed, mask):
     """metric, best, ntep and aux: each of the 14 proper non-empty subsets present, the others NULL (all and none: above)."""
-    dec, ref, front = listed["dec"], listed["ref"], listed["front"]
-    F = 12
-    names = ("metric", "best", "ntep", "aux")
-    bufs = sentinels(dec, F)
-    bufs["perm"], bufs["parity"] = dev_front(front[0][:F], front[1][:F], dec)
-    for b, key in enumerate(names):
-        if not (mask >> b) & 1:
-            bufs[key] = None
-    assert _raw_search(dec, listed["yd"], F, pb_params(dec, listed["order"], listed["snr_db"], bufs["aux"]), bufs) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(words_np(bufs["cw"]), ref["cw"][:F])
-    for key in names:
-        if bufs[key] is not None:
-            got, want = bufs[key].cpu().numpy(), ref[key][:F]
-            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)) if key == "metric" else np.array_equal(got, want), key
+    OF.check_nullable_subsets(FAM, "pb_search", listed, mask)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -316,20 +211,11 @@ def test_every_subset_of_the_nullable_outputs_through_the_search(listed, mask):
 @pytest.mark.parametrize("name", ["wimax_1056"] + list(osdl_model.REFUSED))
 def test_unsupported_shapes_are_refused(name):
     dec = decoder(name)
-    assert not dec.osdl_supported and not dec.osdx_supported and not dec.osdw_supported
-    y, _ = osdl_model.frames(name, 2.0, 4, 1)
-    yd = to_dev(y, dec)
-    bufs = sentinels(dec, 4)
-    clean = {k: v.clone() for k, v in bufs.items()}
-    p = pb_params(dec, 1, 1.0, bufs["aux"])
-    msg = rf"\(-5\).*{NEEDS}.*\({dec.n},{dec.k}\)"
-    with pytest.raises(_lib.LdpcError, match=r"ldpc_osdl_pb_search.*" + msg):
-        dec.osdl_pb_search(yd, bufs["perm"], bufs["parity"], p, out=bufs)
-    with pytest.raises(_lib.LdpcError, match=r"ldpc_osdl_pb_decode.*" + msg):
-        dec.osdl_pb_decode(yd, p, perm=bufs["perm"], parity=bufs["parity"], out=bufs)
-    torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    assert not dec.osdx_supported and not dec.osdw_supported
+    yd = to_dev(osdl_model.frames(name, 2.0, 4, 1)[0], dec)
+    OF.check_unsupported(FAM, dec, yd, {
+        "pb_search": lambda b: dec.osdl_pb_search(yd, b["perm"], b["parity"], pb_params(dec, 1, 1.0, b["aux"]), out=b),
+        "pb_decode": lambda b: dec.osdl_pb_decode(yd, pb_params(dec, 1, 1.0, b["aux"]), perm=b["perm"], parity=b["parity"], out=b)})
 
 
 def test_bad_arguments_are_refused_and_the_older_families_keep_their_refusal():
@@ -340,36 +226,10 @@ def test_bad_arguments_are_refused_and_the_older_families_keep_their_refusal():
     bufs = sentinels(dec, 4)
     clean = {k: v.clone() for k, v in bufs.items()}
     good = pb_params(dec, 2, 1.5, bufs["aux"])
-    bad = [(dec.osd_params(2, _lib.OSD_CONVENTIONAL), r"algo 0 is not LDPC_OSD_PB"),
-           (dec.osd_params(2, _lib.OSD_FS), r"algo 1 is not LDPC_OSD_PB"),
-           (pb_params(dec, 4, 1.5), r"order 4 outside 0\.\.3"),
-           (pb_params(dec, -1, 1.5), r"order -1 outside 0\.\.3"),
-           (pb_params(dec, 2, 1.5, pb_path="replay"), r"flags 0x4 are not served here"),
-           (pb_params(dec, 2, 1.5, table_scan=True), r"flags 0x1 are not served here"),
-           (pb_params(dec, 2, 1.5, y_frames=4), r"y_frames 4 is not served here")]
-    for p, why in bad:
-        with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdl_pb_decode: " + why):
-            dec.osdl_pb_decode(yd, p, perm=bufs["perm"], parity=bufs["parity"], out=bufs)
-        with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdl_pb_search: " + why):
-            dec.osdl_pb_search(yd, bufs["perm"], bufs["parity"], p, out=bufs)
-    for missing in ("cw", "perm", "parity"):
-        assert _raw_decode(dec, yd, None, None, 4, good, {**bufs, missing: None}) == -1
-        assert f"ldpc_osdl_pb_decode: d_{missing} is NULL".encode() in dec.L.ldpc_last_error()
-        assert _raw_search(dec, yd, 4, good, {**bufs, missing: None}) == -1
-        assert f"ldpc_osdl_pb_search: d_{missing} is NULL".encode() in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, None, None, None, 4, good, bufs) == -1 and b"ldpc_osdl_pb_decode: d_y is NULL" in dec.L.ldpc_last_error()
-    assert _raw_search(dec, None, 4, good, bufs) == -1 and b"ldpc_osdl_pb_search: d_y is NULL" in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, yd, None, None, 4, None, bufs) == -1 and b"ldpc_osdl_pb_decode: params is NULL" in dec.L.ldpc_last_error()
-    assert _raw_search(dec, yd, 4, None, bufs) == -1 and b"ldpc_osdl_pb_search: params is NULL" in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, yd, None, None, -1, good, bufs) == -1 and b"ldpc_osdl_pb_decode: bad arguments" in dec.L.ldpc_last_error()
-    assert _raw_search(dec, yd, -1, good, bufs) == -1 and b"ldpc_osdl_pb_search: bad arguments" in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, yd, None, None, 0, good, {}) == 0              # F == 0: LDPC_OK, no launch
-    assert _raw_search(dec, yd, 0, good, {}) == 0
+    OF.check_bad_arguments(FAM, "pb", dec, yd, bufs, lambda order, **kw: pb_params(dec, order, 1.5, **kw), good)
     # the older families still refuse this code, in their own words
     old = {k: v for k, v in bufs.items() if k not in ("perm", "parity")}
-    perm8 = torch.full((4, 128), 0xEE, dtype=torch.uint8, device=dec.device)
-    par64 = torch.full((4, 64), -1, dtype=torch.int64, device=dec.device)
-    par128 = torch.full((4, 128), -1, dtype=torch.int64, device=dec.device)
+    perm8, par64, par128 = (OF.A.sentinel(dec, (4, w), dt) for w, dt in ((128, torch.uint8), (64, torch.int64), (128, torch.int64)))
     osdx = r"\(-5\).*the any-shape OSD kernels need 1 <= k <= 64 and 1 <= n-k <= 64; this code is \(200,100\)"
     osdw = r"\(-5\).*the high-rate OSD kernels need 1 <= n-k <= 64 and n <= 128; this code is \(200,100\)"
     with pytest.raises(_lib.LdpcError, match=osdx):
@@ -381,9 +241,8 @@ def test_bad_arguments_are_refused_and_the_older_families_keep_their_refusal():
     with pytest.raises(_lib.LdpcError, match=osdw):
         dec.osdw_pb_decode(yd, good, perm=perm8, parity=par128, out=old)
     torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
-    assert bool((perm8 == 0xEE).all()) and bool((par64 == -1).all()) and bool((par128 == -1).all())
+    OF.assert_untouched(bufs, clean)
+    assert OF.A.untouched(perm8) and OF.A.untouched(par64) and OF.A.untouched(par128)
 
 
 def test_order_is_bounded_by_k():
@@ -400,8 +259,7 @@ def test_order_is_bounded_by_k():
     with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdl_pb_search: order 2 outside 0\.\.1"):
         dec.osdl_pb_search(yd, bufs["perm"], bufs["parity"], pb_params(dec, 2, 0.0), out=bufs)
     torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    OF.assert_untouched(bufs, clean)
     ref0 = LP.pb(y, front[0], front[3], 0, snr_db)
     aux = new_aux(dec, len(y))
     out = dec.osdl_pb_decode(yd, pb_params(dec, 0, snr_db, aux))

@@ -10,19 +10,21 @@ restatements and whose premises it asserts.  Integers compare equal, floats as u
   4  non-zero padding of perm and P': ignored by every search entry point; a device-side count below F
   5  structured codes (zero columns, repeated columns, a rank-one parity part of G) through the device front end and the decodes
 """
-import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 from short_ldpc_decoding_osd_amd import _lib
+from tests import osd_family as OF
 from tests import osd_shapes as S
 from tests import osdl_model, osdl_pb_model
 from tests import osdl_shapes as LS
 from tests import osdw_fs_model as W
 from tests import osdx_fs_model as M
-from tests.gpu_util import to_dev, words_np
+from tests.gpu_util import to_dev
+from tests.osd_family import fs_params, new_aux
 
 pytestmark = pytest.mark.gpu
 LONG_CASES = [(k, n, name) for k, n in LS.LONG for name in LS.STRUCTURES]
@@ -30,23 +32,20 @@ SHORT_CASES = [(k, n, name) for k, n in LS.SHORT for name in LS.STRUCTURES]
 CODE_CASES = [(k, n, name) for k, n in LS.CODE_SHAPES for name in LS.CODE_STRUCTURES]
 LONG_PAIRS = (("float", "sorted"), ("grid", "sorted"), ("float", "unsorted"))
 SCAN_KEYS = ("cw", "metric", "best", "ntep")
-_decoders, _REF = {}, {}
-_p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+FAM = OF.OSDL
+_REF = {}
+
+
+def _graph(k, n, name):
+    return LS.context_graph(k, n) if name is None else LS.code(k, n, name)[:2]
 
 
 def decoder(k, n, name=None):
     """A context of the shape (a plain H = [A | I] code: the searches never read G), or of the structured code ``name``."""
-    key = (k, n, name)
-    if key not in _decoders:
-        from short_ldpc_decoding_osd_amd import Code
-        from short_ldpc_decoding_osd_amd.runtime import Decoder
-        H, G = LS.context_graph(k, n) if name is None else LS.code(k, n, name)[:2]
-        code = Code(H=H)
-        assert np.array_equal(code.G, G) and (code.k, code.check_matrix_column) == (k, n)
-        dec = Decoder(code)
-        assert dec.osdl_supported and dec.osdw_supported == (n <= 128 and n - k <= 64) and dec.osdx_supported == (k <= 64 and n - k <= 64)
-        _decoders[key] = dec
-    return _decoders[key]
+    dec = OF.decoder((k, n, name), _graph)
+    assert np.array_equal(dec.code.G, _graph(k, n, name)[1]) and (dec.code.k, dec.code.check_matrix_column) == (k, n)
+    assert dec.osdl_supported and dec.osdw_supported == (n <= 128 and n - k <= 64) and dec.osdx_supported == (k <= 64 and n - k <= 64)
+    return dec
 
 
 def ref(kind, c, *args):
@@ -75,44 +74,20 @@ def ref(kind, c, *args):
     return _REF[key]
 
 
-def u32(t):
-    return (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.ascontiguousarray(t)).view(np.uint32)
-
-
 def assert_scan(out, want, tag):
-    F = len(want["best"])
-    assert np.array_equal(words_np(out["cw"])[:F], want["cw"]), tag
-    assert np.array_equal(u32(out["metric"])[:F], u32(want["metric"])), tag
-    assert np.array_equal(out["best"].cpu().numpy()[:F], want["best"]), tag
-    assert np.array_equal(out["ntep"].cpu().numpy()[:F], want["ntep"]), tag
+    OF.assert_scan(out, want, len(want["best"]), tag)
 
 
 def assert_fs(out, want, quirk, tag):
-    key = "ref" if quirk else "hit"
-    assert_scan(out, dict(cw=want["cw_" + key], metric=want["metric_" + key], best=want["best_" + key], ntep=want["ntep"]), tag)
+    assert_scan(out, OF.fs_view(want, quirk), tag)
 
 
 def assert_same(a, b, tag, keys=SCAN_KEYS):
-    for key in keys:
-        x, y = a[key], b[key]
-        if x.dtype == torch.float32:
-            x, y = x.view(torch.int32), y.view(torch.int32)
-        assert torch.equal(x, y), tag + (key,)
-
-
-def fs_params(dec, order, s, quirk):
-    return dec.osd_params(order, _lib.OSD_FS, fs_beta=s[0], fs_tau_e=s[1], fs_tau_psc=s[2], fs_reference_quirk=quirk)
-
-
-def new_aux(dec, F):
-    return torch.full((F, 4), -9, dtype=torch.int32, device=dec.device)
+    OF.assert_same(a, b, keys, tag)
 
 
 def dev_front(perm, parity, dec):
-    """perm [F, 64 S] u16 and parity [F, 64 W, Wp] u64 as the device tensors of the binding (parity [F, 64 W] where Wp = 1)."""
-    parity = np.ascontiguousarray(parity).view(np.int64)
-    return (to_dev(np.ascontiguousarray(perm).view(np.int16), dec),
-            to_dev(parity.reshape(parity.shape[:2]) if parity.shape[2] == 1 else parity, dec))
+    return OF.dev_front(perm, parity, dec, FAM)
 
 
 def run_searches(dec, c, padding=False):
@@ -145,10 +120,7 @@ def _check_conv(c, args, got, tag):
 
 
 def _check_tep(c, args, got, tag):
-    want = ref("tep", c, args[0])
-    assert np.array_equal(words_np(got["cw"]), want["cw"]), tag
-    assert np.array_equal(u32(got["metric"]), u32(want["metric"])), tag
-    assert np.array_equal(got["hd"].cpu().numpy(), want["hd"]), tag
+    OF.assert_outputs(got, ref("tep", c, args[0]), where=tag, keys=("cw", "metric", "hd"))
 
 
 def _check_fs(c, args, got, tag):
@@ -156,9 +128,7 @@ def _check_fs(c, args, got, tag):
 
 
 def _check_pb(c, args, got, tag):
-    want = ref("pb", c, args[0])
-    assert_scan(got, want, tag)
-    assert np.array_equal(got["aux"].cpu().numpy(), want["aux"]), tag
+    OF.assert_pb(got, got["aux"], ref("pb", c, args[0]), where=tag)
 
 
 # the calls of run_searches: (checker against the model, outputs compared between runs)
@@ -269,12 +239,9 @@ def test_padding_of_the_inputs_is_ignored(k, n):
 
 
 def _sentinels(dec, F):
-    return dict(cw=torch.full((F, dec.words), -1, dtype=torch.int64, device=dec.device),
-                metric=torch.full((F,), -5.0, dtype=torch.float32, device=dec.device),
-                best=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                ntep=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                hd=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                aux=torch.full((F, 4), -9, dtype=torch.int32, device=dec.device))
+    """The outputs of the search calls (no perm / parity: they are inputs here) and hd."""
+    b = OF.sentinels(dec, FAM, F, aux=True)
+    return dict({k: b[k] for k in SCAN_KEYS + ("aux",)}, hd=OF.A.sentinel(dec, (F,), torch.int32))
 
 
 @pytest.mark.parametrize("k,n", [(65, 129), (192, 384)])
@@ -291,10 +258,9 @@ def test_padding_through_raw_calls_with_sentinels(k, n):
     count = to_dev(np.array([done], np.int32), dec)
     s = LS.fs_sets(k, n)[0]
     order = LS.fs_order(k)
-    L, ctx, st = dec.L, dec._ctx, dec._stream()
+    front = dict(d_y=yd, d_count=count, F=F, d_perm=perm, d_parity=parity)
     conv = ref("conv", c, 2)
-    r = ref("fs", c, *s)
-    fs = dict(cw=r["cw_ref"], metric=r["metric_ref"], best=r["best_ref"], ntep=r["ntep"])
+    fs = OF.fs_view(ref("fs", c, *s), 1)
     tep = ref("tep", c, 3)
     md = to_dev(LS.split_masks(ref("masks", c)[3], k).view(np.int64), dec)
     fsp, runs = fs_params(dec, order, s, 1), []
@@ -304,28 +270,18 @@ def test_padding_through_raw_calls_with_sentinels(k, n):
         assert call(b) == 0, (name, dec.L.ldpc_last_error())
         runs.append((name, b, {key: want[key] for key in keys}))
 
-    run("osdl_search", conv, SCAN_KEYS, lambda b: L.ldpc_osdl_search(
-        ctx, _p(yd), None, _p(count), F, _p(perm), _p(parity), 2, _p(b["cw"]), _p(b["metric"]), _p(b["best"]), _p(b["ntep"]), st))
-    run("osdl_fs_search", fs, SCAN_KEYS, lambda b: L.ldpc_osdl_fs_search(
-        ctx, _p(yd), None, _p(count), F, _p(perm), _p(parity), C.byref(fsp), _p(b["cw"]), _p(b["metric"]), _p(b["best"]),
-        _p(b["ntep"]), st))
-    run("osdl_tep_eval", tep, ("cw", "metric", "hd"), lambda b: L.ldpc_osdl_tep_eval(
-        ctx, _p(yd), None, _p(count), F, _p(perm), _p(parity), _p(md), _p(b["cw"]), _p(b["metric"]), _p(b["hd"]), st))
+    run("osdl_search", conv, SCAN_KEYS, lambda b: OF.raw(dec, FAM, "search", b, order=2, **front))
+    run("osdl_fs_search", fs, SCAN_KEYS, lambda b: OF.raw(dec, FAM, "fs_search", b, params=fsp, **front))
+    run("osdl_tep_eval", tep, ("cw", "metric", "hd"), lambda b: OF.raw(dec, FAM, "tep_eval", b, d_mask=md, **front))
 
     def pb_call(b):
-        pb = dec.osd_params(order, _lib.OSD_PB, snr_db=1.0, aux=b["aux"])
-        return L.ldpc_osdl_pb_search(ctx, _p(yd), None, _p(count), F, _p(perm), _p(parity), C.byref(pb), _p(b["cw"]),
-                                     _p(b["metric"]), _p(b["best"]), _p(b["ntep"]), st)
+        return OF.raw(dec, FAM, "pb_search", b, params=dec.osd_params(order, _lib.OSD_PB, snr_db=1.0, aux=b["aux"]), **front)
     run("osdl_pb_search", ref("pb", c, 1.0), SCAN_KEYS + ("aux",), pb_call)
     torch.cuda.synchronize()
     clean = _sentinels(dec, F)
     assert len(runs) == 4
     for name, b, want in runs:
-        for key, w in want.items():
-            got = words_np(b[key]) if key == "cw" else b[key].cpu().numpy()
-            if key == "metric":
-                got, w = u32(got), u32(w)
-            assert np.array_equal(got[:done], w[:done]), (name, key)
+        OF.assert_outputs(b, want, slice(0, done), where=name, keys=tuple(want))
         for key in b:
             lo = done if key in want else 0                  # an output the call does not have stays untouched altogether
             assert torch.equal(b[key][lo:], clean[key][lo:]), (name, key)
@@ -334,23 +290,9 @@ def test_padding_through_raw_calls_with_sentinels(k, n):
 # ---------------------------------------------------------------------------------------------------------------------
 # 5: structured codes through the device front end
 # ---------------------------------------------------------------------------------------------------------------------
-def front_np(perm, parity, k, n):
-    """Device front-end results in the oracle's types: perm [F, 64 S] u16, parity [F, 64 W, Wp] u64."""
-    _, W_, Wp = LS.layout(k, n)
-    return perm.cpu().numpy().view(np.uint16), words_np(parity).reshape(-1, 64 * W_, Wp)
-
-
 def assert_front(got, want, k, n, rows=slice(None)):
-    """perm, parity and nswaps against the oracle, whose arrays are zero in the padding; the zero padding once more by itself."""
-    perm, parity = front_np(got[0], got[1], k, n)
-    S_, W_, Wp = LS.layout(k, n)
-    assert perm.shape[1:] == (64 * S_,) and parity.shape[1:] == (64 * W_, Wp)
-    if got[2] is not None:
-        assert np.array_equal(got[2].cpu().numpy(), want[2][rows])
-    assert np.array_equal(perm, want[0][rows])
-    assert np.array_equal(parity, want[1][rows])
-    assert not perm[:, n:].any() and not parity[:, k:].any()
-    assert (n - k) % 64 == 0 or not (parity[:, :, Wp - 1] >> np.uint64((n - k) % 64)).any()
+    """perm, parity and nswaps against the oracle, whose arrays are zero in the padding."""
+    OF.assert_front(FAM, SimpleNamespace(n=n, k=k), got[0], got[1], want, got[2], rows)
 
 
 def decode_frames(k):

@@ -1,8 +1,6 @@
 """-m gpu: OSD for high-rate short codes (ldpc_osdw_front / _search / _decode: n <= 128, 1 <= n-k <= 64, k up to 127) --
 bit-exact against the CPU oracles of tests/osdw_model.py on (121,80), the zoo's deg65 (80,74) and four synthetic codes with
 k = 65, 96, 124 and 66, and against ldpc_osdx_* on CCSDS (128,64) and (121,60).  Floats compare by their bits."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -10,11 +8,13 @@ import torch
 from oracle import np_oracle
 from short_ldpc_decoding_osd_amd import _lib
 from tests import nms_graphs, osdw_model, osdx_model
+from tests import osd_family as OF
 from tests.gpu_util import pack_np, to_dev, words_np
+from tests.osd_family import assert_scan, decoder
 
 pytestmark = pytest.mark.gpu
 ALPHA0 = 0.669435
-_decoders, _front, _scan = {}, {}, {}
+_front, _scan = {}, {}
 
 # The classes of column exchanges the 256 front-end frames must hold, per code: frames without an exchange, frames with three or
 # more, recorded exchanges (a, b) with the pivot step a in the first / second word of the row map and the partner b in the
@@ -29,13 +29,6 @@ EXCHANGES = {
     "s70_66": dict(frames_0=20, frames_ge3=155, most=15, a_lt64=628, a_ge64=288, b_lt64=417, b_mid=195, b_gek=304),
 }
 SEARCHED = ("array_121_80", "s128_65", "s128_96")      # the codes whose order-2 winners have every weight
-
-
-def decoder(name):
-    if name not in _decoders:
-        from short_ldpc_decoding_osd_amd.runtime import Decoder
-        _decoders[name] = Decoder(nms_graphs.make_code(name) if name in ("wimax_1056", "wide") else osdw_model.make_code(name))
-    return _decoders[name]
 
 
 def front_case(name):
@@ -57,33 +50,20 @@ def scan_case(name, order, F):
     return _scan[key]
 
 
-def assert_front(got, want, n, k):
-    perm, parity, ns = got
-    perm_o, par_o, ns_o = want[:3]
-    perm, parity = perm.cpu().numpy(), words_np(parity)
-    assert parity.shape[1] == 128
-    assert np.array_equal(ns.cpu().numpy(), ns_o)
-    assert np.array_equal(perm[:, :n], perm_o[:, :n])
-    assert np.array_equal(parity[:, :k], par_o[:, :k])
-    assert not perm[:, n:].any() and not parity[:, k:].any()            # the padding is written as zero
-    assert not (parity >> np.uint64(n - k)).any() if n - k < 64 else True
+FAM = OF.OSDW
 
 
-def assert_scan(out, ref, F=None):
-    sl = slice(0, F)
-    assert np.array_equal(words_np(out["cw"])[sl], ref["cw"][sl])
-    assert np.array_equal(out["metric"].cpu().numpy().view(np.uint32)[sl], ref["metric"].view(np.uint32)[sl])
-    assert np.array_equal(out["best"].cpu().numpy()[sl], ref["best"][sl])
-    assert np.array_equal(out["ntep"].cpu().numpy()[sl], ref["ntep"][sl])
+def assert_front(got, want, dec):
+    """(perm, parity, nswaps) of a front-end call against a front_oracle result."""
+    OF.assert_front(FAM, dec, got[0], got[1], want, got[2])
 
 
 def _sentinels(dec, F):
-    return dict(perm=torch.full((F, 128), 0xEE, dtype=torch.uint8, device=dec.device),
-                parity=torch.full((F, 128), -1, dtype=torch.int64, device=dec.device),
-                cw=torch.full((F, dec.words), -1, dtype=torch.int64, device=dec.device),
-                metric=torch.full((F,), -5.0, dtype=torch.float32, device=dec.device),
-                best=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                ntep=torch.full((F,), -9, dtype=torch.int32, device=dec.device))
+    return OF.sentinels(dec, FAM, F)
+
+
+def _raw_decode(dec, *args, **kw):
+    return OF.raw_decode(dec, FAM, "decode", *args, **kw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -105,7 +85,7 @@ def test_front_end_matches_oracle(name):
     ns = torch.full((256,), -7, dtype=torch.int32, device=dec.device)
     got = dec.osdw_front(to_dev(y, dec), out=(b["perm"], b["parity"], ns))
     torch.cuda.synchronize()
-    assert_front(got, want, dec.n, dec.k)
+    assert_front(got, want, dec)
 
 
 def awkward_frames(G):
@@ -148,7 +128,7 @@ def test_front_end_awkward_inputs(name):
     torch.cuda.synchronize()
     perm = got[0].cpu().numpy()
     assert all(sorted(p[:dec.n]) == list(range(dec.n)) for p in perm.tolist())
-    assert_front(got, osdw_model.front_oracle(G, y), dec.n, dec.k)
+    assert_front(got, osdw_model.front_oracle(G, y), dec)
 
 
 def test_scan_without_a_finite_cost_flips_nothing():
@@ -190,13 +170,13 @@ def test_scan_matches_oracle(name, order, F):
     yd = to_dev(y, dec)
     fr = dec.osdw_front(yd)
     torch.cuda.synchronize()
-    assert_front(fr, front, dec.n, dec.k)                    # the search runs on oracle-checked front-end results
+    assert_front(fr, front, dec)                    # the search runs on oracle-checked front-end results
     out = dec.osdw_search(yd, fr[0], fr[1], order)
     full = dec.osdw_decode(yd, order)
     torch.cuda.synchronize()
     assert_scan(out, ref)
     assert_scan(full, ref)
-    assert_front((full["perm"], full["parity"], fr[2]), front, dec.n, dec.k)
+    assert_front((full["perm"], full["parity"], fr[2]), front, dec)
 
 
 def test_argmin_ties_go_to_the_first_minimum():
@@ -240,13 +220,6 @@ def test_narrow_codes_equal_the_any_shape_kernels(name):
 # ---------------------------------------------------------------------------------------------------------------------
 # 6: frame lists, device-side counts, nullable outputs, counters
 # ---------------------------------------------------------------------------------------------------------------------
-def _raw_decode(dec, yd, index, count, F, order, bufs, label=None, counts=None):
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-    return dec.L.ldpc_osdw_decode(dec._ctx, p(yd), p(index), p(count), F, order, p(bufs.get("perm")), p(bufs.get("parity")),
-                                  p(bufs.get("cw")), p(bufs.get("metric")), p(bufs.get("best")), p(bufs.get("ntep")),
-                                  p(label), p(counts), dec._stream())
-
-
 @pytest.fixture(scope="module")
 def listed():
     """array_121_80: 600 frames at 3.0 dB through NMS and ldpc_compact; the oracle of the listed frames at order 1."""
@@ -260,47 +233,19 @@ def listed():
     nf = int(count.cpu()[0])
     idx = index[:nf].cpu().numpy()
     assert 40 < nf < 600 and np.all(np.diff(idx) > 0)
-    ref = osdx_model.scan_oracle(G, y[idx], 1, osdw_model.front_oracle(G, y[idx]))
-    return dict(dec=dec, y=y, yd=yd, labels=cw, index=index, count=count, nf=nf, idx=idx, ref=ref)
+    front = osdw_model.front_oracle(G, y[idx])
+    return dict(dec=dec, y=y, yd=yd, labels=cw, label_rows=idx, index=index, count=count, nf=nf, rows=np.arange(nf), front=front,
+                ref=osdx_model.scan_oracle(G, y[idx], 1, front), arg=lambda bufs: 1)
 
 
 @pytest.mark.parametrize("which", ["smaller", "equal", "larger"])
 def test_frame_list_and_device_count(listed, which):
-    dec, nf = listed["dec"], listed["nf"]
-    F = {"smaller": nf + 13, "equal": nf, "larger": nf - 9}[which]       # the device count against the capacity F
-    done = min(nf, F)
-    bufs = _sentinels(dec, nf + 13)
-    clean = {k: v.clone() for k, v in bufs.items()}
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], F, 1, bufs) == 0
-    torch.cuda.synchronize()
-    assert_scan(bufs, listed["ref"], done)
-    for k in bufs:                                                       # nothing at or beyond min(count, F)
-        assert torch.equal(bufs[k][done:], clean[k][done:]), k
+    OF.check_frame_list(FAM, "decode", listed, which)
 
 
 @pytest.mark.parametrize("off", ["metric", "best", "ntep", "counts", "label"])
 def test_nullable_outputs_and_counters(listed, off):
-    dec, nf, ref = listed["dec"], listed["nf"], listed["ref"]
-    label = to_dev(pack_np(listed["labels"]).view(np.int64), dec)
-    bufs = _sentinels(dec, nf)
-    counts = torch.tensor([5, 6, 7], dtype=torch.int64, device=dec.device)
-    if off in bufs:
-        bufs[off] = None
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], nf, 1, bufs,
-                       None if off == "label" else label, None if off == "counts" else counts) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(words_np(bufs["cw"]), ref["cw"])
-    if off != "metric":
-        assert np.array_equal(bufs["metric"].cpu().numpy().view(np.uint32), ref["metric"].view(np.uint32))
-    if off != "best":
-        assert np.array_equal(bufs["best"].cpu().numpy(), ref["best"])
-    if off != "ntep":
-        assert np.array_equal(bufs["ntep"].cpu().numpy(), ref["ntep"])
-    # the counters, recomputed on the host from cw, the labels of the listed frames and ntep
-    wrong = int(np.any(ref["cw"] != pack_np(listed["labels"][listed["idx"]]), axis=1).sum())
-    assert 0 < wrong < nf
-    want = [5, 6, 7] if off in ("counts", "label") else [5 + nf, 6 + wrong, 7 + (0 if off == "ntep" else int(ref["ntep"].sum()))]
-    assert counts.cpu().tolist() == want
+    OF.check_nullable(FAM, "decode", listed, off)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -309,22 +254,14 @@ def test_nullable_outputs_and_counters(listed, off):
 def test_one_wavefront_decodes_several_frames_in_turn():
     """More frames than the grid's 65536 workgroups: wavefront b decodes frame b and then frame 65536 + b.  The frames that
     share a wavefront are checked against the oracle, all of them against the same frames decoded one per wavefront."""
-    dec = decoder("s70_66")
-    G = osdw_model.graph("s70_66")[1]
-    extra = 300
-    F = 65536 + extra
-    y, _ = osdw_model.frames("s70_66", 1.5, F, 31)
-    yd = to_dev(y, dec)
-    out = dec.osdw_decode(yd, 1)
-    head = dec.osdw_decode(yd[:65536].contiguous(), 1)
-    tail = dec.osdw_decode(yd[65536:].contiguous(), 1)
-    torch.cuda.synchronize()
-    for k in ("perm", "parity", "cw", "metric", "best", "ntep"):
-        assert torch.equal(out[k][:65536], head[k]) and torch.equal(out[k][65536:], tail[k]), k
-    for sl in (slice(0, extra), slice(65536, F)):
-        ref = osdx_model.scan_oracle(G, y[sl], 1, osdw_model.front_oracle(G, y[sl]))
-        part = {k: out[k][sl] for k in ("cw", "metric", "best", "ntep")}
-        assert_scan(part, ref)
+    name = "s70_66"
+    dec = decoder(name)
+    G = osdw_model.graph(name)[1]
+
+    def model(ys):
+        front = osdw_model.front_oracle(G, ys)
+        return front, osdx_model.scan_oracle(G, ys, 1, front)
+    OF.check_frames_in_turn(FAM, dec, osdw_model.frames(name, 1.5, 65536 + 300, 31)[0], lambda yd: dec.osdw_decode(yd, 1), model)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -333,21 +270,11 @@ def test_one_wavefront_decodes_several_frames_in_turn():
 @pytest.mark.parametrize("name", ["wimax_1056", "wide"])
 def test_unsupported_shapes_are_refused(name):
     dec = decoder(name)
-    assert not dec.osdw_supported
-    y, _ = nms_graphs.frames(name, 2.0, 4, 1)
-    yd = to_dev(y, dec)
-    bufs = _sentinels(dec, 4)
-    clean = {k: v.clone() for k, v in bufs.items()}
-    msg = rf"\(-5\).*1 <= n-k <= 64 and n <= 128.*\({dec.n},{dec.k}\)"
-    with pytest.raises(_lib.LdpcError, match=msg):
-        dec.osdw_front(yd, out=(bufs["perm"], bufs["parity"], None))
-    with pytest.raises(_lib.LdpcError, match=msg):
-        dec.osdw_search(yd, bufs["perm"], bufs["parity"], 1, out=bufs)
-    with pytest.raises(_lib.LdpcError, match=msg):
-        dec.osdw_decode(yd, 1, perm=bufs["perm"], parity=bufs["parity"], out=bufs)
-    torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    yd = to_dev(nms_graphs.frames(name, 2.0, 4, 1)[0], dec)
+    OF.check_unsupported(FAM, dec, yd, {
+        "front": lambda b: dec.osdw_front(yd, out=(b["perm"], b["parity"], None)),
+        "search": lambda b: dec.osdw_search(yd, b["perm"], b["parity"], 1, out=b),
+        "decode": lambda b: dec.osdw_decode(yd, 1, perm=b["perm"], parity=b["parity"], out=b)})
 
 
 def test_bad_arguments_are_refused_and_the_old_families_keep_their_refusal():
@@ -373,9 +300,8 @@ def test_bad_arguments_are_refused_and_the_old_families_keep_their_refusal():
     with pytest.raises(_lib.LdpcError, match=r"\(-5\).*OSD kernels need an \(n=128, k=64\) code; this one is \(121,80\)"):
         dec.osd_decode(yd, 2)
     torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
-    assert bool((parity64 == -1).all())
+    OF.assert_untouched(bufs, clean)
+    assert OF.A.untouched(parity64)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

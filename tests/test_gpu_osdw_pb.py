@@ -3,72 +3,46 @@ bit-exact against the model of tests/osdx_pb_model.py on (121,80), the synthetic
 the zoo's deg65 (80,74), at the wide shape edges of tests/osd_shapes.py, on the largest frontier (k = 127, order 3) and just above
 the boundaries of the kernel's slot tiers, and against ldpc_osdx_pb_* on the codes both families serve.  The inputs and the
 branches they reach are those tests/test_osdw_pb_host.py asserts on the CPU.  Integers compare equal, floats by their bits."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from short_ldpc_decoding_osd_amd import _lib
-from tests import nms_graphs, osdw_fs_model, osdw_model, osdx_model
+from tests import nms_graphs, osdw_model, osdx_model
+from tests import osd_family as OF
 from tests import osd_shapes as S
 from tests import osdw_pb_model as W
-from tests.gpu_util import pack_np, to_dev, words_np
+from tests.gpu_util import pack_np, to_dev
+from tests.osd_family import assert_pb, assert_same, new_aux, pb_params
 
 pytestmark = pytest.mark.gpu
-_decoders = {}
+FAM = OF.OSDW
 KEYS = ("cw", "metric", "best", "ntep", "aux")
 
 
 def decoder(name):
-    """A context of a named code, or of a shape (k, n): osdw_fs_model.planted_graph for the (67,100) and (80,121) contexts,
+    """A context of a named code, or of a shape (k, n): osd_family.shape_graph for the (67,100) and (80,121) contexts,
     osd_shapes.context_graph for the shape edges (the searches never read G)."""
-    if name not in _decoders:
-        from short_ldpc_decoding_osd_amd import Code
-        from short_ldpc_decoding_osd_amd.runtime import Decoder
-        if isinstance(name, tuple):
-            H = osdw_fs_model.planted_graph(*name)[0] if name in ((67, 100), (80, 121)) else S.context_graph(*name)[0]
-            code = Code(H=H)
-        else:
-            code = nms_graphs.make_code(name) if name in ("wimax_1056", "wide") else osdw_model.make_code(name)
-        _decoders[name] = Decoder(code)
-    return _decoders[name]
+    if isinstance(name, tuple) and name not in ((67, 100), (80, 121)):
+        return OF.decoder(name, S.context_graph)
+    return OF.decoder(name)
 
 
-def new_aux(dec, F):
-    return torch.full((F, 4), -9, dtype=torch.int32, device=dec.device)
+
+def assert_front(perm, parity, front, dec, pick=slice(None)):
+    OF.assert_front(FAM, dec, perm, parity, front, rows=pick)
 
 
-def pb_params(dec, order, snr_db, aux=None, **kw):
-    return dec.osd_params(order, _lib.OSD_PB, snr_db=snr_db, aux=aux, **kw)
+def _sentinels(dec, F):
+    return OF.sentinels(dec, FAM, F, aux=True)
 
 
-def assert_pb(out, aux, ref, sl=slice(None), pick=None, where=""):
-    """Every output bit for bit: cw, metric as uint32, best, ntep and the four aux columns.  ``pick``: the model's frames that
-    the outputs hold, in order (a frame list)."""
-    pick = np.arange(len(ref["best"])) if pick is None else np.asarray(pick)
-    assert np.array_equal(words_np(out["cw"])[sl], ref["cw"][pick][sl]), where
-    assert np.array_equal(out["metric"].cpu().numpy().view(np.uint32)[sl], ref["metric"][pick].view(np.uint32)[sl]), where
-    assert np.array_equal(out["best"].cpu().numpy()[sl], ref["best"][pick][sl]), where
-    assert np.array_equal(out["ntep"].cpu().numpy()[sl], ref["ntep"][pick][sl]), where
-    if aux is not None:
-        assert np.array_equal(aux.cpu().numpy()[sl], ref["aux"][pick][sl]), where
+def _raw_decode(dec, *args, **kw):
+    return OF.raw_decode(dec, FAM, "pb_decode", *args, **kw)
 
 
-def assert_front(perm, parity, front, n, k, pick=slice(None)):
-    perm, parity = perm.cpu().numpy(), words_np(parity)
-    assert parity.shape[1] == 128
-    assert np.array_equal(perm[:, :n], front[0][pick][:, :n])
-    assert np.array_equal(parity[:, :k], front[1][pick][:, :k])
-    assert not perm[:, n:].any() and not parity[:, k:].any()
-
-
-def assert_same(got, want, keys, where=""):
-    for key in keys:
-        a, b = got[key], want[key]
-        if a.dtype == torch.float32:
-            a, b = a.view(torch.int32), b.view(torch.int32)
-        assert torch.equal(a, b), (where, key)
+def _raw_search(dec, *args):
+    return OF.raw_search(dec, FAM, "pb_search", *args)
 
 
 def search_on(dec, c, F, order, snr_db):
@@ -96,7 +70,7 @@ def test_pb_matches_the_model(name, i):
     again = dec.osdw_pb_search(yd, full["perm"], full["parity"], pb_params(dec, order, snr_db, aux3))
     torch.cuda.synchronize()
     assert_pb(out, aux1, ref, where="search")
-    assert_front(full["perm"], full["parity"], front, dec.n, dec.k)
+    assert_front(full["perm"], full["parity"], front, dec)
     assert_pb(full, aux2, ref, where="decode")
     assert_pb(again, aux3, ref, where="search on the decode's front")
 
@@ -179,31 +153,6 @@ def test_both_shapes_equal_the_any_shape_kernel(k, n):
 # ---------------------------------------------------------------------------------------------------------------------
 # 6: frame lists, device-side counts, nullable outputs, counters
 # ---------------------------------------------------------------------------------------------------------------------
-def _sentinels(dec, F):
-    return dict(perm=torch.full((F, 128), 0xEE, dtype=torch.uint8, device=dec.device),
-                parity=torch.full((F, 128), -1, dtype=torch.int64, device=dec.device),
-                cw=torch.full((F, dec.words), -1, dtype=torch.int64, device=dec.device),
-                metric=torch.full((F,), -5.0, dtype=torch.float32, device=dec.device),
-                best=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                ntep=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                aux=new_aux(dec, F))
-
-
-_p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-
-
-def _raw_decode(dec, yd, index, count, F, params, bufs, label=None, counts=None):
-    return dec.L.ldpc_osdw_pb_decode(dec._ctx, _p(yd), _p(index), _p(count), F, C.byref(params) if params is not None else None,
-                                     _p(bufs.get("perm")), _p(bufs.get("parity")), _p(bufs.get("cw")), _p(bufs.get("metric")),
-                                     _p(bufs.get("best")), _p(bufs.get("ntep")), _p(label), _p(counts), dec._stream())
-
-
-def _raw_search(dec, yd, F, params, bufs):
-    return dec.L.ldpc_osdw_pb_search(dec._ctx, _p(yd), None, None, F, _p(bufs.get("perm")), _p(bufs.get("parity")),
-                                     C.byref(params) if params is not None else None, _p(bufs.get("cw")), _p(bufs.get("metric")),
-                                     _p(bufs.get("best")), _p(bufs.get("ntep")), dec._stream())
-
-
 @pytest.fixture(scope="module")
 def listed():
     """array_121_80, the 48 frames of set 0 (order 2, both stop rules): a list of 40 of them with repeats, not ascending."""
@@ -214,72 +163,25 @@ def listed():
     nf = len(idx)
     assert len(set(idx.tolist())) < nf and np.any(np.diff(idx) < 0)
     assert len(set(ref["aux"][idx, 3].tolist())) == 2 and len(set(ref["ntep"][idx].tolist())) > 3
-    return dict(dec=dec, yd=to_dev(y, dec), labels=cw, index=to_dev(idx, dec), count=to_dev(np.array([nf], np.int32), dec), nf=nf,
-                idx=idx, ref=ref, front=front, order=order, snr_db=snr_db)
+    return dict(dec=dec, yd=to_dev(y, dec), labels=cw, label_rows=idx, index=to_dev(idx, dec),
+                count=to_dev(np.array([nf], np.int32), dec), nf=nf, rows=idx, ref=ref, front=front, order=order, snr_db=snr_db,
+                arg=lambda bufs: pb_params(dec, order, snr_db, bufs["aux"]))
 
 
 @pytest.mark.parametrize("which", ["smaller", "equal", "larger"])
 def test_frame_list_and_device_count(listed, which):
-    dec, nf = listed["dec"], listed["nf"]
-    F = {"smaller": nf + 13, "equal": nf, "larger": nf - 9}[which]       # the device count against the capacity F
-    done = min(nf, F)
-    bufs = _sentinels(dec, nf + 13)
-    clean = {k: v.clone() for k, v in bufs.items()}
-    params = pb_params(dec, listed["order"], listed["snr_db"], bufs["aux"])
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], F, params, bufs) == 0
-    torch.cuda.synchronize()
-    pick = np.concatenate([listed["idx"], np.zeros(13, np.int32)])       # (rows beyond `done` are not compared)
-    assert_pb(bufs, bufs["aux"], listed["ref"], slice(0, done), pick)
-    assert_front(bufs["perm"][:done], bufs["parity"][:done], listed["front"], dec.n, dec.k, listed["idx"][:done])
-    for k in bufs:                                                       # nothing at or beyond min(count, F)
-        assert torch.equal(bufs[k][done:], clean[k][done:]), k
+    OF.check_frame_list(FAM, "pb_decode", listed, which)
 
 
 @pytest.mark.parametrize("off", ["none", "metric", "best", "ntep", "aux", "counts", "label", "metric+best+ntep+aux"])
 def test_nullable_outputs_and_counters(listed, off):
-    dec, nf, ref, idx = listed["dec"], listed["nf"], listed["ref"], listed["idx"]
-    label = to_dev(pack_np(listed["labels"]).view(np.int64), dec)
-    bufs = _sentinels(dec, nf)
-    counts = torch.tensor([5, 6, 7], dtype=torch.int64, device=dec.device)
-    gone = off.split("+")
-    for key in gone:
-        if key in bufs:
-            bufs[key] = None
-    params = pb_params(dec, listed["order"], listed["snr_db"], bufs["aux"])
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], nf, params, bufs,
-                       None if off == "label" else label, None if off == "counts" else counts) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(words_np(bufs["cw"]), ref["cw"][idx])
-    if "metric" not in gone:
-        assert np.array_equal(bufs["metric"].cpu().numpy().view(np.uint32), ref["metric"][idx].view(np.uint32))
-    for key in ("best", "ntep", "aux"):
-        if key not in gone:
-            assert np.array_equal(bufs[key].cpu().numpy(), ref[key][idx]), key
-    # the counters, recomputed on the host: teps_total is the sum of the per-frame ntep and moves only with d_ntep
-    wrong = int(np.any(ref["cw"][idx] != pack_np(listed["labels"][idx]), axis=1).sum())
-    assert 0 < wrong < nf
-    want = [5, 6, 7] if off in ("counts", "label") else [5 + nf, 6 + wrong, 7 + (0 if "ntep" in gone else int(ref["ntep"][idx].sum()))]
-    assert counts.cpu().tolist() == want
+    OF.check_nullable(FAM, "pb_decode", listed, off)
 
 
 @pytest.mark.parametrize("mask", range(1, 15))
 def test_every_subset_of_the_nullable_outputs_through_the_search(listed, mask):
     """metric, best, ntep and aux: each of the 14 proper non-empty subsets present, the others NULL (all and none: above)."""
-    dec, ref, front = listed["dec"], listed["ref"], listed["front"]
-    F = 12
-    names = ("metric", "best", "ntep", "aux")
-    bufs = _sentinels(dec, F)
-    bufs["perm"], bufs["parity"] = to_dev(front[0][:F], dec), to_dev(front[1][:F].view(np.int64), dec)
-    for b, key in enumerate(names):
-        if not (mask >> b) & 1:
-            bufs[key] = None
-    assert _raw_search(dec, listed["yd"], F, pb_params(dec, listed["order"], listed["snr_db"], bufs["aux"]), bufs) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(words_np(bufs["cw"]), ref["cw"][:F])
-    for key in names:
-        if bufs[key] is not None:
-            got, want = bufs[key].cpu().numpy(), ref[key][:F]
-            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)) if key == "metric" else np.array_equal(got, want), key
+    OF.check_nullable_subsets(FAM, "pb_search", listed, mask)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -332,20 +234,11 @@ def test_one_wavefront_decodes_several_frames_in_turn(order):
 @pytest.mark.parametrize("name", ["wimax_1056", "wide"])
 def test_unsupported_shapes_are_refused(name):
     dec = decoder(name)
-    assert not dec.osdw_supported and (dec.n > 128 or dec.n - dec.k > 64)
-    y, _ = nms_graphs.frames(name, 2.0, 4, 1)
-    yd = to_dev(y, dec)
-    bufs = _sentinels(dec, 4)
-    clean = {k: v.clone() for k, v in bufs.items()}
-    p = pb_params(dec, 1, 1.0, bufs["aux"])
-    msg = rf"\(-5\).*the high-rate OSD kernels need 1 <= n-k <= 64 and n <= 128; this code is \({dec.n},{dec.k}\)"
-    with pytest.raises(_lib.LdpcError, match=msg):
-        dec.osdw_pb_search(yd, bufs["perm"], bufs["parity"], p, out=bufs)
-    with pytest.raises(_lib.LdpcError, match=msg):
-        dec.osdw_pb_decode(yd, p, perm=bufs["perm"], parity=bufs["parity"], out=bufs)
-    torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    assert dec.n > 128 or dec.n - dec.k > 64
+    yd = to_dev(nms_graphs.frames(name, 2.0, 4, 1)[0], dec)
+    OF.check_unsupported(FAM, dec, yd, {
+        "pb_search": lambda b: dec.osdw_pb_search(yd, b["perm"], b["parity"], pb_params(dec, 1, 1.0, b["aux"]), out=b),
+        "pb_decode": lambda b: dec.osdw_pb_decode(yd, pb_params(dec, 1, 1.0, b["aux"]), perm=b["perm"], parity=b["parity"], out=b)})
 
 
 def test_bad_arguments_are_refused_and_the_any_shape_family_keeps_its_refusal():
@@ -355,31 +248,7 @@ def test_bad_arguments_are_refused_and_the_any_shape_family_keeps_its_refusal():
     bufs = _sentinels(dec, 4)
     clean = {k: v.clone() for k, v in bufs.items()}
     good = pb_params(dec, 2, 1.5, bufs["aux"])
-    bad = [(dec.osd_params(2, _lib.OSD_CONVENTIONAL), r"algo 0 is not LDPC_OSD_PB"),
-           (dec.osd_params(2, _lib.OSD_FS), r"algo 1 is not LDPC_OSD_PB"),
-           (pb_params(dec, 4, 1.5), r"order 4 outside 0\.\.3"),
-           (pb_params(dec, -1, 1.5), r"order -1 outside 0\.\.3"),
-           (pb_params(dec, 2, 1.5, pb_path="replay"), r"flags 0x4 are not served here"),
-           (pb_params(dec, 2, 1.5, table_scan=True), r"flags 0x1 are not served here"),
-           (pb_params(dec, 2, 1.5, y_frames=4), r"y_frames 4 is not served here")]
-    for p, why in bad:
-        with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdw_pb_decode: " + why):
-            dec.osdw_pb_decode(yd, p, perm=bufs["perm"], parity=bufs["parity"], out=bufs)
-        with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdw_pb_search: " + why):
-            dec.osdw_pb_search(yd, bufs["perm"], bufs["parity"], p, out=bufs)
-    for missing in ("cw", "perm", "parity"):
-        assert _raw_decode(dec, yd, None, None, 4, good, {**bufs, missing: None}) == -1
-        assert f"ldpc_osdw_pb_decode: d_{missing} is NULL".encode() in dec.L.ldpc_last_error()
-        assert _raw_search(dec, yd, 4, good, {**bufs, missing: None}) == -1
-        assert f"ldpc_osdw_pb_search: d_{missing} is NULL".encode() in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, None, None, None, 4, good, bufs) == -1 and b"ldpc_osdw_pb_decode: d_y is NULL" in dec.L.ldpc_last_error()
-    assert _raw_search(dec, None, 4, good, bufs) == -1 and b"ldpc_osdw_pb_search: d_y is NULL" in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, yd, None, None, 4, None, bufs) == -1 and b"ldpc_osdw_pb_decode: params is NULL" in dec.L.ldpc_last_error()
-    assert _raw_search(dec, yd, 4, None, bufs) == -1 and b"ldpc_osdw_pb_search: params is NULL" in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, yd, None, None, -1, good, bufs) == -1 and b"ldpc_osdw_pb_decode: bad arguments" in dec.L.ldpc_last_error()
-    assert _raw_search(dec, yd, -1, good, bufs) == -1 and b"ldpc_osdw_pb_search: bad arguments" in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, yd, None, None, 0, good, {}) == 0              # F == 0: LDPC_OK, no launch
-    assert _raw_search(dec, yd, 0, good, {}) == 0
+    OF.check_bad_arguments(FAM, "pb", dec, yd, bufs, lambda order, **kw: pb_params(dec, order, 1.5, **kw), good)
     # the any-shape family still refuses this code, in its own words
     old = {k: v for k, v in bufs.items() if k not in ("perm", "parity")}
     parity64 = bufs["parity"][:, :64].contiguous()
@@ -389,22 +258,13 @@ def test_bad_arguments_are_refused_and_the_any_shape_family_keeps_its_refusal():
     with pytest.raises(_lib.LdpcError, match=osdx):
         dec.osdx_pb_decode(yd, good, perm=bufs["perm"], parity=parity64, out=old)
     torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
-    assert bool((parity64 == -1).all())
+    OF.assert_untouched(bufs, clean)
+    assert OF.A.untouched(parity64)
 
 
 def test_order_is_bounded_by_k():
     """A (6,2) code: weight class 3 does not exist, so order 3 is refused; order 2 visits {1}, {0}, {0, 1} at most."""
-    from oracle import np_oracle
-    from short_ldpc_decoding_osd_amd import Code
-    from short_ldpc_decoding_osd_amd.runtime import Decoder
-    H = np.array([[1, 1, 0, 1, 0, 0], [0, 1, 1, 0, 1, 0], [1, 0, 1, 0, 0, 1], [1, 1, 1, 1, 1, 0]], dtype=np.int64)
-    code = Code(H=H)
-    assert code.k == 2
-    dec = Decoder(code)
-    G = np.asarray(code.G)
-    y, _ = np_oracle.make_frames(G, 0.0, 64, np.random.default_rng(9))
+    dec, G, y = OF.tiny_case()
     yd = to_dev(y, dec)
     bufs = _sentinels(dec, 64)
     clean = {k: v.clone() for k, v in bufs.items()}
@@ -413,8 +273,7 @@ def test_order_is_bounded_by_k():
     with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdw_pb_search: order 3 outside 0\.\.2"):
         dec.osdw_pb_search(yd, bufs["perm"], bufs["parity"], pb_params(dec, 3, 0.0), out=bufs)
     torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    OF.assert_untouched(bufs, clean)
     front = osdw_model.front_oracle(G, y)
     for order in (0, 1, 2):
         ref = W.pb(y, front[0], front[3], order, 0.0)

@@ -1,52 +1,36 @@
 """-m gpu: PB-OSD for short codes of any shape (ldpc_osdx_pb_search / _pb_decode) -- bit-exact against the model of
 tests/osdx_pb_model.py on (96,48), (121,60), the zoo's `short` (40,17) and `thin` (24,11) and CCSDS (128,64), and against the
 specialised PB routes on CCSDS.  The inputs and the branches they reach are those tests/test_osdx_pb_host.py asserts on the CPU."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from short_ldpc_decoding_osd_amd import _lib
 from tests import nms_graphs, osdx_model
+from tests import osd_family as OF
 from tests import osdx_pb_model as M
-from tests.gpu_util import pack_np, to_dev, words_np
+from tests.gpu_util import pack_np, to_dev
+from tests.osd_family import assert_pb, decoder, new_aux, pb_params
 
 pytestmark = pytest.mark.gpu
-_decoders = {}
+FAM = OF.OSDX
 KEYS = ("cw", "metric", "best", "ntep", "aux")
 
 
-def decoder(name):
-    if name not in _decoders:
-        from short_ldpc_decoding_osd_amd.runtime import Decoder
-        _decoders[name] = Decoder(nms_graphs.make_code(name) if name in nms_graphs.NAMES else osdx_model.make_code(name))
-    return _decoders[name]
+def assert_front(perm, parity, front, dec, pick=slice(None)):
+    OF.assert_front(FAM, dec, perm, parity, front, rows=pick)
 
 
-def new_aux(dec, F):
-    return torch.full((F, 4), -9, dtype=torch.int32, device=dec.device)
+def _sentinels(dec, F):
+    return OF.sentinels(dec, FAM, F, aux=True)
 
 
-def pb_params(dec, order, snr_db, aux=None, **kw):
-    return dec.osd_params(order, _lib.OSD_PB, snr_db=snr_db, aux=aux, **kw)
+def _raw_decode(dec, *args, **kw):
+    return OF.raw_decode(dec, FAM, "pb_decode", *args, **kw)
 
 
-def assert_pb(out, aux, ref, sl=slice(None), pick=None, where=""):
-    """Every output bit for bit: cw, metric as uint32, best, ntep and the four aux columns.  ``pick``: the model's frames that
-    the outputs hold, in order (a frame list)."""
-    pick = np.arange(len(ref["best"])) if pick is None else np.asarray(pick)
-    assert np.array_equal(words_np(out["cw"])[sl], ref["cw"][pick][sl]), where
-    assert np.array_equal(out["metric"].cpu().numpy().view(np.uint32)[sl], ref["metric"][pick].view(np.uint32)[sl]), where
-    assert np.array_equal(out["best"].cpu().numpy()[sl], ref["best"][pick][sl]), where
-    assert np.array_equal(out["ntep"].cpu().numpy()[sl], ref["ntep"][pick][sl]), where
-    if aux is not None:
-        assert np.array_equal(aux.cpu().numpy()[sl], ref["aux"][pick][sl]), where
-
-
-def assert_front(perm, parity, front, n, k, pick=slice(None)):
-    assert np.array_equal(perm.cpu().numpy()[:, :n], front[0][pick][:, :n])
-    assert np.array_equal(words_np(parity)[:, :k], front[1][pick][:, :k])
+def _raw_search(dec, *args):
+    return OF.raw_search(dec, FAM, "pb_search", *args)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -61,7 +45,7 @@ def test_pb_matches_the_model(name, i):
     full = dec.osdx_pb_decode(yd, pb_params(dec, order, snr_db, aux1))
     out = dec.osdx_pb_search(yd, to_dev(front[0], dec), to_dev(front[1].view(np.int64), dec), pb_params(dec, order, snr_db, aux2))
     torch.cuda.synchronize()
-    assert_front(full["perm"], full["parity"], front, dec.n, dec.k)
+    assert_front(full["perm"], full["parity"], front, dec)
     assert_pb(full, aux1, ref, where="decode")
     assert_pb(out, aux2, ref, where="search")
 
@@ -106,31 +90,6 @@ def test_equal_magnitudes(name, order, levels):
 # ---------------------------------------------------------------------------------------------------------------------
 # 4, 5: frame lists, device-side counts, nullable outputs, counters
 # ---------------------------------------------------------------------------------------------------------------------
-def _sentinels(dec, F):
-    return dict(perm=torch.full((F, 128), 0xEE, dtype=torch.uint8, device=dec.device),
-                parity=torch.full((F, 64), -1, dtype=torch.int64, device=dec.device),
-                cw=torch.full((F, dec.words), -1, dtype=torch.int64, device=dec.device),
-                metric=torch.full((F,), -5.0, dtype=torch.float32, device=dec.device),
-                best=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                ntep=torch.full((F,), -9, dtype=torch.int32, device=dec.device),
-                aux=new_aux(dec, F))
-
-
-_p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-
-
-def _raw_decode(dec, yd, index, count, F, params, bufs, label=None, counts=None):
-    return dec.L.ldpc_osdx_pb_decode(dec._ctx, _p(yd), _p(index), _p(count), F, C.byref(params) if params is not None else None,
-                                     _p(bufs.get("perm")), _p(bufs.get("parity")), _p(bufs.get("cw")), _p(bufs.get("metric")),
-                                     _p(bufs.get("best")), _p(bufs.get("ntep")), _p(label), _p(counts), dec._stream())
-
-
-def _raw_search(dec, yd, F, params, bufs):
-    return dec.L.ldpc_osdx_pb_search(dec._ctx, _p(yd), None, None, F, _p(bufs.get("perm")), _p(bufs.get("parity")),
-                                     C.byref(params) if params is not None else None, _p(bufs.get("cw")), _p(bufs.get("metric")),
-                                     _p(bufs.get("best")), _p(bufs.get("ntep")), dec._stream())
-
-
 @pytest.fixture(scope="module")
 def listed():
     """ldpc_96_48, the 96 frames of set 1 (order 2, both stop rules): a list of 40 of them with repeats, not ascending."""
@@ -141,53 +100,19 @@ def listed():
     nf = len(idx)
     assert len(set(idx.tolist())) < nf and np.any(np.diff(idx) < 0)
     assert len(set(ref["aux"][idx, 3].tolist())) == 2 and len(set(ref["ntep"][idx].tolist())) > 3
-    return dict(dec=dec, yd=to_dev(y, dec), labels=cw, index=to_dev(idx, dec), count=to_dev(np.array([nf], np.int32), dec), nf=nf,
-                idx=idx, ref=ref, front=front, order=order, snr_db=snr_db)
+    return dict(dec=dec, yd=to_dev(y, dec), labels=cw, label_rows=idx, index=to_dev(idx, dec),
+                count=to_dev(np.array([nf], np.int32), dec), nf=nf, rows=idx, ref=ref, front=front, order=order, snr_db=snr_db,
+                arg=lambda bufs: pb_params(dec, order, snr_db, bufs["aux"]))
 
 
 @pytest.mark.parametrize("which", ["smaller", "equal", "larger"])
 def test_frame_list_and_device_count(listed, which):
-    dec, nf = listed["dec"], listed["nf"]
-    F = {"smaller": nf + 13, "equal": nf, "larger": nf - 9}[which]       # the device count against the capacity F
-    done = min(nf, F)
-    bufs = _sentinels(dec, nf + 13)
-    clean = {k: v.clone() for k, v in bufs.items()}
-    params = pb_params(dec, listed["order"], listed["snr_db"], bufs["aux"])
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], F, params, bufs) == 0
-    torch.cuda.synchronize()
-    pick = np.concatenate([listed["idx"], np.zeros(13, np.int32)])       # (rows beyond `done` are not compared)
-    assert_pb(bufs, bufs["aux"], listed["ref"], slice(0, done), pick)
-    assert_front(bufs["perm"][:done], bufs["parity"][:done], listed["front"], dec.n, dec.k, listed["idx"][:done])
-    for k in bufs:                                                       # nothing at or beyond min(count, F)
-        assert torch.equal(bufs[k][done:], clean[k][done:]), k
+    OF.check_frame_list(FAM, "pb_decode", listed, which)
 
 
 @pytest.mark.parametrize("off", ["metric", "best", "ntep", "aux", "counts", "label"])
 def test_nullable_outputs_and_counters(listed, off):
-    dec, nf, ref, idx = listed["dec"], listed["nf"], listed["ref"], listed["idx"]
-    label = to_dev(pack_np(listed["labels"]).view(np.int64), dec)
-    bufs = _sentinels(dec, nf)
-    counts = torch.tensor([5, 6, 7], dtype=torch.int64, device=dec.device)
-    if off in bufs:
-        bufs[off] = None
-    params = pb_params(dec, listed["order"], listed["snr_db"], bufs["aux"])
-    assert _raw_decode(dec, listed["yd"], listed["index"], listed["count"], nf, params, bufs,
-                       None if off == "label" else label, None if off == "counts" else counts) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(words_np(bufs["cw"]), ref["cw"][idx])
-    if off != "metric":
-        assert np.array_equal(bufs["metric"].cpu().numpy().view(np.uint32), ref["metric"][idx].view(np.uint32))
-    if off != "best":
-        assert np.array_equal(bufs["best"].cpu().numpy(), ref["best"][idx])
-    if off != "ntep":
-        assert np.array_equal(bufs["ntep"].cpu().numpy(), ref["ntep"][idx])
-    if off != "aux":
-        assert np.array_equal(bufs["aux"].cpu().numpy(), ref["aux"][idx])
-    # the counters, recomputed on the host: teps_total is the sum of the per-frame ntep
-    wrong = int(np.any(ref["cw"][idx] != pack_np(listed["labels"][idx]), axis=1).sum())
-    assert 0 < wrong < nf
-    want = [5, 6, 7] if off in ("counts", "label") else [5 + nf, 6 + wrong, 7 + (0 if off == "ntep" else int(ref["ntep"][idx].sum()))]
-    assert counts.cpu().tolist() == want
+    OF.check_nullable(FAM, "pb_decode", listed, off)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -232,19 +157,10 @@ def test_one_wavefront_decodes_several_frames_in_turn():
 @pytest.mark.parametrize("name", ["wimax_1056", "wide"])
 def test_unsupported_shapes_are_refused(name):
     dec = decoder(name)
-    y, _ = nms_graphs.frames(name, 2.0, 4, 1)
-    yd = to_dev(y, dec)
-    bufs = _sentinels(dec, 4)
-    clean = {k: v.clone() for k, v in bufs.items()}
-    p = pb_params(dec, 1, 1.0, bufs["aux"])
-    msg = rf"\(-5\).*1 <= k <= 64 and 1 <= n-k <= 64.*\({dec.n},{dec.k}\)"
-    with pytest.raises(_lib.LdpcError, match=msg):
-        dec.osdx_pb_search(yd, bufs["perm"], bufs["parity"], p, out=bufs)
-    with pytest.raises(_lib.LdpcError, match=msg):
-        dec.osdx_pb_decode(yd, p, perm=bufs["perm"], parity=bufs["parity"], out=bufs)
-    torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    yd = to_dev(nms_graphs.frames(name, 2.0, 4, 1)[0], dec)
+    OF.check_unsupported(FAM, dec, yd, {
+        "pb_search": lambda b: dec.osdx_pb_search(yd, b["perm"], b["parity"], pb_params(dec, 1, 1.0, b["aux"]), out=b),
+        "pb_decode": lambda b: dec.osdx_pb_decode(yd, pb_params(dec, 1, 1.0, b["aux"]), perm=b["perm"], parity=b["parity"], out=b)})
 
 
 def test_bad_arguments_and_shapes():
@@ -254,58 +170,26 @@ def test_bad_arguments_and_shapes():
     bufs = _sentinels(dec, 4)
     clean = {k: v.clone() for k, v in bufs.items()}
     good = pb_params(dec, 2, 1.5, bufs["aux"])
-    bad = [(dec.osd_params(2, _lib.OSD_CONVENTIONAL), r"algo 0 is not LDPC_OSD_PB"),
-           (dec.osd_params(2, _lib.OSD_FS), r"algo 1 is not LDPC_OSD_PB"),
-           (pb_params(dec, 4, 1.5), r"order 4 outside 0\.\.3"),
-           (pb_params(dec, -1, 1.5), r"order -1 outside 0\.\.3"),
-           (pb_params(dec, 2, 1.5, pb_path="replay"), r"flags 0x4 are not served here"),
-           (pb_params(dec, 2, 1.5, table_scan=True), r"flags 0x1 are not served here"),
-           (pb_params(dec, 2, 1.5, y_frames=4), r"y_frames 4 is not served here")]
-    for p, why in bad:
-        with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdx_pb_decode: " + why):
-            dec.osdx_pb_decode(yd, p, perm=bufs["perm"], parity=bufs["parity"], out=bufs)
-        with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdx_pb_search: " + why):
-            dec.osdx_pb_search(yd, bufs["perm"], bufs["parity"], p, out=bufs)
-    for missing in ("cw", "perm", "parity"):
-        assert _raw_decode(dec, yd, None, None, 4, good, {**bufs, missing: None}) == -1
-        assert f"ldpc_osdx_pb_decode: d_{missing} is NULL".encode() in dec.L.ldpc_last_error()
-        assert _raw_search(dec, yd, 4, good, {**bufs, missing: None}) == -1
-        assert f"ldpc_osdx_pb_search: d_{missing} is NULL".encode() in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, None, None, None, 4, good, bufs) == -1 and b"ldpc_osdx_pb_decode: d_y is NULL" in dec.L.ldpc_last_error()
-    assert _raw_search(dec, None, 4, good, bufs) == -1 and b"ldpc_osdx_pb_search: d_y is NULL" in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, yd, None, None, 4, None, bufs) == -1 and b"ldpc_osdx_pb_decode: params is NULL" in dec.L.ldpc_last_error()
-    assert _raw_search(dec, yd, 4, None, bufs) == -1 and b"ldpc_osdx_pb_search: params is NULL" in dec.L.ldpc_last_error()
-    assert _raw_decode(dec, yd, None, None, 0, good, {}) == 0              # F == 0: LDPC_OK, no launch
-    assert _raw_search(dec, yd, 0, good, {}) == 0
+    OF.check_bad_arguments(FAM, "pb", dec, yd, bufs, lambda order, **kw: pb_params(dec, order, 1.5, **kw), good)
     old = r"\(-5\).*OSD kernels need an \(n=128, k=64\) code; this one is \(96,48\)"
     with pytest.raises(_lib.LdpcError, match=old):                         # the (128,64) entry points keep their refusal
         dec.osd_decode(yd, 2, params=good)
     with pytest.raises(_lib.LdpcError, match=old):
         dec.osd_search(yd, bufs["perm"], bufs["parity"], good, out=bufs)
     torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    OF.assert_untouched(bufs, clean)
 
 
 def test_order_is_bounded_by_k():
     """A (6,2) code: weight class 3 does not exist, so order 3 is refused; order 2 visits {1}, {0}, {0, 1} at most."""
-    from oracle import np_oracle
-    from short_ldpc_decoding_osd_amd import Code
-    from short_ldpc_decoding_osd_amd.runtime import Decoder
-    H = np.array([[1, 1, 0, 1, 0, 0], [0, 1, 1, 0, 1, 0], [1, 0, 1, 0, 0, 1], [1, 1, 1, 1, 1, 0]], dtype=np.int64)
-    code = Code(H=H)
-    assert code.k == 2
-    dec = Decoder(code)
-    G = np.asarray(code.G)
-    y, _ = np_oracle.make_frames(G, 0.0, 64, np.random.default_rng(9))
+    dec, G, y = OF.tiny_case()
     yd = to_dev(y, dec)
     bufs = _sentinels(dec, 64)
     clean = {k: v.clone() for k, v in bufs.items()}
     with pytest.raises(_lib.LdpcError, match=r"\(-1\).*ldpc_osdx_pb_decode: order 3 outside 0\.\.2"):
         dec.osdx_pb_decode(yd, pb_params(dec, 3, 0.0), perm=bufs["perm"], parity=bufs["parity"], out=bufs)
     torch.cuda.synchronize()
-    for k in bufs:
-        assert torch.equal(bufs[k], clean[k]), k
+    OF.assert_untouched(bufs, clean)
     front = osdx_model.front_oracle(G, y)
     for order in (0, 1, 2):
         ref = M.pb(y, front[0], front[3], order, 0.0)
@@ -337,5 +221,5 @@ def test_pb_decode_is_graph_capturable():
         ybuf.copy_(to_dev(y, dec))
         graph.replay()
         torch.cuda.synchronize()
-        assert_front(bufs["perm"], bufs["parity"], front, dec.n, dec.k, slice(0, F))
+        assert_front(bufs["perm"], bufs["parity"], front, dec, slice(0, F))
         assert_pb(bufs, bufs["aux"], ref, slice(0, F), np.arange(F))

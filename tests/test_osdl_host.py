@@ -12,6 +12,7 @@ import pytest
 from oracle import np_oracle
 from short_ldpc_decoding_osd_amd import Code, _lib, build
 from tests import osdl_model
+from tests import osd_family as OF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("ldpc_osdl_supported", "ldpc_osdl_front", "ldpc_osdl_search", "ldpc_osdl_decode")
@@ -132,11 +133,11 @@ def test_shapes_of_the_codes():
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", osdl_model.NEW)
 def test_oracle_self_check(name):
-    assert osdl_model.self_check(name, order=1)
+    assert OF.self_check(osdl_model, name, order=1, frames_=2)
 
 
 def test_oracle_self_check_at_order_2_on_wl384():
-    assert osdl_model.self_check("wl384", order=2, frames_=1)
+    assert OF.self_check(osdl_model, "wl384", order=2, frames_=1)
 
 
 @pytest.mark.parametrize("name", osdl_model.SERVED)

@@ -10,6 +10,7 @@ import pytest
 from oracle import np_oracle
 from short_ldpc_decoding_osd_amd import Code, _lib
 from tests import osdw_model
+from tests import osd_family as OF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("ldpc_osdw_supported", "ldpc_osdw_front", "ldpc_osdw_search", "ldpc_osdw_decode")
@@ -59,4 +60,4 @@ def test_array_121_80_code():
 @pytest.mark.parametrize("name", osdw_model.WIDE)
 def test_oracle_self_check_on_wide_codes(name):
     assert osdw_model.graph(name)[1].shape[0] > 64
-    assert osdw_model.self_check(name)
+    assert OF.self_check(osdw_model, name)

@@ -10,6 +10,7 @@ import pytest
 from oracle import np_oracle
 from short_ldpc_decoding_osd_amd import _lib
 from tests import osdx_model
+from tests import osd_family as OF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("ldpc_osdx_supported", "ldpc_osdx_front", "ldpc_osdx_search", "ldpc_osdx_decode")
@@ -41,4 +42,4 @@ def test_tep_table_of_other_k(k, order):
 
 @pytest.mark.parametrize("name", ["ldpc_96_48", "array_121_60", "short", "thin"])
 def test_scan_oracle_self_check(name):
-    assert osdx_model.self_check(name)
+    assert OF.self_check(osdx_model, name)
