@@ -817,6 +817,50 @@ int ldpc_hosdw_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_m
                        float *d_truth, uint8_t *d_success, uint64_t *d_cw, float *d_metric, int32_t *d_best,
                        int32_t *d_teps_evaluated, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * H-form OSD primitives for longer and low-rate codes: ldpc_hosdl_*, a superset of ldpc_hosdw_* (for an H of at most 192
+ * rows) as ldpc_osdl_* is one of ldpc_osdw_*.
+ *
+ * Shapes served: n <= 384; H as given has R rows, 1 <= R <= 192, of rank m = n - k, 1 <= m <= 192; 1 <= k <= 192.  That is
+ * every code ldpc_hosdx_* and ldpc_hosdw_* serve, plus (384,192), (256,192), (193,1), ...  Everything else is refused with
+ * LDPC_E_UNSUPPORTED before any launch, and the message names the entry point, R, n-k and (n,k); ldpc_hosdl_supported tells
+ * beforehand.
+ *
+ * The contract is that of ldpc_hosdw_front / _search / _sliding above, parameter for parameter (validation order, the
+ * messages that name the NULL pointer, F == 0, every nullable output on its own, the limit of 1024 TEP blocks, win 1..15,
+ * group, soft_margin compared in double, the classifier's float order, the row deletion of the elimination; a call
+ * allocates nothing and synchronises nothing, so it can be captured in a graph), with these layouts, S = ceil(n/64),
+ * Wm = ceil(m/64), Wk = ceil(k/64):
+ *   d_lri, d_uidx       [F][64 S] u16 : entries >= n are written as 0 and ignored as inputs.
+ *   d_M            [F][64 Wm][Wk] u64 : entry [r][w] holds bits j = 64w .. 64w+63 of row r of updated_M; rows >= m and
+ *                                       bits >= k are written as 0 and ignored as inputs.
+ *   d_cw, d_label_bits      [F][S] u64, original bit order.
+ *   d_teps            [ntep][4] u8    : positions < k <= 192, as ldpc_hosdl_pattern_teps writes them for bounds within 0..k;
+ *                                       a position >= k is the caller's error: that frame's result is unspecified, but nothing
+ *                                       is read or written outside the buffers.
+ * The metric is the any-shape rule over the n updated positions, LRB first, in bytes of eight: each byte is summed ascending
+ * from 0.0f and the ceil(n/8) byte sums are added ascending.
+ * ldpc_hosdl_pattern_teps is ldpc_hosd_pattern_teps with bounds within 0..192.
+ * ldpc_ctx_create uploads the H columns as three-word R-bit columns ([384][3] u64) when the code is in the family.
+ * Wherever ldpc_hosdw_* serves the code every output of every ldpc_hosdl_* call equals that of the ldpc_hosdw_* call of the
+ * same name, bit for bit, once the layouts are converted.
+ * ------------------------------------------------------------------------------------- */
+int ldpc_hosdl_supported(const ldpc_ctx *ctx); /* 1: the entry points below serve this code; 0: they refuse it */
+int64_t ldpc_hosdl_pattern_teps(int32_t nseg, const int32_t *bounds, const int32_t *pattern, uint8_t *teps);
+int ldpc_hosdl_front(ldpc_ctx *ctx, const float *d_order_llr, int64_t F, uint16_t *d_lri, uint16_t *d_uidx,
+                     uint64_t *d_M, int32_t *d_nswaps, void *stream);
+int ldpc_hosdl_search(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F,
+                      const uint16_t *d_lri, const uint16_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps,
+                      const int32_t *d_block_off, int32_t nblk, const uint64_t *d_label_bits, float *d_block_min,
+                      int32_t *d_block_arg, float *d_truth, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                      void *stream);
+int ldpc_hosdl_sliding(ldpc_ctx *ctx, const float *d_order_llr, const float *d_metric_llr, int64_t F, const uint16_t *d_lri,
+                       const uint16_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps, const int32_t *d_block_off,
+                       int32_t nblk, int32_t win, double soft_margin, const float *fcn_weights, int32_t n_weights,
+                       int32_t group, const uint64_t *d_label_bits, int32_t *d_deep_limit, float *d_global_min,
+                       float *d_truth, uint8_t *d_success, uint64_t *d_cw, float *d_metric, int32_t *d_best,
+                       int32_t *d_teps_evaluated, void *stream);
+
 /* The bit-wise CNN of the DL-OSD stage, conv_bitwise.call (nn_net.py:174-197): for every frame f and
  * bit v, the sequence rows[f][0..L-1][v] (the retest layout of ldpc_nms_traj_rows, row 0 = channel
  * values, L = T+1 >= 7; preprocessing_inputs :198-211 without the transpose) through

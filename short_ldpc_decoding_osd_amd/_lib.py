@@ -30,7 +30,9 @@ SYMBOLS = (
     "ldpc_osdl_fs_search", "ldpc_osdl_fs_decode", "ldpc_osdl_tep_eval", "ldpc_osdl_pb_search", "ldpc_osdl_pb_decode",
     "ldpc_hosd_pattern_teps", "ldpc_hosd_front", "ldpc_hosd_search", "ldpc_hosd_sliding",
     "ldpc_hosdx_supported", "ldpc_hosdx_front", "ldpc_hosdx_search", "ldpc_hosdx_sliding",
-    "ldpc_hosdw_supported", "ldpc_hosdw_front", "ldpc_hosdw_search", "ldpc_hosdw_sliding", "ldpc_dia_cnn", "ldpc_dia_cnn_grad",
+    "ldpc_hosdw_supported", "ldpc_hosdw_front", "ldpc_hosdw_search", "ldpc_hosdw_sliding",
+    "ldpc_hosdl_supported", "ldpc_hosdl_pattern_teps", "ldpc_hosdl_front", "ldpc_hosdl_search", "ldpc_hosdl_sliding",
+    "ldpc_dia_cnn", "ldpc_dia_cnn_grad",
     "ldpc_fcn_windows", "ldpc_fcn_grad",
     "ldpc_pipeline_run", "ldpc_pipeline_timing",
 )
@@ -142,6 +144,8 @@ def load():
                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ldpc_hosdx_supported": (C.c_int, [vp]),
         "ldpc_hosdw_supported": (C.c_int, [vp]),
+        "ldpc_hosdl_supported": (C.c_int, [vp]),
+        "ldpc_hosdl_pattern_teps": (i64, [i32, pi32, pi32, C.POINTER(C.c_uint8)]),
         "ldpc_dia_cnn": (C.c_int, [vp, vp, i64, i32, C.POINTER(f32), i32, vp, vp]),
         "ldpc_dia_cnn_grad": (C.c_int, [vp, vp, vp, i64, i32, C.POINTER(f32), i32, vp, vp, vp, vp]),
         "ldpc_fcn_windows": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
@@ -149,8 +153,8 @@ def load():
         "ldpc_pipeline_run": (C.c_int, [vp, C.POINTER(Pipeline), vp]),
         "ldpc_pipeline_timing": (C.c_int, [vp, i32, C.POINTER(f32)]),
     }
-    for op in ("front", "search", "sliding"):     # the any-shape and the wide H-form family: the signatures of ldpc_hosd_*
-        sig[f"ldpc_hosdx_{op}"] = sig[f"ldpc_hosdw_{op}"] = sig[f"ldpc_hosd_{op}"]
+    for op in ("front", "search", "sliding"):     # the any-shape, the wide and the long H-form family: the signatures of ldpc_hosd_*
+        sig[f"ldpc_hosdx_{op}"] = sig[f"ldpc_hosdw_{op}"] = sig[f"ldpc_hosdl_{op}"] = sig[f"ldpc_hosd_{op}"]
     # the entry points that the any-shape and the high-rate family both have, under the same signatures
     for fam in ("osdx", "osdw"):
         sig.update({

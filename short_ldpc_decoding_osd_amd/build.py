@@ -22,7 +22,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libldpcosd.so")
 SOURCES = ["ldpc_host.cpp", "ldpc_api.hip", "ldpc_nms.hip", "ldpc_nms_train.hip", "ldpc_util.hip", "ldpc_osd.hip",
            "ldpc_osd_pb.hip", "ldpc_osdx.hip", "ldpc_osdw.hip", "ldpc_osdl.hip", "ldpc_osdl_fs.hip", "ldpc_osdl_pb.hip",
-           "ldpc_hosd.hip", "ldpc_dia.hip", "ldpc_gen.hip"]
+           "ldpc_hosd.hip", "ldpc_hosdl.hip", "ldpc_dia.hip", "ldpc_gen.hip"]
 # -ffp-contract=off: the float order of the NMS / OSD metric is part of the contract (no FMA fusion)
 # -fno-slp-vectorize: packed v_pk_add_f32 is no faster than two v_add_f32 on gfx950 and blocks the
 #                      fusion of the DPP rotations into their consumers

@@ -10,6 +10,8 @@ int osd_ctx_init(ldpc_ctx *ctx);      // ldpc_osd.hip
 void osd_ctx_release(ldpc_ctx *ctx);  // ldpc_osd.hip
 int hosd_ctx_init(ldpc_ctx *ctx);     // ldpc_hosd.hip
 void hosd_ctx_release(ldpc_ctx *ctx); // ldpc_hosd.hip
+int hosdl_ctx_init(ldpc_ctx *ctx);    // ldpc_hosdl.hip
+void hosdl_ctx_release(ldpc_ctx *ctx); // ldpc_hosdl.hip
 }  // namespace ldpc
 
 template <typename T>
@@ -90,6 +92,7 @@ int ldpc_ctx_create(const ldpc_code *code, int32_t device, ldpc_ctx **out)
         if (rc) break;
         if ((rc = osd_ctx_init(ctx))) break;
         if ((rc = hosd_ctx_init(ctx))) break;
+        if ((rc = hosdl_ctx_init(ctx))) break;
         if ((rc = gen_ctx_init(ctx))) break;
     } while (0);
     (void)hipSetDevice(prev);
@@ -103,6 +106,7 @@ void ldpc_ctx_destroy(ldpc_ctx *ctx)
     if (!ctx) return;
     osd_ctx_release(ctx);
     hosd_ctx_release(ctx);
+    hosdl_ctx_release(ctx);
     gen_ctx_release(ctx);
     (void)hipFree(ctx->osd_tables.d_Gcols); (void)hipFree(ctx->osd_tables.d_tep); (void)hipFree(ctx->osd_tables.d_tep_fs);
     (void)hipFree(ctx->osd_tables.d_pb);

@@ -383,14 +383,15 @@ int pack_osdl_tables(const ldpc_code &c, const OsdwTables &base, OsdlTables &t, 
 
 // osd.error_pattern_gen (DL_OSD_Testing_serial/ordered_statistics_decoding.py:81-98): product over
 // the segments (leftmost slowest) of the lexicographic combinations inside each segment
-int64_t hosd_pattern_teps(int nseg, const int32_t *bounds, const int32_t *pattern, uint8_t *teps)
+// (max_bound: 128 for ldpc_hosd_pattern_teps, 192 for ldpc_hosdl_pattern_teps)
+int64_t hosd_pattern_teps(int nseg, const int32_t *bounds, const int32_t *pattern, uint8_t *teps, int max_bound)
 {
     if (nseg < 1 || nseg > 64 || !bounds || !pattern) return fail(LDPC_E_ARG, "hosd_pattern_teps: bad arguments");
     int weight = 0;
     int64_t total = 1;
     for (int s = 0; s < nseg; ++s) {
         const int len = bounds[s + 1] - bounds[s];
-        if (bounds[s] < 0 || bounds[s + 1] > 128 || len < 0 || pattern[s] < 0)
+        if (bounds[s] < 0 || bounds[s + 1] > max_bound || len < 0 || pattern[s] < 0)
             return fail(LDPC_E_ARG, "hosd_pattern_teps: segment %d = [%d, %d), %d flips", s, bounds[s], bounds[s + 1], pattern[s]);
         weight += pattern[s];
         total *= pattern[s] > len ? 0 : binom(len, pattern[s]);   // combinations() of too many items is empty
@@ -556,6 +557,11 @@ int64_t ldpc_osdl_pb_table(int32_t n, int32_t k, double *table)
 int64_t ldpc_hosd_pattern_teps(int32_t nseg, const int32_t *bounds, const int32_t *pattern, uint8_t *teps)
 {
     return hosd_pattern_teps(nseg, bounds, pattern, teps);
+}
+
+int64_t ldpc_hosdl_pattern_teps(int32_t nseg, const int32_t *bounds, const int32_t *pattern, uint8_t *teps)
+{
+    return hosd_pattern_teps(nseg, bounds, pattern, teps, 192);
 }
 
 }  // extern "C"

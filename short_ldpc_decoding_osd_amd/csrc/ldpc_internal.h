@@ -89,13 +89,15 @@ struct ldpc_ctx {
     uint64_t *d_Hcols = nullptr;   // [128] column v < n of H as an m-bit word (bit r = H[r][v]), zero beyond n; with hosdx_ok only
     uint32_t *d_gen_G = nullptr;   // [ceil(k/32)][4][ceil(n/4)] G's columns packed over k, transposed for ldpc_gen_frames (ldpc_gen.hip)
     uint64_t *d_HcolsW = nullptr;  // [128][2] column v < n of H as given, rows 0..63 / 64..127, zero beyond n; with hosdw_ok only
-    bool dpp_ror_up = true;        // probed: row_ror:n moves data towards higher lanes
+    uint64_t *d_HcolsL = nullptr;  // [384][3] column v < n of H as given, rows 0..63 / 64..127 / 128..191, zero beyond n; with hosdl_ok only
+    bool dpp_ror_up = true;       // probed: row_ror:n moves data towards higher lanes
     int dpp_wave_rol_dir = 0;      // probed: wave_rol:1 -- +1 lane j receives lane j-1, -1 lane j+1, 0 unusable
     bool osd_ok = false;
     bool hosd_ok = false;          // (128,64): ldpc_hosd_*
     bool hosdx_ok = false;         // 1 <= k <= 64, an H of exactly n - k <= 64 rows: ldpc_hosdx_*
     bool hosdw_ok = false;         // n <= 128, an H of 1 <= R <= 127 rows and rank 1 <= n - k <= 64: ldpc_hosdw_*
-    void *osd_state = nullptr;     // ldpc::OsdState ((128,64) constants; per-stream workspaces behind its mutex)
+    bool hosdl_ok = false;         // n <= 384, an H of 1 <= R <= 192 rows, rank 1 <= n - k <= 192, 1 <= k <= 192: ldpc_hosdl_*
+    void *osd_state = nullptr;    // ldpc::OsdState ((128,64) constants; per-stream workspaces behind its mutex)
     hipEvent_t *timing = nullptr;  // [LDPC_TIMING_SLOTS][6] events of ldpc_pipeline_run, created with the context
     unsigned timing_recorded[LDPC_TIMING_SLOTS] = {};   // bit i: event i of the slot was recorded by the last run that used it
 };
@@ -108,7 +110,7 @@ int build_code(ldpc_code &c);  // fills G, graph tables, qc flag from c.H/m/n
 int64_t tep_table(int k, int order, uint8_t *supports, int64_t *boundaries);
 int64_t tep_table_fs(int k, int w, uint8_t *supports);
 // (pack_osd_tables, which packs both into the context's tables: ldpc_osd_tables.h)
-int64_t hosd_pattern_teps(int nseg, const int32_t *bounds, const int32_t *pattern, uint8_t *teps);
+int64_t hosd_pattern_teps(int nseg, const int32_t *bounds, const int32_t *pattern, uint8_t *teps, int max_bound = 128);
 
 // launchers (one per .hip file)
 int launch_nms(ldpc_ctx *ctx, const float *d_llr, int64_t B, int T, const float *alpha, float w_in, float w_out,

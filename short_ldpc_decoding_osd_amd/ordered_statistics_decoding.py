@@ -5,7 +5,8 @@ of nn_testing.py:65-82,120-148 and globalmap.py:57-76 that feed it.
 Everything per frame and per TEP -- ascending reliability sort, elimination of the permuted H, MRB
 bookkeeping, re-encoding and weighted-distance scan of every TEP block -- runs in the HIP kernels behind
 ``ldpc_hosd_front`` / ``ldpc_hosd_search`` ((128,64)), ``ldpc_hosdx_*`` (any shape with k, n-k <= 64 and an H of
-n-k rows) or ``ldpc_hosdw_*`` (k up to 127, or an H with redundant rows; ``runtime.Decoder.hosd_stage`` picks).
+n-k rows), ``ldpc_hosdw_*`` (k up to 127, or an H with redundant rows) or ``ldpc_hosdl_*`` (n up to 384, k and n-k up to 192;
+``runtime.Decoder.hosd_stage`` picks).
 ``sliding_osd`` evaluates ALL blocks of the decoding
 path on the device (the reference evaluates them lazily) and then replays the reference's window
 loop on the block minima with a host callable ``fcn``, so decisions, window counts and complexity
@@ -146,9 +147,11 @@ class osd:   # noqa: N801  (name kept from the reference)
         nseg = len(range_list)
         b = (C.c_int32 * (nseg + 1))(*bounds)
         p = (C.c_int32 * nseg)(*[int(v) for v in direction])
-        n = _lib.check(L.ldpc_hosd_pattern_teps(nseg, b, p, None), "ldpc_hosd_pattern_teps")
+        name = "ldpc_hosdl_pattern_teps" if self.k > 128 else "ldpc_hosd_pattern_teps"     # (bounds within 0..192 / 0..128)
+        enum = getattr(L, name)
+        n = _lib.check(enum(nseg, b, p, None), name)
         t = np.zeros((max(n, 1), 4), dtype=np.uint8)
-        _lib.check(L.ldpc_hosd_pattern_teps(nseg, b, p, t.ctypes.data_as(C.POINTER(C.c_uint8))), "ldpc_hosd_pattern_teps")
+        _lib.check(enum(nseg, b, p, t.ctypes.data_as(C.POINTER(C.c_uint8))), name)
         E = np.zeros((n, self.k), dtype=int)
         for q in range(3):
             sel = t[:n, 3] > q
@@ -165,11 +168,19 @@ class osd:   # noqa: N801  (name kept from the reference)
         metric = np.where(hard, -mag, mag).astype(np.float32)       # (a zero weight costs nothing under either sign)
         order = np.ones(self.n_dims, dtype=np.float32)
         order[self.m:] = np.where(np.asarray(initial_mrb).astype(bool), -1.0, 1.0)
-        ident = torch.arange(128, dtype=torch.uint8, device=dec.device)[None].contiguous()
-        wide = dec.hosd_stage_family() == "hosdw"                   # [F,128]: bits j < 64 at entry r, bits j >= 64 at 64 + r
-        Mpad = np.zeros((64, 128 if wide else 64), dtype=np.uint8)  # rows r < m, bits j < k of the [F,64] u64 layout
-        Mpad[:self.m, :self.k] = np.asarray(M_matrix, dtype=np.uint8)
-        Mrows = np.packbits(Mpad, axis=1, bitorder="little").view(np.int64).reshape(64, -1).T.reshape(1, -1)
+        fam = dec.hosd_stage_family()
+        if fam == "hosdl":                                          # [F,64 S] int16 indices, M [F,64 Wm,Wk]: word w of row r at [r][w]
+            itail, mtail = dec._hosdl_layout()
+            ident = torch.arange(itail[0], dtype=torch.int16, device=dec.device)[None].contiguous()
+            Mpad = np.zeros((mtail[0], 64 * mtail[1]), dtype=np.uint8)
+            Mpad[:self.m, :self.k] = np.asarray(M_matrix, dtype=np.uint8)
+            Mrows = np.packbits(Mpad, axis=1, bitorder="little").view(np.int64).reshape((1,) + mtail)
+        else:
+            ident = torch.arange(128, dtype=torch.uint8, device=dec.device)[None].contiguous()
+            wide = fam == "hosdw"                                       # [F,128]: bits j < 64 at entry r, bits j >= 64 at 64 + r
+            Mpad = np.zeros((64, 128 if wide else 64), dtype=np.uint8)  # rows r < m, bits j < k of the [F,64] u64 layout
+            Mpad[:self.m, :self.k] = np.asarray(M_matrix, dtype=np.uint8)
+            Mrows = np.packbits(Mpad, axis=1, bitorder="little").view(np.int64).reshape(64, -1).T.reshape(1, -1)
         teps = torch.from_numpy(_teps_from_matrix(error_pattern_matrix)).to(dec.device)
         off = torch.tensor([0, teps.shape[0]], dtype=torch.int32, device=dec.device)
         out = dec.hosd_stage("search")(torch.from_numpy(order[None]).to(dec.device), torch.from_numpy(metric[None]).to(dec.device),

@@ -564,13 +564,22 @@ class Decoder:
         rank n-k <= 64; k up to 127)."""
         return bool(self.L.ldpc_hosdw_supported(self._ctx))
 
+    @property
+    def hosdl_supported(self):
+        """Whether the long H-form calls serve this code (``ldpc_hosdl_*``: n <= 384, an H of at most 192 rows as given, of
+        rank n-k <= 192; k up to 192)."""
+        return bool(self.L.ldpc_hosdl_supported(self._ctx))
+
     def hosd_stage_family(self):
         """The H-form family the DL-OSD stage runs on this code: ``"hosd"`` on (128,64), ``"hosdx"`` where
-        ``hosdx_supported``, else ``"hosdw"`` (high rate, or an H with redundant rows; it refuses what it does not serve).
+        ``hosdx_supported``, ``"hosdw"`` where ``hosdw_supported`` (high rate, or an H with redundant rows), ``"hosdl"``
+        where only ``hosdl_supported`` holds (longer and low-rate codes), else ``"hosdw"``, which refuses the code.
         ``hosd_stage(op)`` is that family's ``front`` / ``search`` / ``sliding`` method."""
         if (self.n, self.k, self.m) == (128, 64, 64):
             return "hosd"
-        return "hosdx" if self.hosdx_supported else "hosdw"
+        if self.hosdx_supported:
+            return "hosdx"
+        return "hosdl" if not self.hosdw_supported and self.hosdl_supported else "hosdw"
 
     def hosd_stage(self, op):
         return getattr(self, f"{self.hosd_stage_family()}_{op}")
@@ -580,14 +589,34 @@ class Decoder:
         (which refuse what they do not serve)."""
         return "hosd" if (self.n, self.k, self.m) == (128, 64, 64) else "hosdx"
 
-    def _hosd_M(self, fam, M):
-        """The wide family reads 128 words of M per frame: front-end results of another family are refused here."""
+    def _hosdl_layout(self):
+        """The long family's buffers: (index tail [64 S] int16, M tail [64 ceil(m/64), Wk] int64), m the rank of H."""
+        m = self.n - self.k
+        return (64 * self.words,), (64 * ((m + 63) // 64), (self.k + 63) // 64)
+
+    def _hosd_M(self, fam, M, lri=None, uidx=None):
+        """The wide family reads 128 words of M per frame, the long one its own layouts: front-end results of another family
+        are refused here."""
         if fam == "hosdw" and tuple(M.shape[1:]) != (128,):
             raise ValueError(f"front: hosdw takes M [*, 128] (hosdw_front's), got {tuple(M.shape)}")
+        if fam == "hosdl":
+            itail, mtail = self._hosdl_layout()
+            if tuple(M.shape[1:]) != mtail or M.dtype != torch.int64:
+                raise ValueError(f"front: hosdl takes M [*, {mtail[0]}, {mtail[1]}] int64 (hosdl_front's), got {tuple(M.shape)}")
+            for name, t in (("lri", lri), ("uidx", uidx)):
+                if t.dtype != torch.int16 or tuple(t.shape[1:]) != itail:
+                    raise ValueError(f"front: hosdl takes {name} [*, {itail[0]}] int16 (hosdl_front's), got {tuple(t.shape)} {t.dtype}")
 
     def _hosd_front(self, fam, order_llr):
         self._chk(order_llr, torch.float32, (self.n,), "order_llr")
         F = order_llr.shape[0]
+        if fam == "hosdl":
+            itail, mtail = self._hosdl_layout()
+            lri, uidx = self.empty((F,) + itail, torch.int16), self.empty((F,) + itail, torch.int16)
+            M = self.empty((F,) + mtail, torch.int64)
+            ns = self.empty((F,), torch.int32)
+            self._osd_call(fam, "front", _ptr(order_llr), F, _ptr(lri), _ptr(uidx), _ptr(M), _ptr(ns))
+            return lri, uidx, M, ns
         lri = self.empty((F, 128), torch.uint8)
         uidx = self.empty((F, 128), torch.uint8)
         M = self.empty((F, 128 if fam == "hosdw" else 64), torch.int64)
@@ -597,7 +626,7 @@ class Decoder:
 
     def _hosd_search(self, fam, order_llr, metric_llr, front, teps, block_off, label_bits, want_arg, want_best):
         lri, uidx, M, F, nblk = self._hosd_args(order_llr, metric_llr, front, teps, block_off)
-        self._hosd_M(fam, M)
+        self._hosd_M(fam, M, lri, uidx)
         out = dict(block_min=self.empty((F, nblk), torch.float32),
                    block_arg=self.empty((F, nblk), torch.int32) if want_arg else None,
                    truth=self.empty((F,), torch.float32) if label_bits is not None else None,
@@ -612,7 +641,7 @@ class Decoder:
     def _hosd_sliding(self, fam, order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights, label_bits,
                       group, want_best):
         lri, uidx, M, F, nblk = self._hosd_args(order_llr, metric_llr, front, teps, block_off)
-        self._hosd_M(fam, M)
+        self._hosd_M(fam, M, lri, uidx)
         w = np.ascontiguousarray(np.asarray(fcn_weights, dtype=np.float32).reshape(-1))
         lab = label_bits is not None
         out = dict(deep_limit=self.empty((F,), torch.int32), global_min=self.empty((F,), torch.float32),
@@ -677,6 +706,22 @@ class Decoder:
                       group=0, want_best=True):
         """``hosd_sliding`` through the wide kernels on ``hosdw_front``'s results."""
         return self._hosd_sliding("hosdw", order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights,
+                                  label_bits, group, want_best)
+
+    def hosdl_front(self, order_llr):
+        """``hosd_front`` through the long kernels (``ldpc_hosdl_front``): lri / uidx are [F, 64 S] int16 (S = ceil(n/64),
+        entries at or beyond n are 0), M is [F, 64 ceil(m/64), ceil(k/64)] int64 (m = n-k: entry [r][w] bits j = 64w..64w+63
+        of row r of updated_M, 0 elsewhere); the elimination deletes redundant rows of H as the reference does."""
+        return self._hosd_front("hosdl", order_llr)
+
+    def hosdl_search(self, order_llr, metric_llr, front, teps, block_off, label_bits=None, want_arg=True, want_best=True):
+        """``hosd_search`` through the long kernels on ``hosdl_front``'s results (TEP positions < k <= 192)."""
+        return self._hosd_search("hosdl", order_llr, metric_llr, front, teps, block_off, label_bits, want_arg, want_best)
+
+    def hosdl_sliding(self, order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights, label_bits=None,
+                      group=0, want_best=True):
+        """``hosd_sliding`` through the long kernels on ``hosdl_front``'s results."""
+        return self._hosd_sliding("hosdl", order_llr, metric_llr, front, teps, block_off, win, soft_margin, fcn_weights,
                                   label_bits, group, want_best)
 
     def dia_cnn(self, rows, weights, out=None):
