@@ -420,7 +420,7 @@ int ldpc_osd_counts(ldpc_ctx *ctx, const uint64_t *d_cw, const uint64_t *d_label
  *   one given TEP per frame     one_tep_compare, FS_OSD/fs_testing.py:51-64
  *   PB-OSD                      pb_osd, PB_OSD/pb_testing.py:100-149, orders 0..min(3, k)
  * Everything else of this header that says OSD -- the PB tuning (ldpc_pb_tuning), the elimination primitive, the H-form
- * primitives, the one-call pipeline, the LDPC_OSD_F_* flags (the LDPC_OSD_F_PB_* routes among them) and y_frames of
+ * primitives, ldpc_pipeline_run (the one call on these shapes is ldpc_family_pipeline_run, at the end of this header), the LDPC_OSD_F_* flags (the LDPC_OSD_F_PB_* routes among them) and y_frames of
  * ldpc_osd_params, d_aux outside the PB pair, and the entry points above themselves -- stays with (n = 128, k = 64) and
  * keeps answering LDPC_E_UNSUPPORTED on other shapes.
  * Same rules as above for d_index / d_count (min(*d_count, F) frames, read on the device; nothing at or beyond that
@@ -496,7 +496,7 @@ int ldpc_osdx_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
  * the conventional search (orders 0..3), FS-OSD and PB-OSD (orders 0..min(3, k)) and one-TEP evaluation.  Codes with k <= 64
  * are served as well; there d_perm, d_cw, d_metric, d_best, d_ntep, d_hd, d_nswaps and d_aux equal those of the ldpc_osdx_*
  * call of the same name bit for bit, and the first 64 rows of d_parity equal the d_parity of those calls.  The staged PB
- * routes, ldpc_pb_tuning, the LDPC_OSD_F_PB_* flags and the one-call pipeline stay with (128,64); codes with n-k > 64 or
+ * routes, ldpc_pb_tuning, the LDPC_OSD_F_PB_* flags and ldpc_pipeline_run stay with (128,64) (ldpc_family_pipeline_run serves this family); codes with n-k > 64 or
  * n > 128 are refused by every OSD entry point.
  * The contract is that of ldpc_osdx_front / _search / _decode -- d_index / d_count, ties of the sort, the pivot rule, the
  * TEP table of this code's k (first minimum), the float order of the metric, the nullable outputs, d_label_bits with
@@ -564,8 +564,8 @@ int ldpc_osdw_pb_decode(ldpc_ctx *ctx, const float *d_y, const int32_t *d_index,
  * OSD for longer and low-rate codes, i.e. every code with n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192: the reference's
  * wimax-like (384,192) code and the codes with n <= 128 and n-k > 64, which the two families above refuse.  Served: the
  * front end, the conventional search (orders 0..3), FS-OSD and PB-OSD (orders 0..min(3, k)) and one-TEP evaluation.  The
- * H-form primitives, the staged PB routes, ldpc_pb_tuning, the LDPC_OSD_F_PB_* flags and the one-call pipeline
- * are not served for these shapes; codes with n > 384, k > 192 or n-k > 192 -- wimax (1056,880) among them -- are refused
+ * H-form primitives, the staged PB routes, ldpc_pb_tuning, the LDPC_OSD_F_PB_* flags and ldpc_pipeline_run
+ * are not served for these shapes (ldpc_family_pipeline_run is); codes with n > 384, k > 192 or n-k > 192 -- wimax (1056,880) among them -- are refused
  * by every OSD entry point.
  * The contract is that of ldpc_osdx_front / _search / _decode -- d_index / d_count read on the device and nothing written at
  * or beyond frame min(*d_count, F), ties of the sort to the lower index, the reference's pivot and exchange rule, the TEP
@@ -993,6 +993,78 @@ int ldpc_pipeline_run(ldpc_ctx *ctx, const ldpc_pipeline *p, void *stream);
 /* ms[3] = {NMS, OSD front end, OSD search} of the run that used `slot` (call after the stream is idle);
  * when d_perm/d_parity were NULL the OSD ran through ldpc_osd_decode: ms[1] = 0, ms[2] = whole OSD stage */
 int ldpc_pipeline_timing(ldpc_ctx *ctx, int32_t slot, float *ms);
+
+/* ---------------------------------------------------------------------------------------
+ * The decoder's final output: the OSD codewords back among the NMS decisions, and the bit errors before and after.
+ * For every j < min(*d_count, F) (read on the device), with f = d_index[j]:
+ *   d_hard    [*][W] u64, W = ceil(n/64), nullable: d_hard[f] = d_cw[j], all W words, in place; no other row is touched
+ *   d_counts  [4] i64 += {frames merged, frames with d_cw[j] != label[f], bit errors of d_cw[j] against label[f],
+ *             bit errors of the OLD d_hard[f] against label[f]} -- with d_label_bits ([*][W] u64, addressed through
+ *             d_index) and d_counts as a pair, or neither (the rule of the family decode calls); the fourth stays 0
+ *             when d_hard is NULL
+ * Every code a context exists for is served (no OSD family is needed).  The old word is read before it is replaced, by
+ * the same thread; the entries of d_index are trusted and distinct, as everywhere in this header.  End-to-end bit
+ * errors of a batch: nms bit_err - before + after; end-to-end frame errors: undetected + frames wrong.
+ * One launch with work proportional to the failures; no workspace, nothing synchronises (graph-capturable).
+ * F == 0 is LDPC_OK without a launch, and so is d_hard NULL with no counters; d_cw, d_index or d_count NULL with
+ * F > 0 is LDPC_E_ARG naming the pointer.                                                                         */
+int ldpc_osd_merge(ldpc_ctx *ctx, const uint64_t *d_cw /*[F][W]*/, const int32_t *d_index, const int32_t *d_count,
+                   int64_t F, uint64_t *d_hard, const uint64_t *d_label_bits, int64_t *d_counts, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The one-call pipeline on the three G-form OSD families, i.e. for every code the ldpc_osdx_*, ldpc_osdw_* or
+ * ldpc_osdl_* entry points serve (up to (384,192)); ldpc_pipeline_run above stays with (n = 128, k = 64).
+ * The results of this sequence on one stream, with no host round trip, no allocation and no synchronisation:
+ *   ldpc_nms_decode
+ *   ldpc_eval_counts + ldpc_compact     (one launch when d_label_bits and d_nms_counts are given)
+ *   ldpc_osd{x,w,l}_decode, _fs_decode or _pb_decode by osd.algo, on d_llr as ldpc_pipeline_run does, with
+ *                                       d_label_bits and d_osd_counts riding in the scan
+ *   ldpc_osd_merge into d_hard          (with `merge`), d_final_counts its counters
+ * The members ldpc_pipeline has keep their meaning, and the nullable ones switch their stage off, each on its own.
+ *   family        LDPC_OSD_FAMILY_AUTO: ldpc_osdx_* where it serves the code, else ldpc_osdw_*, else ldpc_osdl_*; or one
+ *                 family by name.  A forced family that refuses the code, or AUTO on a code none serves (then with the
+ *                 sentence of ldpc_osdl_*), is LDPC_E_UNSUPPORTED with "; this code is (n,k)".
+ *   d_perm, d_parity   in the layouts of the chosen family's _front; REQUIRED with the OSD stage on: the caller's scratch
+ *                 and output, as in the family decode calls (no library workspace).
+ *   osd_capacity  the frames that d_perm, d_parity, d_cw, d_metric, d_best, d_ntep and osd.d_aux hold; 0 = B.  The OSD
+ *                 stage and the merge run on min(*d_count, osd_capacity) frames and write nothing at or beyond that
+ *                 frame; *d_count stays the number of syndrome failures, so frames were left out exactly when
+ *                 d_osd_counts[0] < d_nms_counts[4].
+ *   osd           order, algo and the FS / PB members as the family's entry points read them; flags and y_frames must be
+ *                 0 and d_aux NULL outside LDPC_OSD_PB (LDPC_E_ARG naming the offender).
+ * Everything is checked before the first launch.  With osd_enable = 0 every code a context exists for is served and
+ * every member from `osd` on is ignored (NMS and its counters alone).  With B = 0 and the OSD stage on, *d_count is
+ * zeroed.  timing_slot and ldpc_pipeline_timing serve both pipelines: ms = {NMS, front end, search}.
+ * ------------------------------------------------------------------------------------- */
+#define LDPC_OSD_FAMILY_AUTO 0   /* osdx where it serves the code, else osdw, else osdl */
+#define LDPC_OSD_FAMILY_X 1
+#define LDPC_OSD_FAMILY_W 2
+#define LDPC_OSD_FAMILY_L 3
+typedef struct ldpc_family_pipeline {
+    const float *d_llr;            /* [B][n]                                               */
+    int64_t B;
+    int32_t T, nms_kernel;
+    const float *alpha;            /* host [T]                                             */
+    float w_in, w_out;
+    float *d_soft;                 /* [B][n] nullable                                      */
+    uint64_t *d_hard;              /* [B][ceil(n/64)]                                      */
+    uint8_t *d_fail;               /* [B]                                                  */
+    const uint64_t *d_label_bits;  /* [B][ceil(n/64)] nullable: no counters                */
+    int64_t *d_nms_counts;         /* [5] accumulated, nullable                            */
+    int32_t osd_enable, timing_slot;
+    ldpc_osd_params osd;
+    int32_t family, merge;         /* LDPC_OSD_FAMILY_*; merge != 0: ldpc_osd_merge into d_hard */
+    int32_t *d_index, *d_count;    /* [B], [1]                                             */
+    void *d_perm;                  /* [C][...] the family's perm rows, C = osd_capacity    */
+    uint64_t *d_parity;            /* [C][...] the family's parity rows                    */
+    int64_t osd_capacity;          /* C; 0 = B                                             */
+    uint64_t *d_cw;                /* [C][ceil(n/64)]                                      */
+    float *d_metric;               /* [C] nullable                                         */
+    int32_t *d_best, *d_ntep;      /* [C] nullable, each on its own                        */
+    int64_t *d_osd_counts;         /* [3] accumulated, nullable (as the family decode calls) */
+    int64_t *d_final_counts;       /* [4] accumulated, nullable (as ldpc_osd_merge)        */
+} ldpc_family_pipeline;
+int ldpc_family_pipeline_run(ldpc_ctx *ctx, const ldpc_family_pipeline *p, void *stream);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,9 @@ front-end results: every frame evaluates the TEP that flips MRB positions 0 and 
 --oracle N times the C oracle's front end (oracle/c_oracle.osd_front, one core) on the first N failures and prints its frames/s.
 --gen hip draws the frames with the library's counter-based generator (Decoder.gen_frames: frames 0 .. --frames - 1 of the set
 --seed, one launch) instead of the torch ops; the JSON line says which.
+--pipeline makes the same run through ONE call as well (pipeline.FamilyPipeline, ldpc_family_pipeline_run: NMS, counters,
+compaction, the family's OSD and ldpc_osd_merge) and asserts that its outputs and counters equal those of the four calls above;
+it prints the bit error rate before and after the OSD codewords are merged into the NMS decisions.
 One JSON line at the end."""
 import argparse
 import json
@@ -93,6 +96,36 @@ def timed(fn, calls, repeats, warmup):
     return out
 
 
+def pipeline_check(dec, args, y, labels, res, nms_counts, index, nf, out, osd_counts, aux):
+    """--pipeline: NMS, counters, compaction, OSD and the merge through ldpc_family_pipeline_run, against the four calls of
+    this script: every output of the listed frames and the counters, exactly; then the merged decisions and the bit error
+    rates the merge's counters give."""
+    from short_ldpc_decoding_osd_amd.pipeline import FamilyPipeline
+    from short_ldpc_decoding_osd_amd.sharding import combine_fer
+    kw = dict(fs_beta=args.beta, fs_tau_e=args.tau_e, fs_tau_psc=args.tau_psc) if args.osd == "fs" else {}
+    pipe = FamilyPipeline(dec, y.shape[0], args.T, args.alpha, osd_order=args.order, snr_db=args.snr,
+                          osd_algo={"conv": _lib.OSD_CONVENTIONAL, "fs": _lib.OSD_FS, "pb": _lib.OSD_PB}[args.osd], **kw).bind(y, labels)
+    pipe.run()
+    torch.cuda.synchronize()
+
+    def same(a, b):
+        return torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b)
+    assert int(pipe.count.item()) == nf and same(pipe.index[:nf], index[:nf]), "failure list"
+    assert same(pipe.soft, res["soft"]) and same(pipe.fail, res["fail"]), "NMS outputs"
+    for key in ("perm", "parity", "cw", "metric", "best", "ntep"):
+        assert same(getattr(pipe, key)[:nf], out[key][:nf]), key
+    assert aux is None or same(pipe.aux[:nf], aux[:nf]), "aux"
+    c = pipe.counters().cpu().tolist()
+    assert c[:5] == nms_counts.cpu().tolist() and c[5:8] == osd_counts.cpu().tolist(), "counters"
+    merged = res["hard"].clone()
+    merged[index[:nf].long()] = out["cw"][:nf]
+    assert same(pipe.hard, merged), "merged decisions"
+    assert c[8] == nf and c[9] == c[6]
+    rates = combine_fer(c, n=dec.n)
+    print(f"  --pipeline: one call (family {pipe.family}) gives the outputs and counters of the four calls; "
+          f"BER {rates['ber_nms']:.3e} after NMS, {rates['ber_end_to_end']:.3e} after the merge", flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--alist", default=None, help="alist file of the code (default: the packaged CCSDS (128,64) code)")
@@ -112,6 +145,8 @@ def main(argv=None):
     ap.add_argument("--tau-e", type=float, default=None, help="FS-OSD: the stop threshold on the Hamming distance")
     ap.add_argument("--tau-psc", type=float, default=30.0, help="FS-OSD: tau_psc (FS_OSD/globalmap.py:50)")
     ap.add_argument("--oracle", type=int, default=0, help="time the C oracle's front end on this many of the failures (one core)")
+    ap.add_argument("--pipeline", action="store_true",
+                    help="the same run through ONE call as well (pipeline.FamilyPipeline); its outputs must equal those of the four calls")
     args = ap.parse_args(argv)
     fs, pb = args.osd == "fs", args.osd == "pb"
     if fs and args.tau_e is None:
@@ -149,6 +184,8 @@ def main(argv=None):
     else:
         out = dec.osdx_decode(y, args.order, index=idx, count=count, label_bits=labels, counts=counts)
     torch.cuda.synchronize()
+    if args.pipeline:
+        pipeline_check(dec, args, y, labels, res, nms_counts, index, nf, out, counts, aux if pb else None)
     nc = nms_counts.cpu().tolist()
     oc = counts.cpu().tolist()
     # a frame is wrong after the stage if NMS left an undetected error (zero syndrome: never listed) or the OSD missed it

@@ -18,6 +18,13 @@ prints `fer_vs_cpu` beside the GPU figures: +-5 % judged when both sides hold >=
 `--gen hip` draws the frames with the library's counter-based generator (`Decoder.gen_frames`, one launch per batch) instead
 of the torch ops: the seed belongs to the SNR point and every batch starts at its first GLOBAL frame number, so a point
 decodes the same frames for every world size, `--batch` and `--streams`; the JSON line says `"gen": "hip"`.
+`--alist FILE` sweeps another code, any that a G-form OSD family serves (ldpc_osdx_*, ldpc_osdw_*, ldpc_osdl_*: up to
+(384,192)), through `pipeline.FamilyPipeline` with every other option unchanged; the JSON line then names the family and adds
+the bit error rates before and after the OSD codewords are merged into the NMS decisions (`ber_nms`, `ber_end_to_end`).
+`--cpu-check` there: the CPU port's NMS serves every shape, its OSD batch calls serve (128,64) only, so the conventional OSD of
+another shape goes through the NumPy port frame by frame (a smaller sample in the same time) and FS / PB are not judged.
+
+    python scripts/snr_sweep.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --osd conv --order 2 --cpu-check
 """
 import argparse
 import json
@@ -32,7 +39,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from short_ldpc_decoding_osd_amd import Code, _lib  # noqa: E402
-from short_ldpc_decoding_osd_amd.pipeline import BatchPipeline  # noqa: E402
+from short_ldpc_decoding_osd_amd.pipeline import BatchPipeline, FamilyPipeline  # noqa: E402
 from short_ldpc_decoding_osd_amd.runtime import Decoder  # noqa: E402
 from short_ldpc_decoding_osd_amd.sharding import combine_fer, end_to_end_errors, rank_seed, shard_range, sweep_point  # noqa: E402
 from short_ldpc_decoding_osd_amd.weights import softplus32  # noqa: E402
@@ -48,6 +55,21 @@ def frames_on_device(dec, B, snr_db, gen):
     return y, dec.pack_bits(cw.to(torch.uint8))
 
 
+def cpu_counts_any_shape(G, H, y, cw, alpha, order, iters, teps):
+    """bench.cpu_counts for a code that is not (128,64), conventional OSD: NMS and the counters by the C port, which serve every
+    shape, then the NumPy port of the front end and the order-p scan on every syndrome failure.  Same int64[5]."""
+    from oracle import c_oracle, np_oracle
+    soft = c_oracle.nms(H, y, iters, alpha)
+    _, fail, cnt = c_oracle.evaluate(H, soft, cw)
+    wrong = int(cnt["synd_fail"])
+    if order is not None:
+        wrong = 0
+        for f in np.flatnonzero(fail):
+            yp, labp, Gp, _, _ = np_oracle.swapped_info(y[f], cw[f], G)
+            wrong += not np_oracle.convention_osd(yp, labp, Gp, order, teps)["correct"]
+    return np.array([y.shape[0], cnt["frame_err"], cnt["undetected"], cnt["synd_fail"], wrong], dtype=np.int64)
+
+
 def cpu_check(code, alpha, args, snr, gpu_errors, gpu_frames):
     """The same SNR point through the CPU port on a bounded sample (all host cores of this rank's share): FER of both
     sides and the +-5 % judgement of BASELINE.json's north_star (>= 1600 frame errors on both sides, else not judged)."""
@@ -56,16 +78,26 @@ def cpu_check(code, alpha, args, snr, gpu_errors, gpu_frames):
     import bench
     from oracle import np_oracle
     algo = ALGOS[args.osd]
+    if args.alist and (code.G.shape != (64, 128)):
+        if args.order is not None and algo != _lib.OSD_CONVENTIONAL:
+            return {"judged": False, "within_5_percent": "not judged",
+                    "reason": "the CPU port's FS-OSD and PB-OSD serve (128,64) only; --osd conv is checked on every shape"}
+        teps = np_oracle.tep_matrix(code.G.shape[0], args.order) if args.order is not None else None
+
+        def counts(G, H, y, cw, alpha, order, algo, snr, iters):
+            return cpu_counts_any_shape(G, H, y, cw, alpha, order, iters, teps)
+    else:
+        counts = bench.cpu_counts
     rng = np.random.default_rng(20241020 + int(round(snr * 100)))
     cores = bench.host_cores()
     probe = 200
     y, cw = np_oracle.make_frames(code.G, snr, probe, rng)
     t0 = time.perf_counter()
-    bench.cpu_counts(code.G, code.H, y, cw, alpha, args.order, algo, snr, args.iters)
+    counts(code.G, code.H, y, cw, alpha, args.order, algo, snr, args.iters)
     per = int(max(100, min(200000, probe / (time.perf_counter() - t0) * args.cpu_seconds)))
     y, cw = np_oracle.make_frames(code.G, snr, per * cores, rng)
     with concurrent.futures.ThreadPoolExecutor(max_workers=cores) as ex:
-        c = sum(ex.map(lambda i: bench.cpu_counts(code.G, code.H, y[i * per:(i + 1) * per], cw[i * per:(i + 1) * per], alpha,
+        c = sum(ex.map(lambda i: counts(code.G, code.H, y[i * per:(i + 1) * per], cw[i * per:(i + 1) * per], alpha,
                                                   args.order, algo, snr, args.iters), range(cores)))
     ec = int(c[4] + c[2]) if args.order is not None else int(c[1])
     fg, fc = gpu_errors / max(gpu_frames, 1), ec / max(int(c[0]), 1)
@@ -102,6 +134,8 @@ def main():
                     help="decode streams: consecutive batches rotate over them, so the tail of one batch's search kernels "
                          "(a few long searches on an emptying chip) overlaps the next batches' decoding (scratch is per stream; "
                          "PB-3 sweep, 2 / 3 / 4 streams: 1.99 / 2.04 / 2.00 x 10^7 frames/s at 1.0 dB, 7.5 / 7.8 / 7.5 x 10^7 at 2.0 dB)")
+    ap.add_argument("--alist", default=None,
+                    help="alist file of another code: the sweep runs on pipeline.FamilyPipeline (any code a G-form OSD family serves)")
     args = ap.parse_args()
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
@@ -115,7 +149,14 @@ def main():
         _, v = weights.parse_values_txt(args.values)
         stored = float([x for k, x in v.items() if "check" in k][0][0])
     alpha = float(softplus32(stored))                           # softplus, ms_test.py:207-208
-    dec = Decoder(Code(), local)
+    dec = Decoder(Code(args.alist) if args.alist else Code(), local)
+
+    def make_pipe(B, snr):
+        """The pipeline object of a batch size: the (128,64) one, or with --alist the one on the OSD families."""
+        if args.alist:
+            return FamilyPipeline(dec, B, args.iters, alpha, osd_order=args.order, osd_algo=ALGOS[args.osd], snr_db=snr, want_soft=False)
+        return BatchPipeline(dec, B, args.iters, alpha, osd_order=args.order, osd_algo=ALGOS[args.osd], snr_db=snr,
+                             want_soft=False, keep_front=False)
     lo, hi = shard_range(args.frames, rank, world)
     mine = hi - lo
     gen = torch.Generator(device=dec.device).manual_seed(rank_seed(20241020, rank))
@@ -129,10 +170,9 @@ def main():
     torch.cuda.synchronize()
     for st in dstreams:
         with torch.cuda.stream(st):
-            if args.order is not None:
+            if args.order is not None and not args.alist:      # (the families have no library workspace)
                 dec.osd_reserve_stream(min(args.batch, max(mine, 1)), dec.osd_params(args.order, ALGOS[args.osd], snr_db=float(args.snr[0])))
-            warm = BatchPipeline(dec, yw.shape[0], args.iters, alpha, osd_order=args.order, osd_algo=ALGOS[args.osd], snr_db=float(args.snr[0]),
-                                 want_soft=False, keep_front=False).bind(yw, lw)
+            warm = make_pipe(yw.shape[0], float(args.snr[0])).bind(yw, lw)
             warm.run()
     torch.cuda.synchronize()
     with_osd = args.order is not None
@@ -175,8 +215,7 @@ def main():
                 key = ((taken[0] - 1) % len(dstreams), B)
                 pipe = pool.get(key)
                 if pipe is None:
-                    pipe = pool[key] = BatchPipeline(dec, B, args.iters, alpha, osd_order=args.order, osd_algo=ALGOS[args.osd], snr_db=snr,
-                                                     want_soft=False, keep_front=False)
+                    pipe = pool[key] = make_pipe(B, snr)
                 else:
                     pipe.reset_counters()
                 pipe.bind(y, lab).run()
@@ -188,12 +227,15 @@ def main():
                 main_stream.wait_event(done_ev)      # (the counters are summed on the main stream; the NEXT batch is already enqueued on the other)
             return c
 
-        total, ran = sweep_point(decode_batch, mine, args.batch, max_batches, args.stop_errors, with_osd, device=dec.device)   # the point's exchange step(s)
+        total, ran = sweep_point(decode_batch, mine, args.batch, max_batches, args.stop_errors, with_osd, device=dec.device,
+                                 width=12 if args.alist else 8)   # the point's exchange step(s)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         if rank == 0:
             c = total.cpu().numpy()
-            out = combine_fer(c)
+            out = combine_fer(c, n=dec.n)
+            if args.alist:
+                out.update(code=[dec.n, dec.k], family=warm.family)
             out.update(snr_db=snr, osd=args.osd, order=args.order, alpha=alpha, n_gpus=world, macro_batches=ran, gen=args.gen,
                        stop_errors=args.stop_errors, **{"frames_per_s_resident_inputs" if args.resident else "frames_per_s_incl_generation": int(c[0]) / dt},
                        stop_rule=("end-to-end errors >= %d, checked per macro-batch of %d x %d frames" % (args.stop_errors, args.batch, world)) if args.stop_errors else "none: every frame decoded")

@@ -35,6 +35,7 @@ SYMBOLS = (
     "ldpc_dia_cnn", "ldpc_dia_cnn_grad",
     "ldpc_fcn_windows", "ldpc_fcn_grad",
     "ldpc_pipeline_run", "ldpc_pipeline_timing",
+    "ldpc_osd_merge", "ldpc_family_pipeline_run",
 )
 
 NMS_AUTO, NMS_GENERIC, NMS_QC16 = 0, 1, 2
@@ -75,6 +76,25 @@ class Pipeline(C.Structure):
                 ("d_index", C.c_void_p), ("d_count", C.c_void_p), ("d_perm", C.c_void_p), ("d_parity", C.c_void_p),
                 ("d_cw", C.c_void_p), ("d_metric", C.c_void_p), ("d_best", C.c_void_p), ("d_ntep", C.c_void_p),
                 ("d_osd_counts", C.c_void_p)]
+
+
+# ldpc_family_pipeline.family (LDPC_OSD_FAMILY_*) and the prefix of each family's entry points
+OSD_FAMILY_AUTO, OSD_FAMILY_X, OSD_FAMILY_W, OSD_FAMILY_L = 0, 1, 2, 3
+OSD_FAMILIES = {"osdx": OSD_FAMILY_X, "osdw": OSD_FAMILY_W, "osdl": OSD_FAMILY_L}
+
+
+class FamilyPipeline(C.Structure):
+    """ldpc_family_pipeline of include/ldpc_osd.h (device pointers as integers)."""
+    _fields_ = [("d_llr", C.c_void_p), ("B", C.c_int64), ("T", C.c_int32), ("nms_kernel", C.c_int32),
+                ("alpha", C.POINTER(C.c_float)), ("w_in", C.c_float), ("w_out", C.c_float),
+                ("d_soft", C.c_void_p), ("d_hard", C.c_void_p), ("d_fail", C.c_void_p),
+                ("d_label_bits", C.c_void_p), ("d_nms_counts", C.c_void_p),
+                ("osd_enable", C.c_int32), ("timing_slot", C.c_int32), ("osd", OsdParams),
+                ("family", C.c_int32), ("merge", C.c_int32),
+                ("d_index", C.c_void_p), ("d_count", C.c_void_p), ("d_perm", C.c_void_p), ("d_parity", C.c_void_p),
+                ("osd_capacity", C.c_int64),
+                ("d_cw", C.c_void_p), ("d_metric", C.c_void_p), ("d_best", C.c_void_p), ("d_ntep", C.c_void_p),
+                ("d_osd_counts", C.c_void_p), ("d_final_counts", C.c_void_p)]
 
 
 TIMING_SLOTS = 64
@@ -152,6 +172,8 @@ def load():
         "ldpc_fcn_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, C.POINTER(f32), i32, f32, vp, vp, vp, vp, vp, vp]),
         "ldpc_pipeline_run": (C.c_int, [vp, C.POINTER(Pipeline), vp]),
         "ldpc_pipeline_timing": (C.c_int, [vp, i32, C.POINTER(f32)]),
+        "ldpc_osd_merge": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp]),
+        "ldpc_family_pipeline_run": (C.c_int, [vp, C.POINTER(FamilyPipeline), vp]),
     }
     for op in ("front", "search", "sliding"):     # the any-shape, the wide and the long H-form family: the signatures of ldpc_hosd_*
         sig[f"ldpc_hosdx_{op}"] = sig[f"ldpc_hosdw_{op}"] = sig[f"ldpc_hosdl_{op}"] = sig[f"ldpc_hosd_{op}"]

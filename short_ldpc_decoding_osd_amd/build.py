@@ -6,7 +6,9 @@
 --asan: CPU sanitizer build ("race detection / sanitizers"): the library's HOST code (csrc/ldpc_host.cpp: alist
 parser, G construction, GF(2) elimination, TEP tables, CRC-32C) and the C oracle under -fsanitize=address,undefined, as
 libldpcosd_asan.so / oracle/_build/libldpc_oracle_asan.so; --run then runs the host-side test files against them
-(LDPC_OSD_LIB / LDPC_ORACLE_LIB select the libraries, the sanitizer runtime is preloaded).  Device code is never
+(LDPC_OSD_LIB / LDPC_ORACLE_LIB select the libraries, the sanitizer runtime is preloaded).  The host-side validation of
+ldpc_osd_merge and ldpc_family_pipeline_run (csrc/ldpc_family_check.h) is part of that library, and --run first runs a
+stand-alone program on it (csrc/ldpc_sanitizer_main.cpp: contexts made by hand, no device, nothing preloaded).  Device code is never
 sanitized: GPU AddressSanitizer runs are not available on this pool.
 """
 from __future__ import annotations
@@ -75,6 +77,7 @@ def build(force=False, verbose=False):
 
 
 ASAN_LIB = os.path.join(HERE, "libldpcosd_asan.so")
+ASAN_MAIN = os.path.join(OBJ, "ldpc_sanitizer_main")
 ASAN_TESTS = ["tests/test_cabi.py", "tests/test_hosd_host.py", "tests/test_tfrecord.py", "tests/test_weights.py", "tests/test_oracle_golden.py"]
 
 
@@ -83,13 +86,17 @@ def build_asan(verbose=False):
     root = os.path.dirname(HERE)
     san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]
     cmd = ["g++", "-std=c++17", "-fPIC", "-shared", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"] + san + [
-        os.path.join(CSRC, "ldpc_host.cpp"), os.path.join(CSRC, "ldpc_sanitizer_stubs.cpp"), "-o", ASAN_LIB,
-        "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-lamdhip64"]
+        os.path.join(CSRC, "ldpc_host.cpp"), os.path.join(CSRC, "ldpc_sanitizer_stubs.cpp"), os.path.join(CSRC, "ldpc_sanitizer_checks.cpp"),
+        "-o", ASAN_LIB, "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-lamdhip64"]
+    # the stand-alone driver of the validation in ldpc_sanitizer_checks.cpp, linked against that library
+    os.makedirs(OBJ, exist_ok=True)
+    cmd_main = ["g++", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"] + san + [
+        os.path.join(CSRC, "ldpc_sanitizer_main.cpp"), ASAN_LIB, "-o", ASAN_MAIN, "-Wl,-rpath," + HERE, "-Wl,-rpath,/opt/rocm/lib"]
     oracle_so = os.path.join(root, "oracle", "_build", "libldpc_oracle_asan.so")
     os.makedirs(os.path.dirname(oracle_so), exist_ok=True)
     cmd2 = ["gcc", "-std=c11", "-fPIC", "-shared", "-Wall", "-Wextra", "-ffp-contract=off", "-fno-fast-math"] + san + [
         os.path.join(root, "oracle", "ldpc_oracle.c"), "-o", oracle_so, "-lm"]
-    for c in (cmd, cmd2):
+    for c in (cmd, cmd2, cmd_main):
         if verbose:
             print(" ".join(c), flush=True)
         p = subprocess.run(c, capture_output=True, text=True)
@@ -103,6 +110,10 @@ def run_asan_tests(extra=()):
     """pytest over the host-side test files with the sanitized libraries; returns the subprocess result."""
     lib, oracle_so, rt = build_asan()
     root = os.path.dirname(HERE)
+    alone = subprocess.run([ASAN_MAIN], cwd=root, capture_output=True, text=True,
+                           env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
+    if alone.returncode:
+        return alone
     env = dict(os.environ, LDPC_OSD_LIB=lib, LDPC_ORACLE_LIB=oracle_so, LD_PRELOAD=rt,
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     return subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider"] + ASAN_TESTS + list(extra),

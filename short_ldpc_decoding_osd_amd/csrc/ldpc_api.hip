@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include "ldpc_internal.h"
+#include "ldpc_osd_family.h"   // FamilyStage: the OSD stage of ldpc_family_pipeline_run
 
 using namespace ldpc;
 
@@ -234,6 +235,48 @@ int ldpc_pipeline_run(ldpc_ctx *ctx, const ldpc_pipeline *p, void *stream)
     if (counts && !counted &&
         (rc = ldpc_osd_counts(ctx, p->d_cw, p->d_label_bits, p->d_index, p->d_count, p->d_ntep, p->B, p->d_osd_counts, stream))) return rc;
 #undef LDPC_EV
+    return LDPC_OK;
+}
+
+int ldpc_family_pipeline_run(ldpc_ctx *ctx, const ldpc_family_pipeline *p, void *stream)
+{
+    static const char who[] = "ldpc_family_pipeline_run";
+    int family, rc;
+    int64_t F;                          // the frames the OSD buffers hold
+    if ((rc = family_pipeline_check(ctx, p, who, &family, &F))) return rc;
+    const FamilyStage *fam = family == LDPC_OSD_FAMILY_X ? &osdx_stage() : family == LDPC_OSD_FAMILY_W ? &osdw_stage() : &osdl_stage();
+    hipStream_t s = (hipStream_t)stream;
+    hipEvent_t *ev = nullptr;
+    unsigned *rec = nullptr;            // which of the slot's events THIS run records (ldpc_pipeline_timing reads only those)
+    if (p->timing_slot >= 0) {
+        ev = ctx->timing + p->timing_slot * 6;
+        rec = &ctx->timing_recorded[p->timing_slot];
+        *rec = 0;
+    }
+#define LDPC_EV(i) do { if (ev) { LDPC_HIP(hipEventRecord(ev[i], s)); *rec |= 1u << (i); } } while (0)
+    LDPC_EV(0);
+    if ((rc = ldpc_nms_decode(ctx, p->d_llr, p->B, p->T, p->alpha, p->w_in, p->w_out, p->d_soft, nullptr, p->d_hard,
+                              p->d_fail, p->nms_kernel, stream))) return rc;
+    LDPC_EV(1);
+    const bool want_eval = p->d_label_bits && p->d_nms_counts;
+    if (!p->osd_enable) {
+        if (want_eval && (rc = ldpc_eval_counts(ctx, p->d_hard, p->d_label_bits, p->d_fail, p->B, p->d_nms_counts, stream))) return rc;
+        return LDPC_OK;
+    }
+    if (want_eval && p->B > 0) {   // counters and the compaction's counting pass share one kernel
+        if ((rc = eval_and_compact(ctx, p->d_hard, p->d_label_bits, p->d_fail, p->B, p->d_nms_counts, p->d_index,
+                                   p->d_count, s))) return rc;
+    } else if ((rc = ldpc_compact(ctx, p->d_fail, p->B, p->d_index, p->d_count, stream))) return rc;
+    if (F == 0) return LDPC_OK;
+    const OsdFrames fr{p->d_llr, p->d_index, p->d_count, F};
+    LDPC_EV(2);
+    if ((rc = fam->front(ctx, fr, p->d_perm, p->d_parity, s))) return rc;
+    LDPC_EV(3);
+    if ((rc = fam->scan(ctx, fr, p->d_perm, p->d_parity, &p->osd, {p->d_cw, p->d_metric, p->d_best, p->d_ntep},
+                        osd_counting(p->d_label_bits, p->d_osd_counts), s))) return rc;
+    LDPC_EV(4);
+#undef LDPC_EV
+    if (p->merge) return ldpc_osd_merge(ctx, p->d_cw, p->d_index, p->d_count, F, p->d_hard, p->d_label_bits, p->d_final_counts, stream);
     return LDPC_OK;
 }
 

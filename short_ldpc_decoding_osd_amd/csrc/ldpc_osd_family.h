@@ -16,6 +16,7 @@
 #pragma once
 
 #include "ldpc_internal.h"
+#include "ldpc_family_check.h"   // check_order, check_scan_algo: the validation without a kernel in sight
 
 namespace ldpc {
 
@@ -48,11 +49,6 @@ int family_open(const ldpc_ctx *ctx, int64_t F, const char *who)
 {
     if (!ctx || F < 0) return fail(LDPC_E_ARG, "%s: bad arguments", who);
     return FAM::tables(ctx).k ? LDPC_OK : fail(LDPC_E_UNSUPPORTED, "%s; this code is (%d,%d)", FAM::needs, ctx->code.n, ctx->code.k);
-}
-
-inline int check_order(int order, const char *who)
-{
-    return order < 0 || order > 3 ? fail(LDPC_E_ARG, "%s: order %d outside 0..3", who, order) : LDPC_OK;
 }
 
 // the pointers every scan with F > 0 needs
@@ -145,14 +141,7 @@ constexpr OsdScan<typename FAM::perm_t> fs_scan{LDPC_OSD_FS, "LDPC_OSD_FS", fals
 template <class PERM>
 int check_scan_params(int k, const ldpc_osd_params *p, const OsdScan<PERM> &scan, const char *who)
 {
-    if (!p) return fail(LDPC_E_ARG, "%s: params is NULL", who);
-    if (p->algo != scan.algo) return fail(LDPC_E_ARG, "%s: algo %d is not %s", who, p->algo, scan.algo_name);
-    const int omax = k < 3 ? k : 3;
-    if (p->order < 0 || p->order > omax) return fail(LDPC_E_ARG, "%s: order %d outside 0..%d", who, p->order, omax);
-    if (p->flags != 0) return fail(LDPC_E_ARG, "%s: flags 0x%x are not served here (flags must be 0)", who, (unsigned)p->flags);
-    if (p->d_aux && !scan.aux_allowed) return fail(LDPC_E_ARG, "%s: d_aux is not served here (it must be NULL)", who);
-    if (p->y_frames != 0) return fail(LDPC_E_ARG, "%s: y_frames %lld is not served here (it must be 0)", who, (long long)p->y_frames);
-    return LDPC_OK;
+    return check_scan_algo(k, p, scan.algo, scan.algo_name, scan.aux_allowed, who);
 }
 
 template <class FAM>
@@ -192,5 +181,39 @@ int family_tep_eval(ldpc_ctx *ctx, const OsdFrames &fr, const typename FAM::perm
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
 }
+
+// ---------------------------------------------------------------------------------------
+// The OSD stage of ldpc_family_pipeline_run (ldpc_api.hip) on one family: its two launches, front end and scan apart (the
+// pipeline records a timing event in between), behind one signature.  d_perm travels as void *: its element is the family's
+// perm_t.  PB: the family's PB scan (each family launches its own kernel).  The checks are family_pipeline_check's
+// (ldpc_family_check.h), which needs no kernel.
+// ---------------------------------------------------------------------------------------
+struct FamilyStage {
+    int (*front)(const ldpc_ctx *, const OsdFrames &, void *d_perm, uint64_t *d_parity, hipStream_t);
+    int (*scan)(const ldpc_ctx *, const OsdFrames &, const void *d_perm, const uint64_t *d_parity, const ldpc_osd_params *, const OsdScanOut &,
+                OsdCounting, hipStream_t);
+};
+
+template <class FAM, const OsdScan<typename FAM::perm_t> &PB>
+struct FamilyStageOf {
+    using perm_t = typename FAM::perm_t;
+    static int front(const ldpc_ctx *ctx, const OsdFrames &fr, void *d_perm, uint64_t *d_parity, hipStream_t s)
+    {
+        return family_launch_front<FAM>(ctx, fr, static_cast<perm_t *>(d_perm), d_parity, nullptr, s);
+    }
+    static int scan(const ldpc_ctx *ctx, const OsdFrames &fr, const void *d_perm, const uint64_t *d_parity, const ldpc_osd_params *p,
+                    const OsdScanOut &o, OsdCounting c, hipStream_t s)
+    {
+        const perm_t *perm = static_cast<const perm_t *>(d_perm);
+        if (p->algo == LDPC_OSD_FS) return family_launch_fs<FAM>(ctx, fr, perm, d_parity, p, o, c, s);
+        if (p->algo == LDPC_OSD_PB) return PB.launch(ctx, fr, perm, d_parity, p, o, c, s);
+        return family_launch_search<FAM>(ctx, fr, perm, d_parity, p->order, o, c, s);
+    }
+    static FamilyStage make() { return {front, scan}; }
+};
+// one per family, each beside the family's PB scan: ldpc_osdx.hip, ldpc_osdw.hip, ldpc_osdl_pb.hip
+const FamilyStage &osdx_stage();
+const FamilyStage &osdw_stage();
+const FamilyStage &osdl_stage();
 
 }  // namespace ldpc

@@ -1,7 +1,7 @@
 // OSD for longer and low-rate codes: the ldpc_osdl_* entry points.
 // For every code with n <= 384, 1 <= k <= 192 and 1 <= n - k <= 192: the front end and the conventional order-p scan (device
-// code: ldpc_osdl.h).  FS-OSD and the one-TEP primitive of the family are in ldpc_osdl_fs.hip; PB-OSD and the one-call pipeline
-// stay with the families of ldpc_osdx.hip / ldpc_osdw.hip and with the (128,64) kernels.
+// code: ldpc_osdl.h).  FS-OSD and the one-TEP primitive of the family are in ldpc_osdl_fs.hip, PB-OSD and the family's
+// stage of ldpc_family_pipeline_run in ldpc_osdl_pb.hip.
 // The W-word G columns and the TEP tables of k are the context's OsdlTables (ldpc_osd_tables.h), uploaded by ldpc_ctx_create.
 // Validation, launches and the bodies of the entry points are those of ldpc_osd_family.h, shared with ldpc_osdx.hip and
 // ldpc_osdw.hip; this family's d_perm is uint16_t and its kernels are instantiations chosen by the shape (ldpc_osdl_family.h).

@@ -23,7 +23,7 @@ struct Osdl {
     using pb_fn = void (*)(const float *, const int *, const int *, long long, int, int, const unsigned short *, const u64 *, const double *,
                            PbxParams, u64 *, float *, int *, int *, int *, const u64 *, u64 *);
     static const OsdlTables &tables(const ldpc_ctx *ctx) { return ctx->osdl_tables; }
-    static constexpr const char *needs = "the long / low-rate OSD kernels need n <= 384, 1 <= k <= 192 and 1 <= n-k <= 192";
+    static constexpr const char *needs = kOsdlNeeds;
     static front_fn front(const OsdlTables &t);         // ldpc_osdl.hip: S = ceil(n / 64) rounded up to 2, 4 or 6 slots, W = ceil(k / 64) row words
     static search_fn search(const OsdlTables &t);       // ldpc_osdl.hip: Wp = ceil((n - k) / 64) words of discrepancy
     static fs_fn fs(const OsdlTables &t);               // ldpc_osdl_fs.hip: Wp

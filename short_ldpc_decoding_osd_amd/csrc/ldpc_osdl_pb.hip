@@ -45,6 +45,7 @@ static int osdl_launch_pb(const ldpc_ctx *ctx, const OsdFrames &fr, const uint16
     return LDPC_OK;
 }
 constexpr OsdScan<uint16_t> osdl_pb_scan{LDPC_OSD_PB, "LDPC_OSD_PB", true, osdl_launch_pb};
+const FamilyStage &osdl_stage() { static const FamilyStage st = FamilyStageOf<Osdl, osdl_pb_scan>::make(); return st; }   // ldpc_family_pipeline_run
 
 }  // namespace ldpc
 

@@ -1,7 +1,8 @@
 // OSD for high-rate short codes: the ldpc_osdw_* entry points.
 // For every code with n <= 128 and 1 <= n - k <= 64, hence k up to 127: the front end, the conventional order-p scan (device
 // code: ldpc_osdw.h), FS-OSD and the one-TEP primitive (ldpc_osdw_fs.h) and PB-OSD (ldpc_osdw_pb.h).  The PB tuning and routes and
-// the one-call pipeline stay with the (128,64) kernels of ldpc_osd.hip / ldpc_osd_pb.hip.
+// ldpc_pipeline_run stay with the (128,64) kernels of ldpc_osd.hip / ldpc_osd_pb.hip; osdw_stage() is this family's OSD stage of
+// ldpc_family_pipeline_run (ldpc_api.hip).
 // The two-word G columns and the TEP tables of k are the context's OsdwTables (ldpc_osd_tables.h), uploaded by ldpc_ctx_create.
 // Validation, launches and the bodies of the entry points are those of ldpc_osd_family.h, shared with ldpc_osdx.hip; PB-OSD has a
 // kernel per family, so each family launches its own.
@@ -15,7 +16,7 @@ namespace ldpc {
 
 struct Osdw {
     static const OsdwTables &tables(const ldpc_ctx *ctx) { return ctx->osdw_tables; }
-    static constexpr const char *needs = "the high-rate OSD kernels need 1 <= n-k <= 64 and n <= 128";
+    static constexpr const char *needs = kOsdwNeeds;
     using perm_t = uint8_t;
     static constexpr auto front(const OsdwTables &) { return osdw_front_kernel; }
     static constexpr auto search(const OsdwTables &) { return osdw_search_kernel; }
@@ -45,6 +46,7 @@ static int osdw_launch_pb(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_
     return LDPC_OK;
 }
 constexpr OsdScan<uint8_t> osdw_pb_scan{LDPC_OSD_PB, "LDPC_OSD_PB", true, osdw_launch_pb};
+const FamilyStage &osdw_stage() { static const FamilyStage st = FamilyStageOf<Osdw, osdw_pb_scan>::make(); return st; }   // ldpc_family_pipeline_run
 
 }  // namespace ldpc
 

@@ -1,7 +1,8 @@
 // OSD for short codes of any shape: the ldpc_osdx_* entry points.
 // For every code with 1 <= k <= 64 and 1 <= n - k <= 64: the front end, the conventional order-p scan (device code:
-// ldpc_osdx.h), FS-OSD and the one-TEP primitive (ldpc_osdx_fs.h) and PB-OSD (ldpc_osdx_pb.h).  The PB tuning and routes and the
-// one-call pipeline stay with the (128,64) kernels of ldpc_osd.hip / ldpc_osd_pb.hip.
+// ldpc_osdx.h), FS-OSD and the one-TEP primitive (ldpc_osdx_fs.h) and PB-OSD (ldpc_osdx_pb.h).  The PB tuning and routes and
+// ldpc_pipeline_run stay with the (128,64) kernels of ldpc_osd.hip / ldpc_osd_pb.hip; osdx_stage() is this family's OSD stage of
+// ldpc_family_pipeline_run (ldpc_api.hip).
 // The G columns and the TEP tables are the context's OsdTables (ldpc_osd_tables.h), the set the (128,64) kernels read as well.
 // Validation, launches and the bodies of the entry points are those of ldpc_osd_family.h, shared with ldpc_osdw.hip; PB-OSD has a
 // kernel per family, so each family launches its own.
@@ -15,7 +16,7 @@ namespace ldpc {
 
 struct Osdx {
     static const OsdTables &tables(const ldpc_ctx *ctx) { return ctx->osd_tables; }
-    static constexpr const char *needs = "the any-shape OSD kernels need 1 <= k <= 64 and 1 <= n-k <= 64";
+    static constexpr const char *needs = kOsdxNeeds;
     using perm_t = uint8_t;
     static constexpr auto front(const OsdTables &) { return osdx_front_kernel; }
     static constexpr auto search(const OsdTables &) { return osdx_search_kernel; }
@@ -40,6 +41,7 @@ static int osdx_launch_pb(const ldpc_ctx *ctx, const OsdFrames &fr, const uint8_
     return LDPC_OK;
 }
 constexpr OsdScan<uint8_t> osdx_pb_scan{LDPC_OSD_PB, "LDPC_OSD_PB", true, osdx_launch_pb};
+const FamilyStage &osdx_stage() { static const FamilyStage st = FamilyStageOf<Osdx, osdx_pb_scan>::make(); return st; }   // ldpc_family_pipeline_run
 
 }  // namespace ldpc
 

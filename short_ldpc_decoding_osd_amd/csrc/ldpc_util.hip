@@ -6,6 +6,7 @@
 // :51 (failure index), Ldpc_128_testing/data_generating.py / read_TFdata.py (labels are one
 // int64 per bit).
 #include "ldpc_internal.h"
+#include "ldpc_family_check.h"   // osd_merge_check
 
 namespace ldpc {
 
@@ -43,6 +44,49 @@ __global__ __launch_bounds__(256) void eval_counts_kernel(const unsigned long lo
     // serialise at the memory side, so keep them rare
     if (threadIdx.x < 5)
         atomicAdd(&counts[threadIdx.x], part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
+}
+
+// ---------------------------------------------------------------------------------------
+// ldpc_osd_merge: the OSD codewords back among the NMS decisions, and the bit errors before and after.  One lane per
+// listed frame j < min(*count, F): f = index[j], the `words` words of hard[f] are replaced by cw[j] -- the lane reads
+// the old word before it writes the new one, and the entries of index are distinct, so the in-place form has no race --
+// and counts[4] += {frames, frames with cw[j] != label[f], bit errors of cw[j], bit errors of the OLD hard[f]}.
+// Work proportional to the failures: a listed frame costs 2-3 reads and a write of `words` words.  Per-wave reduction
+// by shuffles, one atomic per counter and block.
+// ---------------------------------------------------------------------------------------
+template <bool HARD, bool COUNT>
+__global__ __launch_bounds__(256) void osd_merge_kernel(const unsigned long long *__restrict__ cw, const int *__restrict__ index,
+                                                        const int *__restrict__ count, long long F, int words,
+                                                        unsigned long long *__restrict__ hard,
+                                                        const unsigned long long *__restrict__ label,
+                                                        unsigned long long *__restrict__ counts)
+{
+    __shared__ unsigned long long part[4][4];
+    const long long c = *count, nframes = c < F ? c : F;
+    if ((long long)blockIdx.x * blockDim.x >= nframes) return;   // (the whole block: the grid is sized by F, not by the count)
+    unsigned long long cnt = 0, wrong = 0, after = 0, before = 0;
+    for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < nframes; j += (long long)gridDim.x * blockDim.x) {
+        const long long f = index[j];
+        int ea = 0, eb = 0;
+        for (int w = 0; w < words; ++w) {
+            const unsigned long long v = cw[j * words + w];
+            if constexpr (COUNT) {
+                const unsigned long long l = label[f * words + w];
+                ea += __popcll(v ^ l);
+                if constexpr (HARD) eb += __popcll(hard[f * words + w] ^ l);
+            }
+            if constexpr (HARD) hard[f * words + w] = v;
+        }
+        cnt += 1; wrong += ea != 0; after += ea; before += eb;
+    }
+    if constexpr (COUNT) {
+        cnt = wave_sum(cnt); wrong = wave_sum(wrong); after = wave_sum(after); before = wave_sum(before);
+        const int wave = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) { part[wave][0] = cnt; part[wave][1] = wrong; part[wave][2] = after; part[wave][3] = before; }
+        __syncthreads();
+        if (threadIdx.x < 4)
+            atomicAdd(&counts[threadIdx.x], part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -276,6 +320,23 @@ int ldpc_eval_counts(ldpc_ctx *ctx, const uint64_t *d_hard, const uint64_t *d_la
     hipLaunchKernelGGL(eval_counts_kernel, dim3(grid_for(B, 1024, 128)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const unsigned long long *>(d_hard),
                        reinterpret_cast<const unsigned long long *>(d_label), d_fail, (long long)B, words,
+                       reinterpret_cast<unsigned long long *>(d_counts));
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+int ldpc_osd_merge(ldpc_ctx *ctx, const uint64_t *d_cw, const int32_t *d_index, const int32_t *d_count, int64_t F, uint64_t *d_hard,
+                   const uint64_t *d_label_bits, int64_t *d_counts, void *stream)
+{
+    bool launch;
+    if (int rc = osd_merge_check(ctx, d_cw, d_index, d_count, F, d_hard, d_label_bits, d_counts, &launch)) return rc;
+    if (!launch) return LDPC_OK;
+    const bool counting = d_label_bits && d_counts;   // a pair or neither, as in the family decode calls
+    const int words = (ctx->code.n + 63) / 64;
+    const auto kern = d_hard ? (counting ? osd_merge_kernel<true, true> : osd_merge_kernel<true, false>) : osd_merge_kernel<false, true>;
+    hipLaunchKernelGGL(kern, dim3(grid_for(F, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const unsigned long long *>(d_cw), d_index, d_count, (long long)F, words,
+                       reinterpret_cast<unsigned long long *>(d_hard), reinterpret_cast<const unsigned long long *>(d_label_bits),
                        reinterpret_cast<unsigned long long *>(d_counts));
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;

@@ -82,3 +82,69 @@ class BatchPipeline:
     def counters(self):
         """int64[8]: {frames, frame_err, bit_err, undetected, synd_fail, osd_frames, osd_wrong, teps}."""
         return self._counts
+
+
+class FamilyPipeline:
+    """``BatchPipeline`` for every code a G-form OSD family serves (``ldpc_family_pipeline_run``), with the decoder's final
+    output: after ``run()`` ``hard`` holds the OSD codewords among the NMS decisions (``merge``).
+
+    ``family``: ``"osdx"`` / ``"osdw"`` / ``"osdl"``, or None for the first of them that serves the code; ``.family`` is the
+    prefix that was picked.  ``capacity``: the frames the OSD buffers hold (None: B); the OSD stage and the merge run on
+    min(count, capacity) frames, ``count`` stays the number of syndrome failures.  ``perm`` and ``parity`` are in the
+    family's layouts (``Decoder._osd_layout``).  Without ``osd_order`` this is the NMS-only pipeline, on any code."""
+
+    def __init__(self, dec: Decoder, B: int, T: int, alpha, osd_order=None, osd_algo=_lib.OSD_CONVENTIONAL, snr_db=0.0,
+                 family=None, capacity=None, merge=True, want_soft=True, w_in=1.0, w_out=1.0, **osd_kw):
+        self.dec, self.B, self.T = dec, int(B), int(T)
+        e = dec.empty
+        self.soft = e((B, dec.n), torch.float32) if want_soft else None
+        self.hard = e((B, dec.words), torch.int64)
+        self.fail = e((B,), torch.uint8)
+        self._counts = torch.zeros(12, dtype=torch.int64, device=dec.device)   # one buffer: no torch op to gather them
+        self.nms_counts, self.osd_counts, self.final_counts = self._counts[:5], self._counts[5:8], self._counts[8:]
+        self._alpha = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, dtype=np.float32), (max(T, 1),)))
+        p = _lib.FamilyPipeline()
+        p.B, p.T, p.nms_kernel = self.B, self.T, _lib.NMS_AUTO
+        p.alpha = self._alpha.ctypes.data_as(C.POINTER(C.c_float))
+        p.w_in, p.w_out = float(w_in), float(w_out)
+        p.d_soft = self.soft.data_ptr() if want_soft else None
+        p.d_hard, p.d_fail = self.hard.data_ptr(), self.fail.data_ptr()
+        p.d_nms_counts = self.nms_counts.data_ptr()
+        p.osd_enable, p.timing_slot = int(osd_order is not None), -1
+        self.osd_order, self.family, self.capacity = osd_order, None, None
+        if osd_order is not None:
+            if family is not None and family not in _lib.OSD_FAMILIES:
+                raise ValueError(f"family {family!r}: expected one of {sorted(_lib.OSD_FAMILIES)} or None")
+            self.family = family if family is not None else dec.osd_family()
+            self.capacity = cap = self.B if capacity is None else int(capacity)
+            pdt, ptail, qtail, _ = dec._osd_layout(self.family)
+            self.index, self.count = e((B,), torch.int32), e((1,), torch.int32)
+            self.perm, self.parity = e((cap,) + ptail, pdt), e((cap,) + qtail, torch.int64)
+            self.cw, self.metric = e((cap, dec.words), torch.int64), e((cap,), torch.float32)
+            self.best, self.ntep = e((cap,), torch.int32), e((cap,), torch.int32)
+            self.aux = torch.zeros((cap, 4), dtype=torch.int32, device=dec.device) if osd_algo == _lib.OSD_PB else None
+            p.osd = dec.osd_params(osd_order, osd_algo, snr_db=snr_db, aux=self.aux, **osd_kw)
+            p.family = _lib.OSD_FAMILY_AUTO if family is None else _lib.OSD_FAMILIES[family]
+            p.merge, p.osd_capacity = int(bool(merge)), cap
+            p.d_index, p.d_count = self.index.data_ptr(), self.count.data_ptr()
+            p.d_perm, p.d_parity = self.perm.data_ptr(), self.parity.data_ptr()
+            p.d_cw, p.d_metric = self.cw.data_ptr(), self.metric.data_ptr()
+            p.d_best, p.d_ntep = self.best.data_ptr(), self.ntep.data_ptr()
+            p.d_osd_counts, p.d_final_counts = self.osd_counts.data_ptr(), self.final_counts.data_ptr()
+        self._p = p
+        self._y = self._labels = None
+
+    bind = BatchPipeline.bind
+    timing = BatchPipeline.timing
+    reset_counters = BatchPipeline.reset_counters
+
+    def run(self, timing_slot=-1):
+        if self._y is None:
+            raise RuntimeError("bind() a batch first")
+        self._p.timing_slot = int(timing_slot)
+        _lib.check(self.dec.L.ldpc_family_pipeline_run(self.dec._ctx, C.byref(self._p), self.dec._stream()), "ldpc_family_pipeline_run")
+
+    def counters(self):
+        """int64[12]: the eight of ``BatchPipeline.counters``, then the merge's {merged, merged_wrong, bit_err_after,
+        bit_err_before}.  End-to-end bit errors: counters[2] - counters[11] + counters[10]."""
+        return self._counts

@@ -853,6 +853,22 @@ class Decoder:
                                           F, _ptr(counts), self._stream()), "ldpc_osd_counts")
         return counts
 
+    def osd_merge(self, cw, index, count, hard=None, label_bits=None, counts=None, F=None):
+        """The OSD codewords back among the NMS decisions: hard[index[j]] = cw[j] for j < min(count, F), in place, and with
+        ``label_bits`` counts[4] += {frames, frames_wrong, bit errors of cw, bit errors of the replaced rows of hard} (the last
+        stays 0 without ``hard``).  ``counts`` is allocated when labels come without it.  Returns counts (None without labels)."""
+        F = cw.shape[0] if F is None else F
+        if counts is None and label_bits is not None:
+            counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+        _lib.check(self.L.ldpc_osd_merge(self._ctx, _ptr(cw), _ptr(index), _ptr(count), F, _ptr(hard), _ptr(label_bits),
+                                         _ptr(counts), self._stream()), "ldpc_osd_merge")
+        return counts
+
+    def osd_family(self):
+        """The prefix of the G-form OSD family that serves this code: ``"osdx"`` where ``osdx_supported``, else ``"osdw"``, else
+        ``"osdl"`` (which refuses the code where it does not serve it either): LDPC_OSD_FAMILY_AUTO."""
+        return "osdx" if self.osdx_supported else "osdw" if self.osdw_supported else "osdl"
+
 
 _default = {}
 

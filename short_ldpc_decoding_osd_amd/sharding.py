@@ -42,7 +42,7 @@ def end_to_end_errors(counters, with_osd: bool) -> int:
 
 
 def sweep_point(decode_batch, frames_mine: int, batch: int, max_batches: int, stop_errors: int = 0, with_osd: bool = True,
-                device=None):
+                device=None, width: int = 8):
     """The macro-batch loop of ONE SNR point on one rank, with the reference's stop rule.
 
     ``decode_batch(B)`` decodes the next B frames of this rank's shard and returns their int64[8] counters
@@ -61,9 +61,12 @@ def sweep_point(decode_batch, frames_mine: int, batch: int, max_batches: int, st
     and a rank whose shard is EMPTY never gets a tensor from ``decode_batch`` to copy the device from; default: CPU, which
     is what the gloo tests use).
 
-    Returns (reduced int64[8] totals, macro-batches run)."""
+    ``width``: the number of counters ``decode_batch`` returns, i.e. the length of the zero tensor of a rank without frames: 8
+    for ``BatchPipeline``, 12 for ``FamilyPipeline`` (the four of the merge follow).  The stop rule reads the first eight.
+
+    Returns (reduced int64[width] totals, macro-batches run)."""
     def zeros():
-        return torch.zeros(8, dtype=torch.int64, device=device)
+        return torch.zeros(int(width), dtype=torch.int64, device=device)
 
     total = None
     done = 0
@@ -85,10 +88,14 @@ def sweep_point(decode_batch, frames_mine: int, batch: int, max_batches: int, st
     return allreduce_counters(total if total is not None else zeros()), ran
 
 
-def combine_fer(counters) -> dict:
+def combine_fer(counters, n=None) -> dict:
     """Readable rates from the 8 summed counters {frames, frame_err, bit_err, undetected,
     synd_fail, osd_frames, osd_wrong, teps}: both factors and their product, as the recipe
-    multiplies them (Training and Testing recipe.txt:18)."""
+    multiplies them (Training and Testing recipe.txt:18).
+
+    With the 12 counters of ``FamilyPipeline`` -- then {merged, merged_wrong, bit_err_after, bit_err_before} of the merge -- the
+    bit errors of the final decisions as well: ``bit_err_end_to_end`` = bit_err - bit_err_before + bit_err_after, and with the
+    code length ``n`` the rates ``ber_nms`` and ``ber_end_to_end`` over frames x n bits."""
     c = [int(x) for x in counters]
     frames = max(c[0], 1)
     out = {"frames": c[0], "fer_nms": c[1] / frames, "synd_fail_rate": c[4] / frames, "undetected": c[3]}
@@ -97,4 +104,9 @@ def combine_fer(counters) -> dict:
         out["fer_product"] = out["synd_fail_rate"] * out["fer_osd_given_fail"]
         out["fer_end_to_end"] = (c[6] + c[3]) / frames
         out["mean_teps"] = c[7] / c[5]
+    if len(c) >= 12:
+        out["bit_err_end_to_end"] = c[2] - c[11] + c[10]
+        if n is not None:
+            out["ber_nms"] = c[2] / (frames * int(n))
+            out["ber_end_to_end"] = out["bit_err_end_to_end"] / (frames * int(n))
     return out
