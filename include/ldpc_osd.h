@@ -1066,6 +1066,101 @@ typedef struct ldpc_family_pipeline {
 } ldpc_family_pipeline;
 int ldpc_family_pipeline_run(ldpc_ctx *ctx, const ldpc_family_pipeline *p, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The one-call pipeline with the DL-OSD stage on the four H-form families, i.e. for every code the ldpc_hosd_*,
+ * ldpc_hosdx_*, ldpc_hosdw_* or ldpc_hosdl_* entry points serve (up to (384,192)): the counterpart of
+ * ldpc_family_pipeline_run for the decoder of nn_testing.Testing_OSD, from channel frames.
+ * The results of this sequence on one stream, with no host round trip, no allocation and no synchronisation (the frame
+ * count of every step after the compaction is min(*d_count, C), read on the device; C = osd_capacity):
+ *   ldpc_nms_decode
+ *   ldpc_eval_counts + ldpc_compact     (one launch when d_label_bits and d_nms_counts are given)
+ *   ldpc_nms_traj_rows on the list      -> d_rows [C][T+1][n]                       (with a CNN only)
+ *   ldpc_dia_cnn                        -> d_order_llr [C][n]                       (with a CNN only)
+ *   gather (one launch)                 -> d_metric_llr [C][n] = d_llr[d_index[j]], d_list_labels [C][W] = d_label_bits[d_index[j]]
+ *   ldpc_hosd{,x,w,l}_front  on the ordering values      -> d_lri, d_uidx, d_M, d_nswaps
+ *   ldpc_hosd{,x,w,l}_sliding on them and d_metric_llr   -> d_deep_limit, d_global_min, d_truth, d_success, d_cw, d_metric,
+ *                                                           d_best, d_teps_evaluated
+ *   stage counters (one launch)         -> d_dl_counts
+ *   ldpc_osd_merge into d_hard          (with `merge`), d_final_counts its counters
+ * The members up to timing_slot, d_index, d_count, osd_capacity, merge and d_final_counts are those of
+ * ldpc_family_pipeline, with the same meaning and the same nullable rules.  The stage and the merge run on
+ * min(*d_count, C) frames and write nothing at or beyond that row of any list buffer; *d_count stays the number of
+ * syndrome failures, so frames were left out exactly when d_dl_counts[0] < d_nms_counts[4].
+ *   family        LDPC_HOSD_FAMILY_AUTO: ldpc_hosd_* on (128,64), else ldpc_hosdx_*, else ldpc_hosdw_*, else ldpc_hosdl_*
+ *                 (what Decoder.hosd_stage_family() picks on every code a family serves; on a code none serves that
+ *                 method names hosdw and AUTO ends at hosdl, the last one tried: both refuse); or one family by name.  A forced family that refuses the code
+ *                 is LDPC_E_UNSUPPORTED with that family's own sentence, AUTO on a code none serves with the sentence of
+ *                 ldpc_hosdl_*.
+ *   cnn_weights   host [n_cnn_weights], as ldpc_dia_cnn takes them (L = T + 1 >= 7, checked before any launch).  NULL is
+ *                 DIA = False: no trajectory is decoded, d_rows is neither read nor written and may be NULL, and the
+ *                 ordering values are the channel values.  d_order_llr may then be NULL -- it aliases d_metric_llr: front
+ *                 end and scan read that buffer for both of their inputs -- or a buffer of its own, which the gather fills
+ *                 with the same rows.
+ *   d_teps, d_block_off, nblk, win, soft_margin, fcn_weights, n_fcn_weights, group   as ldpc_hosd_sliding takes them.
+ *                 Both weight blocks are HOST memory and are copied by value into the kernel arguments at the call, and
+ *                 hence at capture: a captured graph keeps the weights it was captured with.
+ *   d_lri, d_uidx, d_M   C rows each in the layouts of the chosen family's _front (u8 [128] / u16 [64 ceil(n/64)] indices);
+ *                 the caller's scratch and output.  Required with the stage on, as are d_index, d_count, d_metric_llr,
+ *                 d_cw, d_teps, d_block_off and fcn_weights; d_rows and d_order_llr with a CNN.
+ *   d_nswaps, d_deep_limit, d_global_min, d_truth, d_success, d_metric, d_best, d_teps_evaluated   [C], nullable, each on
+ *                 its own (d_truth and d_success are written with d_label_bits only); d_deep_limit is required whenever
+ *                 d_dl_counts is given.  d_list_labels [C][W] is required when d_label_bits is given, and ignored without.
+ *   d_dl_counts   [6] i64 += {frames through the stage, frames with global_min == truth (the reference's S), the others
+ *                 (its F), sum of deep_limit - win + 1 (windows), sum of d_block_off[deep_limit] (the reference's
+ *                 complexity, acc_block_size[deep_limit]), sum of d_teps_evaluated}.  [1] and [2] need d_label_bits and
+ *                 somewhere the scan's verdict lands: d_success, or d_global_min and d_truth together (the counters then
+ *                 compare the two floats as the scan does); with labels and none of these they stay.  [5] moves with
+ *                 d_teps_evaluated only.
+ * Everything is checked before the first launch; a refusal begins "ldpc_dlosd_pipeline_run: " and names the member (an
+ * unsupported shape is the family's sentence).  With osd_enable = 0 every code a context exists for is served and every
+ * member from `family` on is ignored (NMS and its counters alone).  With B = 0 and the stage on, *d_count is zeroed.
+ * timing_slot and ldpc_pipeline_timing serve this pipeline too: ms = {NMS, rows + CNN + gather + front end, sliding scan}.
+ * ------------------------------------------------------------------------------------- */
+#define LDPC_HOSD_FAMILY_AUTO 0   /* hosd on (128,64), else hosdx, else hosdw, else hosdl */
+#define LDPC_HOSD_FAMILY_128 1
+#define LDPC_HOSD_FAMILY_X 2
+#define LDPC_HOSD_FAMILY_W 3
+#define LDPC_HOSD_FAMILY_L 4
+typedef struct ldpc_dlosd_pipeline {
+    const float *d_llr;            /* [B][n]                                               */
+    int64_t B;
+    int32_t T, nms_kernel;
+    const float *alpha;            /* host [T]                                             */
+    float w_in, w_out;
+    float *d_soft;                 /* [B][n] nullable                                      */
+    uint64_t *d_hard;              /* [B][ceil(n/64)]                                      */
+    uint8_t *d_fail;               /* [B]                                                  */
+    const uint64_t *d_label_bits;  /* [B][ceil(n/64)] nullable: no counters                */
+    int64_t *d_nms_counts;         /* [5] accumulated, nullable                            */
+    int32_t osd_enable, timing_slot;
+    int32_t family, merge;         /* LDPC_HOSD_FAMILY_*; merge != 0: ldpc_osd_merge into d_hard */
+    int32_t *d_index, *d_count;    /* [B], [1]                                             */
+    int64_t osd_capacity;          /* C; 0 = B                                             */
+    const float *cnn_weights;      /* host [n_cnn_weights]; NULL: no CNN (DIA = False)     */
+    const float *fcn_weights;      /* host [n_fcn_weights]                                 */
+    int32_t n_cnn_weights, n_fcn_weights;
+    const uint8_t *d_teps;         /* [d_block_off[nblk]][4]                               */
+    const int32_t *d_block_off;    /* [nblk + 1]                                           */
+    int32_t nblk, win, group;
+    double soft_margin;
+    float *d_rows;                 /* [C][T+1][n], with a CNN                              */
+    float *d_order_llr;            /* [C][n]; required with a CNN, nullable without        */
+    float *d_metric_llr;           /* [C][n]                                               */
+    uint64_t *d_list_labels;       /* [C][ceil(n/64)], required with d_label_bits          */
+    void *d_lri, *d_uidx;          /* [C][...] the family's index rows                     */
+    uint64_t *d_M;                 /* [C][...] the family's M rows                         */
+    int32_t *d_nswaps;             /* [C] nullable                                         */
+    int32_t *d_deep_limit;         /* [C] nullable without d_dl_counts                     */
+    float *d_global_min, *d_truth; /* [C] nullable                                         */
+    uint8_t *d_success;            /* [C] nullable                                         */
+    uint64_t *d_cw;                /* [C][ceil(n/64)]                                      */
+    float *d_metric;               /* [C] nullable                                         */
+    int32_t *d_best, *d_teps_evaluated;   /* [C] nullable, each on its own                 */
+    int64_t *d_dl_counts;          /* [6] accumulated, nullable                            */
+    int64_t *d_final_counts;       /* [4] accumulated, nullable (as ldpc_osd_merge)        */
+} ldpc_dlosd_pipeline;
+int ldpc_dlosd_pipeline_run(ldpc_ctx *ctx, const ldpc_dlosd_pipeline *p, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,18 @@ the bit error rates before and after the OSD codewords are merged into the NMS d
 another shape goes through the NumPy port frame by frame (a smaller sample in the same time) and FS / PB are not judged.
 
     python scripts/snr_sweep.py --alist tests/golden/LDPC_N96_K48_P8_set0_dmin10.alist --osd conv --order 2 --cpu-check
+
+`--osd dl --training DIR [--alist FILE]` sweeps NMS + the DL-OSD stage on `pipeline.DlOsdPipeline` (one call per batch, any code
+an H-form family serves), with the networks and the decoding path taken exactly as `scripts/run_dl_osd.py` takes them: the CNN
+and classifier checkpoints under DIR/ckpts/, the dist-error-pattern pickle under DIR/log/ (or `--convention-path`), `--no-dia`
+for DIA = False, `--type` for the decoder type in those paths.  `--capacity` sizes the per-failure buffers (frames beyond it
+stay NMS failures; the JSON line's `left_out` counts them).  Every other option works as on the other legs (`--gen hip`,
+`--streams`, multi-rank, `--stop-errors`: undetected + merged wrong).  The JSON line carries the 15 counters' rates: `fer_end_to_end`,
+`ber_nms`, `ber_end_to_end`, `fer_dl_given_fail`, `mean_windows`, `mean_complexity`, `mean_teps`.  `--cpu-check` there: the
+failures of the point's last batch on rank 0 (at most `--cpu-frames`) go through the host route `osd.sliding_osd` -- block minima
+on the device, the window loop and the classifier on the host -- and `dl_vs_host` holds both sides' (S, F, windows, complexity).
+
+    python scripts/snr_sweep.py --osd dl --training DIR --snr 2.0 3.0 3 --iters 12 --capacity 16384 --cpu-check
 """
 import argparse
 import json
@@ -39,7 +51,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from short_ldpc_decoding_osd_amd import Code, _lib  # noqa: E402
-from short_ldpc_decoding_osd_amd.pipeline import BatchPipeline, FamilyPipeline  # noqa: E402
+from short_ldpc_decoding_osd_amd.pipeline import BatchPipeline, DlOsdPipeline, FamilyPipeline  # noqa: E402
 from short_ldpc_decoding_osd_amd.runtime import Decoder  # noqa: E402
 from short_ldpc_decoding_osd_amd.sharding import combine_fer, end_to_end_errors, rank_seed, shard_range, sweep_point  # noqa: E402
 from short_ldpc_decoding_osd_amd.weights import softplus32  # noqa: E402
@@ -108,13 +120,64 @@ def cpu_check(code, alpha, args, snr, gpu_errors, gpu_frames):
             "judged": bool(enough), "within_5_percent": bool(abs(rel) <= 0.05) if enough else "not judged"}
 
 
+def dl_setup(args):
+    """The DL-OSD stage's settings, networks and decoding path, as scripts/run_dl_osd.py and nn_testing.Testing_OSD take them
+    -> dict(dec, inst, fcn, nn, blocks, acc, teps, off, win, margin, path)."""
+    from short_ldpc_decoding_osd_amd import globalmap as GL
+    from short_ldpc_decoding_osd_amd import nn_testing as NT
+    from short_ldpc_decoding_osd_amd import ordered_statistics_decoding as OSD
+    GL.global_setting(["prog", args.snr[0], args.snr[1], args.snr[2], str(args.batch), str(args.iters),
+                       args.alist or "CCSDS_ldpc_n128_k64.alist", args.type], stage="DL")
+    GL.set_map('dl_training_dir', os.path.join(os.path.abspath(args.training), ""))
+    GL.set_map('convention_path', args.convention_path)
+    indicator_list, prefix_list = [True, False, False], ['model_cnn', 'model_rnn1', 'model_rnn2']
+    restore_list = [GL.logistic_setting_model(indicator_list, prefix_list), GL.set_predict_model(True)]
+    dia = not args.no_dia
+    inst = OSD.osd(GL.get_map('code_parameters'))
+    query = NT.query_convention_path if args.convention_path else NT.query_decoding_path
+    path, _ = query(indicator_list, prefix_list, dia)
+    blocks, acc = OSD.generate_teps(inst, path)
+    nn, fcn = NT.NN_gen(restore_list, indicator_list) if dia else (None, NT.load_fcn(restore_list[1]))
+    dec = OSD._dec()                                            # (the host route of --cpu-check decodes on this context too)
+    teps, off = inst._device_blocks(dec, blocks)
+    return dict(dec=dec, inst=inst, fcn=fcn, nn=nn, blocks=blocks, acc=np.asarray(acc, dtype=np.int64), teps=teps, off=off,
+                win=GL.get_map('sliding_win_width'), margin=GL.get_map('soft_margin'), path=path)
+
+
+def dl_cpu_check(dl, pipe, limit):
+    """The failures that ``pipe`` holds (its last batch; at most ``limit``) through the host route osd.sliding_osd, beside what the
+    one call made of the same frames: (success, failure, windows, complexity) of both sides."""
+    dec, win = pipe.dec, dl["win"]
+    F = min(int(pipe.count.item()), pipe.capacity, int(limit))
+    if F == 0:
+        return {"frames": 0, "agree": "not judged"}
+    L = pipe.T + 1
+    metric = pipe.metric_llr[:F].cpu().numpy()
+    if pipe.rows is not None:
+        input_list, ordering = pipe.rows[:F].cpu().numpy().reshape(F * L, dec.n), pipe.order_llr[:F].cpu().numpy()
+    else:                                                       # DIA = False: only row 0 of a trajectory is read
+        input_list, ordering = np.zeros((F * L, dec.n), dtype=np.float32), metric
+        input_list[0::L] = metric
+    labels = dec.unpack_bits(pipe.list_labels[:F].contiguous()).cpu().numpy()
+    host = dl["inst"].sliding_osd(dl["fcn"], input_list, ordering, labels, (dl["blocks"], dl["acc"]))
+    deep, ok = pipe.deep_limit[:F].cpu().numpy().astype(np.int64), pipe.success[:F].cpu().numpy().astype(bool)
+    device = (int(ok.sum()), int((~ok).sum()), int((deep - win + 1).sum()), int(dl["acc"][deep].sum()))
+    return {"frames": F, "host": [int(v) for v in host], "device": list(device), "agree": tuple(int(v) for v in host) == device}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--snr", nargs=3, default=["1.0", "3.5", "6"], metavar=("LO", "HI", "NUM"))
     ap.add_argument("--frames", type=int, default=1 << 20, help="frames per SNR point, all ranks together")
     ap.add_argument("--batch", type=int, default=131072, help="frames per device batch")
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--osd", choices=sorted(ALGOS), default="pb")
+    ap.add_argument("--osd", choices=sorted(ALGOS) + ["dl"], default="pb")
+    ap.add_argument("--training", default=None, help="--osd dl: the training stage's directory (ckpts/, log/), as run_dl_osd.py takes it")
+    ap.add_argument("--type", default="NMS-1", help="--osd dl: the decoder type in the training directory's paths")
+    ap.add_argument("--no-dia", action="store_true", help="--osd dl: no CNN, the ordering values are the channel values")
+    ap.add_argument("--convention-path", action="store_true", help="--osd dl: the conventional decoding path instead of the pickle's")
+    ap.add_argument("--capacity", type=int, default=0, help="--osd dl: rows of the per-failure buffers (0: the batch size)")
+    ap.add_argument("--cpu-frames", type=int, default=256, help="--osd dl --cpu-check: failures that go through the host route")
     ap.add_argument("--order", type=int, default=3)
     ap.add_argument("--weight", type=float, default=-0.048, help="stored (pre-softplus) NMS-1 weight")
     ap.add_argument("--values", default=None, help="par/values.txt of the training stage (overrides --weight)")
@@ -149,10 +212,21 @@ def main():
         _, v = weights.parse_values_txt(args.values)
         stored = float([x for k, x in v.items() if "check" in k][0][0])
     alpha = float(softplus32(stored))                           # softplus, ms_test.py:207-208
-    dec = Decoder(Code(args.alist) if args.alist else Code(), local)
+    dl = None
+    if args.osd == "dl":
+        if not args.training:
+            ap.error("--osd dl needs --training DIR")
+        dl = dl_setup(args)
+        dec = dl["dec"]
+    else:
+        dec = Decoder(Code(args.alist) if args.alist else Code(), local)
 
     def make_pipe(B, snr):
         """The pipeline object of a batch size: the (128,64) one, or with --alist the one on the OSD families."""
+        if dl:
+            return DlOsdPipeline(dec, B, args.iters, alpha, dl["teps"], dl["off"], dl["win"], dl["margin"], dl["fcn"].packed(),
+                                 dl["nn"].packed() if dl["nn"] is not None else None, capacity=min(B, args.capacity) if args.capacity else None,
+                                 want_soft=False)
         if args.alist:
             return FamilyPipeline(dec, B, args.iters, alpha, osd_order=args.order, osd_algo=ALGOS[args.osd], snr_db=snr, want_soft=False)
         return BatchPipeline(dec, B, args.iters, alpha, osd_order=args.order, osd_algo=ALGOS[args.osd], snr_db=snr,
@@ -170,12 +244,12 @@ def main():
     torch.cuda.synchronize()
     for st in dstreams:
         with torch.cuda.stream(st):
-            if args.order is not None and not args.alist:      # (the families have no library workspace)
+            if args.order is not None and not args.alist and not dl:      # (the families have no library workspace)
                 dec.osd_reserve_stream(min(args.batch, max(mine, 1)), dec.osd_params(args.order, ALGOS[args.osd], snr_db=float(args.snr[0])))
             warm = make_pipe(yw.shape[0], float(args.snr[0])).bind(yw, lw)
             warm.run()
     torch.cuda.synchronize()
-    with_osd = args.order is not None
+    with_osd = args.order is not None or dl is not None
     max_batches = -(-shard_range(args.frames, 0, world)[1] // args.batch)       # rank 0 owns the largest shard
 
     def produce(B, snr, st, k):
@@ -201,6 +275,7 @@ def main():
         if not args.resident:
             ahead = [produce(sizes[0], snr, dstreams[0], 0)] if sizes else []
         taken = [0]
+        last = [None]  # the pipeline object of the last batch decoded (--osd dl --cpu-check reads its buffers)
         pool = {}      # (stream number, batch size) -> pipeline object of this point: its output buffers are made once, not per batch
 
         def decode_batch(B, snr=snr):
@@ -219,6 +294,7 @@ def main():
                 else:
                     pipe.reset_counters()
                 pipe.bind(y, lab).run()
+                last[0] = pipe
                 c = pipe.counters().clone()      # (the object's own counters are zeroed for its next batch on this stream)
                 done_ev = torch.cuda.Event()
                 done_ev.record(st)
@@ -228,18 +304,23 @@ def main():
             return c
 
         total, ran = sweep_point(decode_batch, mine, args.batch, max_batches, args.stop_errors, with_osd, device=dec.device,
-                                 width=12 if args.alist else 8)   # the point's exchange step(s)
+                                 width=15 if dl else 12 if args.alist else 8)   # the point's exchange step(s)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         if rank == 0:
             c = total.cpu().numpy()
             out = combine_fer(c, n=dec.n)
-            if args.alist:
+            if args.alist or dl:
                 out.update(code=[dec.n, dec.k], family=warm.family)
+            if dl:
+                out.update(path_blocks=len(dl["path"]), path_teps=int(dl["acc"][-1]), win=dl["win"], soft_margin=dl["margin"],
+                           dia=dl["nn"] is not None, capacity=warm.capacity)
             out.update(snr_db=snr, osd=args.osd, order=args.order, alpha=alpha, n_gpus=world, macro_batches=ran, gen=args.gen,
                        stop_errors=args.stop_errors, **{"frames_per_s_resident_inputs" if args.resident else "frames_per_s_incl_generation": int(c[0]) / dt},
                        stop_rule=("end-to-end errors >= %d, checked per macro-batch of %d x %d frames" % (args.stop_errors, args.batch, world)) if args.stop_errors else "none: every frame decoded")
-            if args.cpu_check:
+            if args.cpu_check and dl:
+                out["dl_vs_host"] = dl_cpu_check(dl, last[0], args.cpu_frames) if last[0] is not None else {"frames": 0, "agree": "not judged"}
+            elif args.cpu_check:
                 out["fer_vs_cpu"] = cpu_check(dec.code, alpha, args, snr, end_to_end_errors(c, with_osd), int(c[0]))
             print(json.dumps(out), flush=True)
         if args.cpu_check:

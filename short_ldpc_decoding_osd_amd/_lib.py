@@ -35,7 +35,7 @@ SYMBOLS = (
     "ldpc_dia_cnn", "ldpc_dia_cnn_grad",
     "ldpc_fcn_windows", "ldpc_fcn_grad",
     "ldpc_pipeline_run", "ldpc_pipeline_timing",
-    "ldpc_osd_merge", "ldpc_family_pipeline_run",
+    "ldpc_osd_merge", "ldpc_family_pipeline_run", "ldpc_dlosd_pipeline_run",
 )
 
 NMS_AUTO, NMS_GENERIC, NMS_QC16 = 0, 1, 2
@@ -95,6 +95,31 @@ class FamilyPipeline(C.Structure):
                 ("osd_capacity", C.c_int64),
                 ("d_cw", C.c_void_p), ("d_metric", C.c_void_p), ("d_best", C.c_void_p), ("d_ntep", C.c_void_p),
                 ("d_osd_counts", C.c_void_p), ("d_final_counts", C.c_void_p)]
+
+
+# ldpc_dlosd_pipeline.family (LDPC_HOSD_FAMILY_*) and the prefix of each H-form family's entry points
+HOSD_FAMILY_AUTO, HOSD_FAMILY_128, HOSD_FAMILY_X, HOSD_FAMILY_W, HOSD_FAMILY_L = 0, 1, 2, 3, 4
+HOSD_FAMILIES = {"hosd": HOSD_FAMILY_128, "hosdx": HOSD_FAMILY_X, "hosdw": HOSD_FAMILY_W, "hosdl": HOSD_FAMILY_L}
+
+
+class DlOsdPipeline(C.Structure):
+    """ldpc_dlosd_pipeline of include/ldpc_osd.h (device pointers as integers)."""
+    _fields_ = [("d_llr", C.c_void_p), ("B", C.c_int64), ("T", C.c_int32), ("nms_kernel", C.c_int32),
+                ("alpha", C.POINTER(C.c_float)), ("w_in", C.c_float), ("w_out", C.c_float),
+                ("d_soft", C.c_void_p), ("d_hard", C.c_void_p), ("d_fail", C.c_void_p),
+                ("d_label_bits", C.c_void_p), ("d_nms_counts", C.c_void_p),
+                ("osd_enable", C.c_int32), ("timing_slot", C.c_int32),
+                ("family", C.c_int32), ("merge", C.c_int32),
+                ("d_index", C.c_void_p), ("d_count", C.c_void_p), ("osd_capacity", C.c_int64),
+                ("cnn_weights", C.POINTER(C.c_float)), ("fcn_weights", C.POINTER(C.c_float)),
+                ("n_cnn_weights", C.c_int32), ("n_fcn_weights", C.c_int32),
+                ("d_teps", C.c_void_p), ("d_block_off", C.c_void_p),
+                ("nblk", C.c_int32), ("win", C.c_int32), ("group", C.c_int32), ("soft_margin", C.c_double),
+                ("d_rows", C.c_void_p), ("d_order_llr", C.c_void_p), ("d_metric_llr", C.c_void_p), ("d_list_labels", C.c_void_p),
+                ("d_lri", C.c_void_p), ("d_uidx", C.c_void_p), ("d_M", C.c_void_p), ("d_nswaps", C.c_void_p),
+                ("d_deep_limit", C.c_void_p), ("d_global_min", C.c_void_p), ("d_truth", C.c_void_p), ("d_success", C.c_void_p),
+                ("d_cw", C.c_void_p), ("d_metric", C.c_void_p), ("d_best", C.c_void_p), ("d_teps_evaluated", C.c_void_p),
+                ("d_dl_counts", C.c_void_p), ("d_final_counts", C.c_void_p)]
 
 
 TIMING_SLOTS = 64
@@ -174,6 +199,7 @@ def load():
         "ldpc_pipeline_timing": (C.c_int, [vp, i32, C.POINTER(f32)]),
         "ldpc_osd_merge": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp]),
         "ldpc_family_pipeline_run": (C.c_int, [vp, C.POINTER(FamilyPipeline), vp]),
+        "ldpc_dlosd_pipeline_run": (C.c_int, [vp, C.POINTER(DlOsdPipeline), vp]),
     }
     for op in ("front", "search", "sliding"):     # the any-shape, the wide and the long H-form family: the signatures of ldpc_hosd_*
         sig[f"ldpc_hosdx_{op}"] = sig[f"ldpc_hosdw_{op}"] = sig[f"ldpc_hosdl_{op}"] = sig[f"ldpc_hosd_{op}"]

@@ -7,7 +7,8 @@
 parser, G construction, GF(2) elimination, TEP tables, CRC-32C) and the C oracle under -fsanitize=address,undefined, as
 libldpcosd_asan.so / oracle/_build/libldpc_oracle_asan.so; --run then runs the host-side test files against them
 (LDPC_OSD_LIB / LDPC_ORACLE_LIB select the libraries, the sanitizer runtime is preloaded).  The host-side validation of
-ldpc_osd_merge and ldpc_family_pipeline_run (csrc/ldpc_family_check.h) is part of that library, and --run first runs a
+ldpc_osd_merge, ldpc_family_pipeline_run (csrc/ldpc_family_check.h) and ldpc_dlosd_pipeline_run (csrc/ldpc_dlosd_check.h) is part
+of that library, and --run first runs a
 stand-alone program on it (csrc/ldpc_sanitizer_main.cpp: contexts made by hand, no device, nothing preloaded).  Device code is never
 sanitized: GPU AddressSanitizer runs are not available on this pool.
 """

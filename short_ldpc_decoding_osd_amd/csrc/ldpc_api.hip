@@ -3,6 +3,8 @@
 
 #include "ldpc_internal.h"
 #include "ldpc_osd_family.h"   // FamilyStage: the OSD stage of ldpc_family_pipeline_run
+#include "ldpc_dlosd_check.h"  // dlosd_pipeline_check
+#include "ldpc_dlosd_stage.h"  // HosdStage and the other launches of ldpc_dlosd_pipeline_run
 
 using namespace ldpc;
 
@@ -276,6 +278,60 @@ int ldpc_family_pipeline_run(ldpc_ctx *ctx, const ldpc_family_pipeline *p, void 
                         osd_counting(p->d_label_bits, p->d_osd_counts), s))) return rc;
     LDPC_EV(4);
 #undef LDPC_EV
+    if (p->merge) return ldpc_osd_merge(ctx, p->d_cw, p->d_index, p->d_count, F, p->d_hard, p->d_label_bits, p->d_final_counts, stream);
+    return LDPC_OK;
+}
+
+int ldpc_dlosd_pipeline_run(ldpc_ctx *ctx, const ldpc_dlosd_pipeline *p, void *stream)
+{
+    int family, rc;
+    int64_t F;                          // the rows the list buffers hold
+    if ((rc = dlosd_pipeline_check(ctx, p, kDlosdWho, &family, &F))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipEvent_t *ev = nullptr;
+    unsigned *rec = nullptr;            // which of the slot's events THIS run records (ldpc_pipeline_timing reads only those)
+    if (p->timing_slot >= 0) {
+        ev = ctx->timing + p->timing_slot * 6;
+        rec = &ctx->timing_recorded[p->timing_slot];
+        *rec = 0;
+    }
+#define LDPC_EV(i) do { if (ev) { LDPC_HIP(hipEventRecord(ev[i], s)); *rec |= 1u << (i); } } while (0)
+    LDPC_EV(0);
+    if ((rc = ldpc_nms_decode(ctx, p->d_llr, p->B, p->T, p->alpha, p->w_in, p->w_out, p->d_soft, nullptr, p->d_hard,
+                              p->d_fail, p->nms_kernel, stream))) return rc;
+    LDPC_EV(1);
+    const bool want_eval = p->d_label_bits && p->d_nms_counts;
+    if (!p->osd_enable) {
+        if (want_eval && (rc = ldpc_eval_counts(ctx, p->d_hard, p->d_label_bits, p->d_fail, p->B, p->d_nms_counts, stream))) return rc;
+        return LDPC_OK;
+    }
+    if (want_eval && p->B > 0) {   // counters and the compaction's counting pass share one kernel
+        if ((rc = eval_and_compact(ctx, p->d_hard, p->d_label_bits, p->d_fail, p->B, p->d_nms_counts, p->d_index,
+                                   p->d_count, s))) return rc;
+    } else if ((rc = ldpc_compact(ctx, p->d_fail, p->B, p->d_index, p->d_count, stream))) return rc;
+    if (F == 0) return LDPC_OK;
+    const HosdStage &fam = family == LDPC_HOSD_FAMILY_L ? hosdl_stage() : hosd_stage(family);
+    LDPC_EV(2);
+    // without a CNN the ordering values are the channel values: the gather fills d_order_llr with them where the caller gave it,
+    // else front end and scan read d_metric_llr for both inputs
+    const float *xo = p->d_order_llr ? p->d_order_llr : p->d_metric_llr;
+    if (p->cnn_weights) {
+        if ((rc = ldpc_nms_traj_rows(ctx, p->d_llr, p->d_index, p->d_count, F, p->T, p->alpha, p->w_in, p->w_out, p->d_rows, p->nms_kernel,
+                                     stream))) return rc;
+        if ((rc = dia_cnn_counted(ctx, p->d_rows, p->d_count, F, p->T + 1, p->cnn_weights, p->d_order_llr, s))) return rc;
+        xo = p->d_order_llr;
+    }
+    if ((rc = dlosd_gather(ctx, p->d_llr, p->d_label_bits, p->d_index, p->d_count, F, p->d_metric_llr, p->cnn_weights ? nullptr : p->d_order_llr,
+                           p->d_list_labels, s))) return rc;
+    if ((rc = fam.front(ctx, xo, p->d_count, F, p->d_lri, p->d_uidx, p->d_M, p->d_nswaps, s))) return rc;
+    LDPC_EV(3);
+    if ((rc = fam.sliding(ctx, xo, p->d_metric_llr, p->d_count, F, p, p->d_label_bits ? p->d_list_labels : nullptr, s))) return rc;
+    LDPC_EV(4);
+#undef LDPC_EV
+    if (p->d_dl_counts &&
+        (rc = dlosd_counts(p->d_deep_limit, p->d_label_bits ? p->d_success : nullptr, p->d_label_bits ? p->d_global_min : nullptr,
+                           p->d_label_bits ? p->d_truth : nullptr, p->d_teps_evaluated, p->d_block_off, p->nblk, p->win,
+                           p->d_count, F, p->d_dl_counts, s))) return rc;
     if (p->merge) return ldpc_osd_merge(ctx, p->d_cw, p->d_index, p->d_count, F, p->d_hard, p->d_label_bits, p->d_final_counts, stream);
     return LDPC_OK;
 }

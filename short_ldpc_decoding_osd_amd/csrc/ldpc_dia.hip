@@ -30,10 +30,12 @@
 //                           in f64, written in the packed order of the weights.
 // The shape of both trees depends on (F, n, L) alone: repeated calls give the same bits on any stream.
 #include "ldpc_internal.h"
+#include "ldpc_wave.h"          // the counted form of dia_cnn_kernel
+#include "ldpc_dlosd_check.h"   // kDiaMaxL
+#include "ldpc_dlosd_stage.h"   // dia_cnn_counted
 
 namespace ldpc {
 
-constexpr int kDiaMaxL = 64;   // longest trajectory (T + 1) the weight block in the kernel arguments holds
 constexpr int kDiaMaxWeights = 24 + 96 + 24 + 2 * (kDiaMaxL - 6) + 1;
 constexpr int kDiaGradMaxBlocks = 4096;          // grid cap of dia_grad_kernel: a few workgroups per CU, 2 MiB of partials at most
 constexpr size_t kDiaGradLdsBudget = 48 * 1024;  // accumulators of one workgroup; the workgroup shrinks until they fit
@@ -93,9 +95,14 @@ __device__ __forceinline__ float dia_forward(const float *__restrict__ x, int L,
     return acc + w.bias;
 }
 
+template <class... COUNT>   // (the counted form: ldpc_wave.h)
 __global__ __launch_bounds__(256) void dia_cnn_kernel(const float *__restrict__ rows, long long F, int L, int n,
-                                                      DiaCnnArg w, float *__restrict__ out)
+                                                      DiaCnnArg w, float *__restrict__ out, COUNT... count)
 {
+    if constexpr (kCounted<COUNT...>) {
+        F = counted_frames(F, count...);
+        if ((long long)blockIdx.x * 256 >= F * n) return;   // (the grid is sized by the capacity, not by the count)
+    }
     const long long total = F * n;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const long long f = i / n;
@@ -236,7 +243,20 @@ static int launch_dia_cnn(const ldpc_ctx *ctx, const float *d_rows, int64_t F, i
     const int n = ctx->code.n;
     const long long total = F * n, want_blocks = (total + 255) / 256;
     const unsigned grid = (unsigned)(want_blocks < 65536 ? want_blocks : 65536);
-    hipLaunchKernelGGL(dia_cnn_kernel, dim3(grid), dim3(256), 0, st, d_rows, (long long)F, L, n, w, d_out);
+    hipLaunchKernelGGL(dia_cnn_kernel<>, dim3(grid), dim3(256), 0, st, d_rows, (long long)F, L, n, w, d_out);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+// ldpc_dia_cnn on min(*d_count, F) trajectories (ldpc_dlosd_pipeline_run, which validated L and the weights); the grid of F
+int dia_cnn_counted(const ldpc_ctx *ctx, const float *d_rows, const int32_t *d_count, int64_t F, int L, const float *weights, float *d_out,
+                    hipStream_t st)
+{
+    const int n = ctx->code.n;
+    const long long total = F * n, want_blocks = (total + 255) / 256;
+    const unsigned grid = (unsigned)(want_blocks < 65536 ? want_blocks : 65536);
+    hipLaunchKernelGGL(dia_cnn_kernel<const int *>, dim3(grid), dim3(256), 0, st, d_rows, (long long)F, L, n, dia_unpack(weights, L), d_out,
+                       (const int *)d_count);
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
 }

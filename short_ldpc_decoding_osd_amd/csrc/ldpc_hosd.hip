@@ -20,6 +20,8 @@
 #include "ldpc_internal.h"
 #include "ldpc_wave.h"
 #include "ldpc_hosd_scan.h"
+#include "ldpc_dlosd_check.h"   // hosd_family_refusal: the sentence of each family
+#include "ldpc_dlosd_stage.h"   // HosdStage: the counted launches of ldpc_dlosd_pipeline_run
 
 namespace ldpc {
 
@@ -30,12 +32,17 @@ struct __attribute__((aligned(16))) HFrontLds {
     unsigned char lri[128];    // sorted position -> original bit
 };
 
+template <class... COUNT>   // (the counted form: ldpc_wave.h)
 __global__ __launch_bounds__(256) void hosd_front_kernel(const float *__restrict__ x, long long F,
                                                          const u64 *__restrict__ Hcols,
                                                          unsigned char *__restrict__ lri_out,
                                                          unsigned char *__restrict__ uidx_out, u64 *__restrict__ M_out,
-                                                         int *__restrict__ nswaps)
+                                                         int *__restrict__ nswaps, COUNT... count)
 {
+    if constexpr (kCounted<COUNT...>) {
+        F = counted_frames(F, count...);
+        if ((long long)blockIdx.x * 4 >= F) return;   // (the grid is sized by the capacity, not by the count)
+    }
     __shared__ HFrontLds lds[4];
     const int lane = threadIdx.x & 63;
     HFrontLds &L = lds[threadIdx.x >> 6];
@@ -253,12 +260,13 @@ struct HostHosd128 {
     static int check(const ldpc_ctx *ctx, const char *)
     {
         if (ctx->hosd_ok) return LDPC_OK;
-        return fail(LDPC_E_UNSUPPORTED, "H-form OSD kernels need n=128, m=k=64; this code is n=%d m=%d k=%d", ctx->code.n, ctx->code.m,
-                    ctx->code.k);
+        return hosd_family_refusal(ctx, LDPC_HOSD_FAMILY_128, nullptr);
     }
     static const uint64_t *hcols(const ldpc_ctx *ctx) { return ctx->d_Hcols; }
-    static constexpr auto front = hosd_front_kernel;
-    static constexpr auto sliding = hosd_sliding_kernel;
+    static constexpr auto front = hosd_front_kernel<>;
+    static constexpr auto front_counted = hosd_front_kernel<const int *>;
+    static constexpr auto sliding = hosd_sliding_kernel<>;
+    static constexpr auto sliding_counted = hosd_sliding_kernel<const int *>;
     template <bool RUNS> static constexpr auto search = hosd_search_kernel<RUNS>;
     static std::tuple<> front_shape(const ldpc_code &) { return {}; }
     static std::tuple<> scan_shape(const ldpc_code &) { return {}; }
@@ -268,13 +276,13 @@ struct HostHosdX {
     static int check(const ldpc_ctx *ctx, const char *who)
     {
         if (ctx->hosdx_ok) return LDPC_OK;
-        const ldpc_code &c = ctx->code;
-        return fail(LDPC_E_UNSUPPORTED, "%s: H-form OSD kernels need 1 <= k <= 64 and an H of exactly n-k <= 64 rows; this H has %d rows, "
-                    "n-k = %d, code (%d,%d)", who, c.m, c.n - c.k, c.n, c.k);
+        return hosd_family_refusal(ctx, LDPC_HOSD_FAMILY_X, who);
     }
     static const uint64_t *hcols(const ldpc_ctx *ctx) { return ctx->d_Hcols; }
-    static constexpr auto front = hosdx_front_kernel;
-    static constexpr auto sliding = hosdx_sliding_kernel;
+    static constexpr auto front = hosdx_front_kernel<>;
+    static constexpr auto front_counted = hosdx_front_kernel<const int *>;
+    static constexpr auto sliding = hosdx_sliding_kernel<>;
+    static constexpr auto sliding_counted = hosdx_sliding_kernel<const int *>;
     template <bool RUNS> static constexpr auto search = hosdx_search_kernel<RUNS>;
     static std::tuple<int, int> front_shape(const ldpc_code &c) { return {c.n, c.m}; }
     static std::tuple<int, int> scan_shape(const ldpc_code &c) { return {c.n, c.n - c.k}; }   // (n - k == c.m wherever hosdx_ok holds)
@@ -284,13 +292,13 @@ struct HostHosdW {
     static int check(const ldpc_ctx *ctx, const char *who)
     {
         if (ctx->hosdw_ok) return LDPC_OK;
-        const ldpc_code &c = ctx->code;
-        return fail(LDPC_E_UNSUPPORTED, "%s: wide H-form OSD kernels need n <= 128, an H of 1 <= R <= 127 rows and 1 <= n-k <= 64; this H has "
-                    "%d rows, n-k = %d, code (%d,%d)", who, c.m, c.n - c.k, c.n, c.k);
+        return hosd_family_refusal(ctx, LDPC_HOSD_FAMILY_W, who);
     }
     static const uint64_t *hcols(const ldpc_ctx *ctx) { return ctx->d_HcolsW; }
-    static constexpr auto front = hosdw_front_kernel;
-    static constexpr auto sliding = hosdw_sliding_kernel;
+    static constexpr auto front = hosdw_front_kernel<>;
+    static constexpr auto front_counted = hosdw_front_kernel<const int *>;
+    static constexpr auto sliding = hosdw_sliding_kernel<>;
+    static constexpr auto sliding_counted = hosdw_sliding_kernel<const int *>;
     template <bool RUNS> static constexpr auto search = hosdw_search_kernel<RUNS>;
     static std::tuple<int, int, int> front_shape(const ldpc_code &c) { return {c.n, c.m, c.n - c.k}; }
     static std::tuple<int, int> scan_shape(const ldpc_code &c) { return {c.n, c.n - c.k}; }
@@ -308,8 +316,7 @@ static void hosd_launch(K kernel, unsigned blocks, void *stream, const std::tupl
 static const u64 *w64(const uint64_t *p) { return reinterpret_cast<const u64 *>(p); }
 static u64 *w64(uint64_t *p) { return reinterpret_cast<u64 *>(p); }
 
-// the classifier of the sliding scans and of ldpc_fcn_grad: its weight count for a window, and the kernel argument
-static int fcn_weight_count(int win) { return (win + 1) * (win + 1) + 2 * (win + 1); }
+// the classifier of the sliding scans and of ldpc_fcn_grad: the kernel argument (its weight count: ldpc_hosd_limits.h)
 static SlideFcnArg slide_fcn_arg(const float *fcn_weights, int win)
 {
     const int d = win + 1;
@@ -321,15 +328,20 @@ static SlideFcnArg slide_fcn_arg(const float *fcn_weights, int win)
 
 template <class FAM>
 static int hosd_front(const char *who, ldpc_ctx *ctx, const float *d_order_llr, int64_t F, uint8_t *d_lri, uint8_t *d_uidx, uint64_t *d_M,
-                      int32_t *d_nswaps, void *stream)
+                      int32_t *d_nswaps, void *stream, const int32_t *d_count = nullptr)
 {
     if (!ctx || F < 0) return fail(LDPC_E_ARG, "%s: bad arguments (ctx %p, F %lld)", who, (void *)ctx, (long long)F);
     if (F > 0)
         if (int rc = first_null(who, {{"d_order_llr", d_order_llr}, {"d_lri", d_lri}, {"d_uidx", d_uidx}, {"d_M", d_M}})) return rc;
     if (int rc = FAM::check(ctx, who)) return rc;
     if (F == 0) return LDPC_OK;
-    hosd_launch(FAM::front, grid_for(F, 4), stream, std::make_tuple(d_order_llr, (long long)F), FAM::front_shape(ctx->code),
-                std::make_tuple(w64(FAM::hcols(ctx)), d_lri, d_uidx, w64(d_M), d_nswaps));
+    const auto head = std::make_tuple(d_order_llr, (long long)F);
+    const auto tail = std::make_tuple(w64(FAM::hcols(ctx)), d_lri, d_uidx, w64(d_M), d_nswaps);
+    // (d_count: the counted form, on min(*d_count, F) frames -- ldpc_dlosd_pipeline_run alone)
+    if (d_count)
+        hosd_launch(FAM::front_counted, grid_for(F, 4), stream, head, FAM::front_shape(ctx->code), std::tuple_cat(tail, std::make_tuple((const int *)d_count)));
+    else
+        hosd_launch(FAM::front, grid_for(F, 4), stream, head, FAM::front_shape(ctx->code), tail);
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
 }
@@ -367,7 +379,8 @@ static int hosd_sliding(const char *who, ldpc_ctx *ctx, const float *d_order_llr
                         const uint8_t *d_uidx, const uint64_t *d_M, const uint8_t *d_teps, const int32_t *d_block_off, int32_t nblk,
                         int32_t win, double soft_margin, const float *fcn_weights, int32_t n_weights, int32_t group,
                         const uint64_t *d_label_bits, int32_t *d_deep_limit, float *d_global_min, float *d_truth, uint8_t *d_success,
-                        uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_teps_evaluated, void *stream)
+                        uint64_t *d_cw, float *d_metric, int32_t *d_best, int32_t *d_teps_evaluated, void *stream,
+                        const int32_t *d_count = nullptr)
 {
     if (!ctx || F < 0 || win < 1 || win > kSlideMaxWin || nblk < win || group < 0)
         return fail(LDPC_E_ARG, "%s: bad arguments (ctx %p, F %lld, win %d, nblk %d, group %d)", who, (void *)ctx, (long long)F,
@@ -382,12 +395,42 @@ static int hosd_sliding(const char *who, ldpc_ctx *ctx, const float *d_order_llr
     if (int rc = FAM::check(ctx, who)) return rc;
     if (nblk > kHosdMaxBlocks) return fail(LDPC_E_UNSUPPORTED, "%s: %d TEP blocks, at most %d", who, nblk, kHosdMaxBlocks);
     if (F == 0) return LDPC_OK;
-    hosd_launch(FAM::sliding, grid_for(F, 1), stream, std::make_tuple(d_order_llr, d_metric_llr, (long long)F), FAM::scan_shape(ctx->code),
-                std::make_tuple(d_lri, d_uidx, w64(d_M), reinterpret_cast<const uchar4 *>(d_teps), d_block_off, (int)nblk, (int)win,
-                                soft_margin, slide_fcn_arg(fcn_weights, win), (int)group, w64(d_label_bits), d_deep_limit, d_global_min,
-                                d_truth, d_success, w64(d_cw), d_metric, d_best, d_teps_evaluated));
+    const auto head = std::make_tuple(d_order_llr, d_metric_llr, (long long)F);
+    const auto tail = std::make_tuple(d_lri, d_uidx, w64(d_M), reinterpret_cast<const uchar4 *>(d_teps), d_block_off, (int)nblk, (int)win,
+                                      soft_margin, slide_fcn_arg(fcn_weights, win), (int)group, w64(d_label_bits), d_deep_limit, d_global_min,
+                                      d_truth, d_success, w64(d_cw), d_metric, d_best, d_teps_evaluated);
+    // (d_count: the counted form, on min(*d_count, F) frames -- ldpc_dlosd_pipeline_run alone)
+    if (d_count)
+        hosd_launch(FAM::sliding_counted, grid_for(F, 1), stream, head, FAM::scan_shape(ctx->code),
+                    std::tuple_cat(tail, std::make_tuple((const int *)d_count)));
+    else
+        hosd_launch(FAM::sliding, grid_for(F, 1), stream, head, FAM::scan_shape(ctx->code), tail);
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
+}
+
+// The three families of this unit as ldpc_dlosd_pipeline_run sees them: the host side above with the device-side count.
+template <class FAM>
+struct HosdStageOf {
+    static int front(ldpc_ctx *ctx, const float *xo, const int32_t *d_count, int64_t F, void *d_lri, void *d_uidx, uint64_t *d_M,
+                     int32_t *d_nswaps, hipStream_t s)
+    {
+        return hosd_front<FAM>(kDlosdWho, ctx, xo, F, static_cast<uint8_t *>(d_lri), static_cast<uint8_t *>(d_uidx), d_M, d_nswaps, s, d_count);
+    }
+    static int sliding(ldpc_ctx *ctx, const float *xo, const float *xm, const int32_t *d_count, int64_t F, const ldpc_dlosd_pipeline *p,
+                       const uint64_t *d_label, hipStream_t s)
+    {
+        return hosd_sliding<FAM>(kDlosdWho, ctx, xo, xm, F, static_cast<const uint8_t *>(p->d_lri), static_cast<const uint8_t *>(p->d_uidx),
+                                 p->d_M, p->d_teps, p->d_block_off, p->nblk, p->win, p->soft_margin, p->fcn_weights, p->n_fcn_weights,
+                                 p->group, d_label, p->d_deep_limit, p->d_global_min, d_label ? p->d_truth : nullptr,
+                                 d_label ? p->d_success : nullptr, p->d_cw, p->d_metric, p->d_best, p->d_teps_evaluated, s, d_count);
+    }
+};
+const HosdStage &hosd_stage(int family)
+{
+    static const HosdStage st128{HosdStageOf<HostHosd128>::front, HosdStageOf<HostHosd128>::sliding},
+        stx{HosdStageOf<HostHosdX>::front, HosdStageOf<HostHosdX>::sliding}, stw{HosdStageOf<HostHosdW>::front, HosdStageOf<HostHosdW>::sliding};
+    return family == LDPC_HOSD_FAMILY_128 ? st128 : family == LDPC_HOSD_FAMILY_X ? stx : stw;
 }
 
 }  // namespace ldpc

@@ -16,14 +16,13 @@
 #pragma once
 
 #include "ldpc_wave.h"
+#include "ldpc_hosd_limits.h"   // kHosdMaxBlocks, kSlideMaxWin
 
 namespace ldpc {
 
-constexpr int kHosdMaxBlocks = 1024;   // keys kept in LDS (8 KiB); the reference's paths have 30 blocks
 constexpr int kHosdLdsTeps = 2304;     // a TEP table up to this size (256 threads x 9) of weight <= 2 in <= kHosdRunBlocks blocks is kept in LDS,
 constexpr int kHosdRunBlocks = 128;    // two bytes per TEP, and scanned in per-thread runs (the reference's order-2 paths: 2081 TEPs, 28 blocks)
 constexpr int kHosdChunk = 256;        // larger tables: TEPs per work item (a block larger than this is split)
-constexpr int kSlideMaxWin = 15;       // window + the block index: at most 16 classifier inputs
 constexpr int kSlideGroupTeps = 256;   // default group: consecutive blocks until the group holds one TEP per thread
 
 struct HShape128 {                     // (128,64): the shape is compile-time constants
@@ -279,6 +278,7 @@ __device__ __forceinline__ float slide_p1(SlideLds &S, int win, const SlideFcnAr
 #define HOSD_NO_SHAPE_PARAMS
 #define HOSD_NM_SHAPE_PARAMS int n, int m,
 #define HOSD_SLIDING_KERNEL(NAME, FAM, SHAPE_PARAMS, SHAPE) \
+template <class... COUNT>   /* (the counted form: ldpc_wave.h) */                                                                     \
 __global__ __launch_bounds__(256) void NAME(const float *__restrict__ xo, const float *__restrict__ xm, long long F,                   \
                                                             SHAPE_PARAMS const unsigned char *__restrict__ lri,                        \
                                                             const unsigned char *__restrict__ uidx, const u64 *__restrict__ Mrows,     \
@@ -288,8 +288,12 @@ __global__ __launch_bounds__(256) void NAME(const float *__restrict__ xo, const 
                                                             float *__restrict__ gmin_out, float *__restrict__ truth,                   \
                                                             unsigned char *__restrict__ success, u64 *__restrict__ cw_out,             \
                                                             float *__restrict__ metric_out, int *__restrict__ best_out,                \
-                                                            int *__restrict__ nteps_out)                                               \
+                                                            int *__restrict__ nteps_out, COUNT... count)                               \
 {                                                                                                                                      \
+    if constexpr (kCounted<COUNT...>) {                                                                                                \
+        F = counted_frames(F, count...);                                                                                               \
+        if (blockIdx.x >= F) return;   /* (the grid is sized by the capacity, not by the count) */                                     \
+    }                                                                                                                                  \
     __shared__ FAM::Lds<false> L;                                                                                                      \
     __shared__ SlideLds S;                                                                                                             \
     const int tid = threadIdx.x, wave = tid >> 6;                                                                                      \

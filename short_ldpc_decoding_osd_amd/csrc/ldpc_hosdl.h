@@ -161,12 +161,16 @@ struct __attribute__((aligned(16))) HFrontLLds {
 //   M_out [F][64 Wm][Wk] u64          : entry [r][q] bits j = 64 q .. 64 q + 63 of row r of updated_M; rows >= m, bits >= k zero
 // The sort ranks every key against all n keys of the frame through LDS (every lane reads the same entry: a broadcast); the
 // keys are distinct, ascending |x| with ties to the lower index, and a padded slot has no key: it never sorts in front.
-template <int S, int W>
+template <int S, int W, class... COUNT>   // (the counted form: ldpc_wave.h)
 __global__ __launch_bounds__(64) void hosdl_front_kernel(const float *__restrict__ x, long long F, int n, int R, int m,
                                                          const u64 *__restrict__ Hcols, unsigned short *__restrict__ lri_out,
                                                          unsigned short *__restrict__ uidx_out, u64 *__restrict__ M_out,
-                                                         int *__restrict__ nswaps)
+                                                         int *__restrict__ nswaps, COUNT... count)
 {
+    if constexpr (kCounted<COUNT...>) {
+        F = counted_frames(F, count...);
+        if (blockIdx.x >= F) return;   // (the grid is sized by the capacity, not by the count)
+    }
     __shared__ HFrontLLds L;
     const int lane = threadIdx.x;
     const int k = n - m, Sn = (n + 63) >> 6, Wm = (m + 63) >> 6, Wk = (k + 63) >> 6;
@@ -600,7 +604,7 @@ __global__ __launch_bounds__(256) void hosdl_search_kernel(const float *__restri
 
 // The block scan with the reference's sliding-window early stop (sliding_osd :187-218): the text of HOSD_SLIDING_KERNEL
 // (ldpc_hosd_scan.h) on this family's set-up, run scan and epilogue.  Group rule, decision replay and results as there.
-template <int NW, int MW>
+template <int NW, int MW, class... COUNT>   // (the counted form: ldpc_wave.h)
 __global__ __launch_bounds__(256) void hosdl_sliding_kernel(const float *__restrict__ xo, const float *__restrict__ xm, long long F, int n, int m,
                                                             const unsigned short *__restrict__ lri, const unsigned short *__restrict__ uidx,
                                                             const u64 *__restrict__ Mrows, const uchar4 *__restrict__ teps,
@@ -609,8 +613,12 @@ __global__ __launch_bounds__(256) void hosdl_sliding_kernel(const float *__restr
                                                             int *__restrict__ deep_out, float *__restrict__ gmin_out,
                                                             float *__restrict__ truth, unsigned char *__restrict__ success,
                                                             u64 *__restrict__ cw_out, float *__restrict__ metric_out,
-                                                            int *__restrict__ best_out, int *__restrict__ nteps_out)
+                                                            int *__restrict__ best_out, int *__restrict__ nteps_out, COUNT... count)
 {
+    if constexpr (kCounted<COUNT...>) {
+        F = counted_frames(F, count...);
+        if (blockIdx.x >= F) return;   // (the grid is sized by the capacity, not by the count)
+    }
     __shared__ HSearchLLds<NW, MW, false> L;
     __shared__ SlideLds S;
     const int tid = threadIdx.x, wave = tid >> 6;

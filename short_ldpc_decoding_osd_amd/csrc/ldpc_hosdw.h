@@ -118,11 +118,16 @@ struct __attribute__((aligned(16))) HFrontWLds {
 // One frame per wavefront.  R rows of H as given, of rank m; Hcols [128][2]: column v of H, rows 0..63 / 64..127.
 // lri_out / uidx_out [F][128]: entries >= n are written as 0; M_out [F][128]: entry r < m bits j = 0..63 of row r of updated_M,
 // entry 64 + r bits j = 64..k-1; rows >= m and bits >= k are written as 0.
+template <class... COUNT>   // (the counted form: ldpc_wave.h)
 __global__ __launch_bounds__(256) void hosdw_front_kernel(const float *__restrict__ x, long long F, int n, int R, int m,
                                                           const u64 *__restrict__ Hcols, unsigned char *__restrict__ lri_out,
                                                           unsigned char *__restrict__ uidx_out, u64 *__restrict__ M_out,
-                                                          int *__restrict__ nswaps)
+                                                          int *__restrict__ nswaps, COUNT... count)
 {
+    if constexpr (kCounted<COUNT...>) {
+        F = counted_frames(F, count...);
+        if ((long long)blockIdx.x * 4 >= F) return;   // (the grid is sized by the capacity, not by the count)
+    }
     __shared__ HFrontWLds lds[4];
     const int lane = threadIdx.x & 63;
     HFrontWLds &L = lds[threadIdx.x >> 6];

@@ -28,11 +28,16 @@ struct __attribute__((aligned(16))) HFrontXLds {
 
 // One frame per wavefront.  lri_out / uidx_out [F][128]: entries >= n are written as 0; M_out [F][64]: rows >= m and bits >= k
 // are written as 0.
+template <class... COUNT>   // (the counted form: ldpc_wave.h)
 __global__ __launch_bounds__(256) void hosdx_front_kernel(const float *__restrict__ x, long long F, int n, int m,
                                                           const u64 *__restrict__ Hcols, unsigned char *__restrict__ lri_out,
                                                           unsigned char *__restrict__ uidx_out, u64 *__restrict__ M_out,
-                                                          int *__restrict__ nswaps)
+                                                          int *__restrict__ nswaps, COUNT... count)
 {
+    if constexpr (kCounted<COUNT...>) {
+        F = counted_frames(F, count...);
+        if ((long long)blockIdx.x * 4 >= F) return;   // (the grid is sized by the capacity, not by the count)
+    }
     __shared__ HFrontXLds lds[4];
     const int lane = threadIdx.x & 63;
     HFrontXLds &L = lds[threadIdx.x >> 6];

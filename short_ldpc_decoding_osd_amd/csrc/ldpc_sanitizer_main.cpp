@@ -1,8 +1,9 @@
 // Sanitizer build only (python -m short_ldpc_decoding_osd_amd.build --asan --run): a stand-alone program that drives the
-// host-side validation of ldpc_osd_merge and ldpc_family_pipeline_run (ldpc_sanitizer_checks.cpp over ldpc_family_check.h) under
-// -fsanitize=address,undefined.  No device: the contexts are made by hand, with the shape of a code and the k of each family's
+// host-side validation of ldpc_osd_merge, ldpc_family_pipeline_run and ldpc_dlosd_pipeline_run (ldpc_sanitizer_checks.cpp over
+// ldpc_family_check.h and ldpc_dlosd_check.h) under -fsanitize=address,undefined.  No device: the contexts are made by hand, with the shape of a code and the k of each family's
 // tables as ldpc_ctx_create would leave them, and every pointer is a host address that nothing dereferences.  A call that
 // passes validation ends in the stub's "exists only in the HIP build".  Exit status 0 when every expectation holds.
+#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -27,6 +28,11 @@ static ldpc_ctx *make_ctx(int n, int k)
     ctx->osd_tables.k = k <= 64 && m <= 64 ? k : 0;
     ctx->osdw_tables.k = n <= 128 && m <= 64 ? k : 0;
     ctx->osdl_tables.k = n <= 384 && k <= 192 && m <= 192 ? k : 0;
+    // the H-form families, as hosd_ctx_init / hosdl_ctx_init decide for an H of exactly n - k rows
+    ctx->hosdw_ok = n <= 128 && m >= 1 && m <= 64 && k >= 1 && k <= 127;
+    ctx->hosdx_ok = ctx->hosdw_ok && k <= 64;
+    ctx->hosd_ok = n == 128 && k == 64;
+    ctx->hosdl_ok = n <= 384 && m >= 1 && m <= 192 && k >= 1 && k <= 192;
     return ctx;
 }
 
@@ -118,6 +124,90 @@ int main()
     expect(ldpc_family_pipeline_run(c96, &p, nullptr), LDPC_E_ARG, "timing_slot 64", "timing_slot 64");
     p.timing_slot = 0;                                   // (a context made by hand has no event pool)
     expect(ldpc_family_pipeline_run(c96, &p, nullptr), LDPC_E_ARG, "timing_slot 0", "timing_slot without a pool");
+
+    // ---- ldpc_dlosd_pipeline_run
+    const char *dl = "ldpc_dlosd_pipeline_run: ";
+    ldpc_ctx *c128 = make_ctx(128, 64);
+    static float fcn[24], cnn[147];
+    ldpc_dlosd_pipeline dgood;
+    memset(&dgood, 0, sizeof(dgood));
+    dgood.d_llr = floats; dgood.B = 4; dgood.T = 6; dgood.alpha = alpha; dgood.w_in = dgood.w_out = 1.0f;   // (alpha is not read)
+    dgood.d_hard = words; dgood.d_fail = bytes; dgood.d_label_bits = words; dgood.osd_enable = 1; dgood.timing_slot = -1;
+    dgood.family = LDPC_HOSD_FAMILY_AUTO; dgood.merge = 1;
+    dgood.d_index = ints; dgood.d_count = ints;
+    dgood.cnn_weights = cnn; dgood.n_cnn_weights = 147; dgood.fcn_weights = fcn; dgood.n_fcn_weights = 24;
+    dgood.d_teps = bytes; dgood.d_block_off = ints; dgood.nblk = 10; dgood.win = 3; dgood.soft_margin = 0.5;
+    dgood.d_rows = floats; dgood.d_order_llr = floats; dgood.d_metric_llr = floats; dgood.d_list_labels = words;
+    dgood.d_lri = bytes; dgood.d_uidx = bytes; dgood.d_M = words; dgood.d_deep_limit = ints; dgood.d_cw = words; dgood.d_dl_counts = counts;
+    expect(ldpc_dlosd_pipeline_run(nullptr, &dgood, nullptr), LDPC_E_ARG, "ldpc_dlosd_pipeline_run: null argument", "dl ctx");
+    expect(ldpc_dlosd_pipeline_run(c96, nullptr, nullptr), LDPC_E_ARG, "ldpc_dlosd_pipeline_run: null argument", "dl p");
+    expect(ldpc_dlosd_pipeline_run(c128, &dgood, nullptr), LDPC_E_UNSUPPORTED, "validated: family 1, 4 list rows", "dl AUTO on (128,64)");
+    expect(ldpc_dlosd_pipeline_run(c96, &dgood, nullptr), LDPC_E_UNSUPPORTED, "validated: family 2, 4 list rows", "dl AUTO on (96,48)");
+    expect(ldpc_dlosd_pipeline_run(c121, &dgood, nullptr), LDPC_E_UNSUPPORTED, "validated: family 3, 4 list rows", "dl AUTO on (121,80)");
+    expect(ldpc_dlosd_pipeline_run(c384, &dgood, nullptr), LDPC_E_UNSUPPORTED, "validated: family 4, 4 list rows", "dl AUTO on (384,192)");
+    expect(ldpc_dlosd_pipeline_run(c1056, &dgood, nullptr), LDPC_E_UNSUPPORTED,
+           "ldpc_dlosd_pipeline_run: long H-form OSD kernels need n <= 384, an H of 1 <= R <= 192 rows, 1 <= n-k <= 192 and 1 <= k <= 192; "
+           "this H has 176 rows, n-k = 176, code (1056,880)", "dl AUTO on wimax");
+    ldpc_dlosd_pipeline d = dgood;
+    d.osd_enable = 0;
+    expect(ldpc_dlosd_pipeline_run(c1056, &d, nullptr), LDPC_E_UNSUPPORTED, "validated: family 0, 0 list rows", "dl NMS only on wimax");
+    d = dgood; d.family = LDPC_HOSD_FAMILY_128;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_UNSUPPORTED, "H-form OSD kernels need n=128, m=k=64; this code is n=96 m=48 k=48", "dl 128 forced on (96,48)");
+    d.family = LDPC_HOSD_FAMILY_X;
+    expect(ldpc_dlosd_pipeline_run(c121, &d, nullptr), LDPC_E_UNSUPPORTED,
+           "ldpc_dlosd_pipeline_run: H-form OSD kernels need 1 <= k <= 64 and an H of exactly n-k <= 64 rows; this H has 41 rows", "dl X forced on (121,80)");
+    d.family = LDPC_HOSD_FAMILY_W;
+    expect(ldpc_dlosd_pipeline_run(c384, &d, nullptr), LDPC_E_UNSUPPORTED, "ldpc_dlosd_pipeline_run: wide H-form OSD kernels need n <= 128", "dl W forced on (384,192)");
+    d.family = LDPC_HOSD_FAMILY_L;
+    expect(ldpc_dlosd_pipeline_run(c128, &d, nullptr), LDPC_E_UNSUPPORTED, "validated: family 4", "dl L forced on (128,64)");
+    d.family = 5;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "family 5 is no LDPC_HOSD_FAMILY_* value", "dl family 5");
+    d = dgood; d.osd_capacity = 3;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_UNSUPPORTED, "validated: family 2, 3 list rows", "dl capacity 3");
+    d.osd_capacity = -1;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "osd_capacity -1 is negative", "dl capacity -1");
+    d = dgood; d.win = 0;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "win 0 outside 1..15", "dl win 0");
+    d.win = 16;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "win 16 outside 1..15", "dl win 16");
+    d = dgood; d.nblk = 2;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "nblk 2 is below win 3", "dl nblk < win");
+    d.nblk = 1025;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_UNSUPPORTED, "nblk 1025 TEP blocks, at most 1024", "dl nblk 1025");
+    d = dgood; d.group = -1;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "group -1 is negative", "dl group");
+    d = dgood; d.n_fcn_weights = 23;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "n_fcn_weights 23, a window of 3 takes 24", "dl n_fcn_weights");
+    d = dgood; d.n_cnn_weights = 149;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "n_cnn_weights 149, T + 1 = 7 rows take 147", "dl n_cnn_weights");
+    d = dgood; d.T = 4;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "cnn_weights with T 4", "dl T + 1 < 7 with a CNN");
+    d.cnn_weights = nullptr; d.d_rows = nullptr; d.d_order_llr = nullptr;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_UNSUPPORTED, "validated: family 2", "dl no CNN: any T, no rows");
+    const struct { const char *name; size_t off; } required[] = {
+        {"fcn_weights", offsetof(ldpc_dlosd_pipeline, fcn_weights)}, {"d_rows", offsetof(ldpc_dlosd_pipeline, d_rows)},
+        {"d_order_llr", offsetof(ldpc_dlosd_pipeline, d_order_llr)}, {"d_index", offsetof(ldpc_dlosd_pipeline, d_index)},
+        {"d_count", offsetof(ldpc_dlosd_pipeline, d_count)}, {"d_teps", offsetof(ldpc_dlosd_pipeline, d_teps)},
+        {"d_block_off", offsetof(ldpc_dlosd_pipeline, d_block_off)}, {"d_metric_llr", offsetof(ldpc_dlosd_pipeline, d_metric_llr)},
+        {"d_lri", offsetof(ldpc_dlosd_pipeline, d_lri)}, {"d_uidx", offsetof(ldpc_dlosd_pipeline, d_uidx)},
+        {"d_M", offsetof(ldpc_dlosd_pipeline, d_M)}, {"d_cw", offsetof(ldpc_dlosd_pipeline, d_cw)},
+        {"d_list_labels", offsetof(ldpc_dlosd_pipeline, d_list_labels)}, {"d_deep_limit", offsetof(ldpc_dlosd_pipeline, d_deep_limit)}};
+    for (const auto &r : required) {
+        d = dgood;
+        memset((char *)&d + r.off, 0, sizeof(void *));
+        char want[96];
+        snprintf(want, sizeof(want), "%s%s is NULL", dl, r.name);
+        expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, want, r.name);
+    }
+    d = dgood; d.d_label_bits = nullptr; d.d_list_labels = nullptr;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_UNSUPPORTED, "validated: family 2", "dl no labels, no list labels");
+    d = dgood; d.d_dl_counts = nullptr; d.d_deep_limit = nullptr;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_UNSUPPORTED, "validated: family 2", "dl no stage counters, no deep_limit");
+    d = dgood; d.d_hard = nullptr;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "ldpc_dlosd_pipeline_run: d_hard and d_fail are required", "dl d_hard");
+    d = dgood; d.timing_slot = LDPC_TIMING_SLOTS;
+    expect(ldpc_dlosd_pipeline_run(c96, &d, nullptr), LDPC_E_ARG, "ldpc_dlosd_pipeline_run: timing_slot 64", "dl timing_slot 64");
+    delete c128;
     delete c121; delete c96; delete c384; delete c1056;
     printf("%s: %d failure(s)\n", failures ? "FAILED" : "ok", failures);
     return failures ? 1 : 0;

@@ -7,6 +7,7 @@
 // int64 per bit).
 #include "ldpc_internal.h"
 #include "ldpc_family_check.h"   // osd_merge_check
+#include "ldpc_dlosd_stage.h"    // dlosd_gather, dlosd_counts
 
 namespace ldpc {
 
@@ -87,6 +88,71 @@ __global__ __launch_bounds__(256) void osd_merge_kernel(const unsigned long long
         if (threadIdx.x < 4)
             atomicAdd(&counts[threadIdx.x], part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// The two small kernels of ldpc_dlosd_pipeline_run, both on the listed frames j < min(*count, F) and with no workspace.
+// dlosd_gather_kernel: the H-form calls take dense rows, so xm[j] = llr[index[j]] (n floats) and, with labels,
+// list_label[j] = label[index[j]] (`words` words), and xo[j] = xm[j] where the caller wants the ordering values of DIA = False in a
+// buffer of their own.  One wavefront per listed frame, consecutive lanes on consecutive
+// elements; V4: 16-byte loads and stores, for n a multiple of 4 (then every row of both arrays is 16-byte aligned).
+// dlosd_counts_kernel: counts[6] += {frames, frames with success, frames without, sum of deep - win + 1, sum of
+// block_off[deep], sum of nteps}; success is the scan's byte or, without it, gmin[j] == truth[j] (the scan's own comparison, on
+// the two floats it wrote); with neither, and without nteps, their counters stay.  block_off has nblk + 1 entries and
+// the sliding scans write win <= deep <= nblk; the index is clamped all the same, so nothing beyond block_off[nblk] is read
+// whatever the buffer holds.  Per-wave reduction by shuffles, one atomic per counter and block.
+// ---------------------------------------------------------------------------------------
+template <bool V4>
+__global__ __launch_bounds__(256) void dlosd_gather_kernel(const float *__restrict__ llr, const unsigned long long *__restrict__ label,
+                                                           const int *__restrict__ index, const int *__restrict__ count, long long F,
+                                                           int n, int words, float *__restrict__ xm, float *__restrict__ xo,
+                                                           unsigned long long *__restrict__ list_label)
+{
+    const long long c = *count, nframes = c < F ? c : F;
+    if ((long long)blockIdx.x * 4 >= nframes) return;   // (the whole block: the grid is sized by F, not by the count)
+    const int lane = threadIdx.x & 63;
+    for (long long j = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); j < nframes; j += (long long)gridDim.x * 4) {
+        const long long f = index[j];
+        if constexpr (V4) {
+            const float4 *__restrict__ src = reinterpret_cast<const float4 *>(llr + f * n);
+            float4 *__restrict__ dst = reinterpret_cast<float4 *>(xm + j * n);
+            float4 *__restrict__ dst2 = reinterpret_cast<float4 *>(xo + j * n);
+            for (int v = lane; v < (n >> 2); v += 64) { const float4 t = src[v]; dst[v] = t; if (xo) dst2[v] = t; }
+        } else {
+            for (int v = lane; v < n; v += 64) { const float t = llr[f * n + v]; xm[j * n + v] = t; if (xo) xo[j * n + v] = t; }
+        }
+        if (label)
+            for (int w = lane; w < words; w += 64) list_label[j * words + w] = label[f * words + w];
+    }
+}
+
+__global__ __launch_bounds__(256) void dlosd_counts_kernel(const int *__restrict__ deep, const unsigned char *__restrict__ success,
+                                                           const float *__restrict__ gmin, const float *__restrict__ truth,
+                                                           const int *__restrict__ nteps, const int *__restrict__ block_off, int nblk,
+                                                           int win, const int *__restrict__ count, long long F,
+                                                           unsigned long long *__restrict__ counts)
+{
+    __shared__ unsigned long long part[4][6];
+    const long long c = *count, nframes = c < F ? c : F;
+    if ((long long)blockIdx.x * blockDim.x >= nframes) return;   // (the whole block: the grid is sized by F, not by the count)
+    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};
+    for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < nframes; j += (long long)gridDim.x * blockDim.x) {
+        const int dl = deep[j], at = dl < 0 ? 0 : (dl < nblk ? dl : nblk);
+        v[0] += 1;
+        if (success || (gmin && truth)) { const bool ok = success ? success[j] != 0 : gmin[j] == truth[j]; v[1] += ok; v[2] += !ok; }
+        v[3] += (unsigned long long)(long long)(dl - win + 1);
+        v[4] += (unsigned long long)(long long)block_off[at];
+        if (nteps) v[5] += (unsigned long long)(long long)nteps[j];
+    }
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const unsigned long long s = wave_sum(v[i]);
+        if ((threadIdx.x & 63) == 0) part[wave][i] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 6)
+        atomicAdd(&counts[threadIdx.x], part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -375,6 +441,28 @@ int eval_and_compact(ldpc_ctx *ctx, const uint64_t *d_hard, const uint64_t *d_la
     launch_compact<true>(d_fail, B, d_index, d_count, reinterpret_cast<const unsigned long long *>(d_hard),
                          reinterpret_cast<const unsigned long long *>(d_label), (ctx->code.n + 63) / 64,
                          reinterpret_cast<unsigned long long *>(d_counts), st);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+// the gather and the stage counters of ldpc_dlosd_pipeline_run (ldpc_dlosd_stage.h), F > 0
+int dlosd_gather(const ldpc_ctx *ctx, const float *d_llr, const uint64_t *d_label_bits, const int32_t *d_index, const int32_t *d_count, int64_t F,
+                 float *d_metric_llr, float *d_order_llr, uint64_t *d_list_labels, hipStream_t st)
+{
+    const int n = ctx->code.n, words = (n + 63) / 64;
+    const bool v4 = n % 4 == 0 && ((uintptr_t)d_llr | (uintptr_t)d_metric_llr | (uintptr_t)d_order_llr) % 16 == 0;
+    hipLaunchKernelGGL(v4 ? dlosd_gather_kernel<true> : dlosd_gather_kernel<false>, dim3(grid_for(F, 4, 8192)), dim3(256), 0, st, d_llr,
+                       reinterpret_cast<const unsigned long long *>(d_label_bits), d_index, d_count, (long long)F, n, words, d_metric_llr,
+                       d_order_llr, reinterpret_cast<unsigned long long *>(d_list_labels));
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+int dlosd_counts(const int32_t *d_deep_limit, const uint8_t *d_success, const float *d_global_min, const float *d_truth, const int32_t *d_teps_evaluated, const int32_t *d_block_off, int nblk,
+                 int win, const int32_t *d_count, int64_t F, int64_t *d_dl_counts, hipStream_t st)
+{
+    hipLaunchKernelGGL(dlosd_counts_kernel, dim3(grid_for(F, 256, 1024)), dim3(256), 0, st, d_deep_limit, d_success, d_global_min, d_truth, d_teps_evaluated,
+                       d_block_off, nblk, win, d_count, (long long)F, reinterpret_cast<unsigned long long *>(d_dl_counts));
     LDPC_HIP(hipGetLastError());
     return LDPC_OK;
 }

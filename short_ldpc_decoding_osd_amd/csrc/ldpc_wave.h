@@ -18,6 +18,14 @@ __device__ __forceinline__ long long frame_count(const int *count, long long F)
     return nframes;
 }
 
+// The counted form of a kernel whose entry point takes a host F (the H-form front ends and sliding scans, dia_cnn_kernel): the
+// kernel ends in a pack `COUNT... count` that is empty -- the kernel the entry point launches, the code it was without the
+// pack -- or one `const int *`: min(*count, F) frames, F the capacity that sized the grid (ldpc_dlosd_pipeline_run).  The
+// count is its own instantiation and no nullable parameter: routing a count through frame_count rescheduled ldpc_osd_fs.h's
+// and ldpc_osd_scan2r.h's kernels, and the entry points' kernels must not move.
+template <class... COUNT> constexpr bool kCounted = sizeof...(COUNT) != 0;
+__device__ __forceinline__ long long counted_frames(long long F, const int *count) { return frame_count(count, F); }
+
 // ---------------------------------------------------------------------------------------
 // wave-level helpers
 // ---------------------------------------------------------------------------------------

@@ -38,6 +38,8 @@ def end_to_end_errors(counters, with_osd: bool) -> int:
     """Frames still wrong at the end of the path: OSD failures + NMS errors the syndrome did not flag (they are never
     post-processed, ms_test.py:51); without an OSD stage the NMS frame errors."""
     c = [int(x) for x in counters]
+    if with_osd and len(c) == 15:           # DlOsdPipeline: the merged frames still wrong sit behind the six stage counters
+        return c[12] + c[3]
     return c[6] + c[3] if with_osd else c[1]
 
 
@@ -62,7 +64,8 @@ def sweep_point(decode_batch, frames_mine: int, batch: int, max_batches: int, st
     is what the gloo tests use).
 
     ``width``: the number of counters ``decode_batch`` returns, i.e. the length of the zero tensor of a rank without frames: 8
-    for ``BatchPipeline``, 12 for ``FamilyPipeline`` (the four of the merge follow).  The stop rule reads the first eight.
+    for ``BatchPipeline``, 12 for ``FamilyPipeline`` (the four of the merge follow), 15 for ``DlOsdPipeline`` (five of NMS, six of
+    the stage, four of the merge).  The stop rule reads the first eight, at width 15 undetected + merged wrong.
 
     Returns (reduced int64[width] totals, macro-batches run)."""
     def zeros():
@@ -95,10 +98,30 @@ def combine_fer(counters, n=None) -> dict:
 
     With the 12 counters of ``FamilyPipeline`` -- then {merged, merged_wrong, bit_err_after, bit_err_before} of the merge -- the
     bit errors of the final decisions as well: ``bit_err_end_to_end`` = bit_err - bit_err_before + bit_err_after, and with the
-    code length ``n`` the rates ``ber_nms`` and ``ber_end_to_end`` over frames x n bits."""
+    code length ``n`` the rates ``ber_nms`` and ``ber_end_to_end`` over frames x n bits.
+
+    With the 15 counters of ``DlOsdPipeline``: ``fer_end_to_end`` (undetected + merged wrong), the bit errors and rates as above,
+    the stage's own failure rate ``fer_dl_given_fail`` (global_min != truth), and ``mean_windows`` / ``mean_complexity`` /
+    ``mean_teps`` per frame that went through the stage."""
     c = [int(x) for x in counters]
     frames = max(c[0], 1)
     out = {"frames": c[0], "fer_nms": c[1] / frames, "synd_fail_rate": c[4] / frames, "undetected": c[3]}
+    if len(c) == 15:
+        # DlOsdPipeline: {5 NMS; stage frames, success, failure, windows, complexity, teps evaluated; 4 merge}.  The stage's own
+        # success is global_min == truth (the reference's S / F); the end-to-end rates come from the merged decisions.
+        staged = c[5]
+        out["stage_frames"], out["left_out"] = staged, c[4] - staged      # left_out > 0: the capacity was below the failures
+        if staged > 0:
+            out["fer_dl_given_fail"] = c[7] / staged
+            out["mean_windows"] = c[8] / staged
+            out["mean_complexity"] = c[9] / staged
+            out["mean_teps"] = c[10] / staged
+        out["fer_end_to_end"] = (c[3] + c[12]) / frames                   # undetected + merged wrong
+        out["bit_err_end_to_end"] = c[2] - c[14] + c[13]
+        if n is not None:
+            out["ber_nms"] = c[2] / (frames * int(n))
+            out["ber_end_to_end"] = out["bit_err_end_to_end"] / (frames * int(n))
+        return out
     if len(c) >= 8 and c[5] > 0:
         out["fer_osd_given_fail"] = c[6] / c[5]
         out["fer_product"] = out["synd_fail_rate"] * out["fer_osd_given_fail"]
