@@ -3,13 +3,13 @@
 // (ldpc_osd.hip) and the fused PB-OSD head (pb_singles_kernel, ldpc_pb_singles.h).
 #pragma once
 #include "ldpc_internal.h"
+#include "ldpc_bits.h"
 #include "ldpc_wave.h"
 
 namespace ldpc {
 
 struct __attribute__((aligned(16))) FrontLds {
-    RankLds rank;            // reliability sort (bucket_ranks, ldpc_wave.h)
-    u64 colbuf[64];          // parity columns in primed order
+    RankLds rank;            // reliability sort (bucket_ranks, ldpc_wave.h); afterwards its first 1 KiB: the transposition's scratch
     unsigned mask[4];        // 128-bit membership mask of the MRB indices
     unsigned char pi1[128];  // sorted position -> original bit
     unsigned char rowsrc[64];
@@ -65,12 +65,33 @@ __device__ __forceinline__ FrontResult front_device_vals(FrontLds &L, unsigned a
     }
     L.perm[rankM] = L.pi1[idx1];
     L.perm[64 + rankL] = L.pi1[idx2];
-    L.colbuf[rankL] = C2;
     L.rowsrc[rankM] = (unsigned char)rho;          // pivot of MRB slot `lane` is physical row rho
+    // ---- rows of P': the 64x64 bit transposition of the parity columns, with rankL and rowsrc folded into LDS addresses ----
+    // The lane's column (bit = physical row) goes to LDS a byte at a time: byte g of column c at ta[64 g + c], so the eight
+    // bytes at ta[8 (8 g + cb)] are the 8x8 block of rows 8 g .. 8 g + 7 and columns 8 cb .. 8 cb + 7, one column per byte.
+    // Lane 8 g + cb transposes that block in registers (transpose8x8: one row per byte) and scatters it row-major, byte cb of
+    // row 8 g + i at tb[8 (8 g + i) + cb]; row rowsrc[lane] is then one 64-bit read.  Where the cross-lane form (transpose64
+    // and a shfl64 by rowsrc) took 14 ds_bpermute and six butterfly stages, this takes 16 byte stores, two 64-bit reads and the
+    // block transpose.  The scratch is the sort's key array, dead since the ranks were formed (the fence behind pi1); the
+    // next frame's sort writes it again behind the last fence below.
+    unsigned char *const ta = reinterpret_cast<unsigned char *>(L.rank.bk), *const tb = ta + 512;
+    {
+        const unsigned lo = (unsigned)C2, hi = (unsigned)(C2 >> 32);
+        unsigned char *const a = ta + rankL;
+        a[0] = (unsigned char)lo; a[64] = (unsigned char)(lo >> 8); a[128] = (unsigned char)(lo >> 16); a[192] = (unsigned char)(lo >> 24);
+        a[256] = (unsigned char)hi; a[320] = (unsigned char)(hi >> 8); a[384] = (unsigned char)(hi >> 16); a[448] = (unsigned char)(hi >> 24);
+    }
     wave_fence();
-    const u64 R = transpose64(L.colbuf[lane], lane);   // lane = physical row, bit = parity column
+    {
+        const u64 blk = transpose8x8(*reinterpret_cast<const u64 *>(ta + 8 * lane));
+        const unsigned lo = (unsigned)blk, hi = (unsigned)(blk >> 32);
+        unsigned char *const b = tb + (((lane >> 3) << 6) | (lane & 7));
+        b[0] = (unsigned char)lo; b[8] = (unsigned char)(lo >> 8); b[16] = (unsigned char)(lo >> 16); b[24] = (unsigned char)(lo >> 24);
+        b[32] = (unsigned char)hi; b[40] = (unsigned char)(hi >> 8); b[48] = (unsigned char)(hi >> 16); b[56] = (unsigned char)(hi >> 24);
+    }
+    wave_fence();
     FrontResult res;
-    res.Prow = shfl64(R, L.rowsrc[lane]);
+    res.Prow = *reinterpret_cast<const u64 *>(tb + 8 * L.rowsrc[lane]);
     res.o1 = L.perm[lane];
     res.o2 = L.perm[64 + lane];
     res.ns = ns;

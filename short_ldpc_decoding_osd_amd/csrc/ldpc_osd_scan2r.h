@@ -239,7 +239,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void os
 // results: front end AND scan of a frame in ONE wavefront, back to back -- the permutation, the rows of P' and the primed
 // channel values pass from one to the other in registers and LDS and never touch memory.  Two launches moved 640 B of
 // workspace per frame out and in again and read y twice (PMC, round 3: 41 + 49 MB per 33.5 k frames against 18 MB
-// algorithmic: 5.1x); this form reads 512 B and writes 24 B per frame.  The front end's 3.6 KiB of LDS lie inside the
+// algorithmic: 5.1x); this form reads 512 B and writes 24 B per frame.  The front end's 3.1 KiB of LDS lie inside the
 // scan's LUT area (built afterwards), the frame's y row in its P' rows (filled afterwards): 9.5 KiB, 16 wavefronts per CU.
 // ---------------------------------------------------------------------------------------
 template <int DIR>
